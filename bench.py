@@ -32,6 +32,7 @@ After the timed loop (outside it) rank 0 at N = 1
     primitive tests per cast, lanes active per phase), the NIF MLP kernel (K3) on 1440^2 rays and the 16-spp
     preview frame,
   * times the CPU oracle on a bounded pixel sample (`cpu_baseline`).
+With `--dump-outputs DIR` every launch form also writes what its timed steps computed, as .npy files (dump_outputs()).
 
 Prints ONE JSON line on rank 0.
 """
@@ -243,6 +244,9 @@ def bench_group(args, torch, irl):
     elapsed = time.perf_counter() - t0
     c = grp.counters()
     moved = grp.last_transfer()
+    if args.dump_outputs:
+        recs = grp.download(host_rays.copy())
+        dump_outputs(args.dump_outputs, records_frame(recs, width, height), recs)
     out = {
         "metric": "rays/sec (ray casts/s: CompactBvh intersect+occluded calls, whole node), built-in scene 1440x1440 path-trace",
         "value": c["casts"] / elapsed, "unit": "rays/s", "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
@@ -282,6 +286,66 @@ def bench_group(args, torch, irl):
     emit(out)
     if rc:
         sys.exit(rc)
+
+
+DUMP_BUDGET = 64 << 20          # --dump-outputs: bytes of .npy data at most
+DUMP_FULL_FRAME = 40 << 20      # the rgb frame goes out whole up to this size, else as a fixed sample of pixels
+DUMP_PIXELS = 1 << 21           # size of that sample
+DUMP_RECORDS = 1 << 16          # TraceResults (all 84 bytes) of a fixed sample of pixels
+DUMP_SEED = 1442
+
+
+def dump_outputs(out_dir, frame, records=None):
+    """--dump-outputs DIR: what the timed path had computed after its last step, as DIR/<name>.npy (float32 / float64, at
+    most DUMP_BUDGET bytes), so that two builds run with the same arguments can be compared output for output.
+      frame.npy                 [height, width, 3] float32: the rgb frame (accumulated over warm-up + timed frames)
+        - or, for frames above DUMP_FULL_FRAME bytes, frame_sample.npy [S, 3] float32 with frame_sample_pixel.npy [S]
+          float64 (row-major pixel index), S = DUMP_PIXELS pixels drawn with a fixed seed
+      records_sample.npy        [R, 22] float64: every field of the TraceResult of R = DUMP_RECORDS pixels drawn with a fixed
+                                seed, in the record's field order (rgb xyz, u, v, ray origin xyz, tMin, direction xyz, tMax,
+                                primID, normal xyz, throughput xyz, geomID, flags; integers exactly), with
+                                records_sample_pixel.npy [R] float64; only where the caller receives the records (not for
+                                the N > 1 ranks launch, whose rank 0 receives the gathered rgb frame alone)
+      records_sample_nonfinite.npy  [R, 22] float32: 0 where that entry of records_sample is the record's own finite value,
+                                else what the record holds there (+1 = +inf, -1 = -inf, 2 = NaN) while records_sample holds 0.
+                                (A ray whose last segment left the scene keeps tMax = +inf: most records of a frame have one.)
+    `frame`: [height, width, 3] float32; `records`: TRACE_RESULT array of the whole frame in row-major pixel order, or None."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    height, width = frame.shape[:2]
+    n = width * height
+    arrays = {}
+    if frame.nbytes <= DUMP_FULL_FRAME:
+        arrays["frame"] = np.ascontiguousarray(frame, dtype=np.float32)
+    else:
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_PIXELS, replace=False))
+        arrays["frame_sample"] = np.ascontiguousarray(frame.reshape(n, 3)[pix], dtype=np.float32)
+        arrays["frame_sample_pixel"] = pix.astype(np.float64)
+    if records is not None:
+        assert records.size == n
+        pix = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(n, min(n, DUMP_RECORDS), replace=False))
+        with np.errstate(invalid="ignore"):        # (a signalling NaN comes out quiet: the only value that is not kept exactly)
+            vals = np.stack([f.astype(np.float64) for f in leaf_fields(records[pix])], 1)
+        code = np.where(np.isnan(vals), 2.0, np.where(np.isinf(vals), np.sign(vals), 0.0)).astype(np.float32)
+        arrays["records_sample"] = np.where(code == 0, vals, 0.0)
+        arrays["records_sample_nonfinite"] = code
+        arrays["records_sample_pixel"] = pix.astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET, f"--dump-outputs: {total} bytes is over the {DUMP_BUDGET}-byte budget"
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+
+
+def leaf_fields(a):
+    """The scalar fields of a structured array, depth first in declaration order."""
+    if a.dtype.names is None:
+        return [a]
+    return [leaf for name in a.dtype.names for leaf in leaf_fields(a[name])]
+
+
+def records_frame(records, width, height):
+    """[height, width, 3] float32 rgb of a row-major TRACE_RESULT frame."""
+    return np.stack([records["rgb"][k] for k in "xyz"], 1).astype(np.float32).reshape(height, width, 3)
 
 
 def claim_stdout():
@@ -324,6 +388,9 @@ def main():
                                                                               "sharing the visible GPUs rehearses the ranks path on a box with fewer GPUs than ranks)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle legs (parity spot check and CPU baseline)")
     ap.add_argument("--no-extras", action="store_true", help="skip the instrumented probe, the NIF kernel and the 16-spp frame (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (the frame after the last step, a fixed sample of its TraceResults) "
+                         "as DIR/<name>.npy, at most 64 MB; see dump_outputs()")
     args = ap.parse_args()
 
     import torch
@@ -428,11 +495,17 @@ def main():
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
         elapsed = float(tmax[0])
     total_casts, total_paths = float(tot[1]), float(tot[2])
+    if args.dump_outputs and dist is None:
+        # the ray stream as the last timed step left it (one rank: every pixel, row-major)
+        recs = d_rays.cpu().numpy().view(irl.TRACE_RESULT).reshape(n)
+        frame = np.zeros((height, width, 3), np.float32)
+        frame[rows, cols] = np.stack([recs["rgb"][k] for k in "xyz"], 1)
+        dump_outputs(args.dump_outputs, frame, recs)
 
     # N > 1: one more gather behind the timed region (a collective: every rank takes part), so that rank 0 can check the
     # GATHERED frame - dealing, every rank's render and the collective - against the oracle
     final_frame = None
-    if dist is not None and not args.no_cpu_baseline:
+    if dist is not None and (not args.no_cpu_baseline or args.dump_outputs):
         final_frame = gather()
         if final_frame is not None:
             final_frame = final_frame.cpu().numpy()
@@ -441,6 +514,8 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.dump_outputs and final_frame is not None:
+        dump_outputs(args.dump_outputs, final_frame.astype(np.float32, copy=False))
 
     frames_rendered = args.warmup + args.steps
     casts_per_launch = counters["casts"] / max(args.steps, 1)
@@ -626,7 +701,7 @@ def main():
         out["config5"] = config5_record(torch, irl, stream, ncores, check=not args.no_cpu_baseline)
 
     rc = 0
-    if final_frame is not None:
+    if final_frame is not None and not args.no_cpu_baseline:
         # ---------------- N > 1: parity of the gathered frame (rgb is what the gather moves) ----------------
         import oracle_lib
         try:

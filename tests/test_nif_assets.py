@@ -94,10 +94,10 @@ def test_h5_errors_are_reported(tmp_path):
         irl.NifAssets(d)
 
 
-@pytest.mark.skipif(not Path("/root/reference/assets/nif").is_dir(), reason="reference checkout not present")
 def test_reference_metadata_file_parses(tmp_path):
-    """The reference ships the metadata (not the weights) of its trained model: parse that very file."""
-    src = Path("/root/reference/assets/nif/urban_alley_01_4k_fp16_yuv/assets.extra/nif_metadata.txt")
+    """The reference ships the metadata (not the weights) of its trained model: parse that very file (stored byte for byte
+    as tests/golden/urban_alley_nif_metadata.txt, from the reference's assets/nif/urban_alley_01_4k_fp16_yuv/assets.extra)."""
+    src = GOLDEN.parent / "urban_alley_nif_metadata.txt"
     d = tmp_path / "ref"; d.mkdir()
     (d / "nif_metadata.txt").write_bytes(src.read_bytes())
     k = np.zeros((48, 3), np.float32)

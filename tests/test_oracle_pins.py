@@ -215,19 +215,26 @@ def test_reference_permute_abs_and_bounds():
     assert np.array_equal(bits(GOLD["bounds_union"][:, 6:]), bits((umax + umin) * np.float32(0.5)))
 
 
-@pytest.mark.skipif(ol.ref_lib() is None, reason="oracle/_ref only exists where /root/reference was")
 def test_oracle_against_live_reference_dense(o):
+    """20 000 sincos arguments and 5 000 sample_diffuse calls against the reference's answers, stored in
+    tests/golden/ref_live_vectors.npz (generator tests/golden/gen_ref_live_vectors.py); where oracle/_ref exists the
+    reference is also asked live and must still give the stored answers."""
+    live = np.load(Path(__file__).parent / "golden" / "ref_live_vectors.npz")
     r = ol.ref_lib()
-    rng = np.random.default_rng(7)
-    for x in rng.uniform(-30, 30, 20000).astype(np.float32):
-        a, b, c, d = f32(), f32(), f32(), f32()
-        o.o_sincos(float(x), C.byref(a), C.byref(b)); r.ref_sincos(float(x), C.byref(c), C.byref(d))
-        assert (bits([a.value]), bits([b.value])) == (bits([c.value]), bits([d.value]))
-    for _ in range(5000):
-        n = rng.normal(size=3); n /= np.linalg.norm(n); n = n.astype(np.float32)
-        u1, u2 = (float(np.float32(x)) for x in rng.random(2))
-        out = (f32 * 3)(); r.ref_sample_diffuse((f32 * 3)(*[float(x) for x in n]), u1, u2, out)
-        assert np.array_equal(bits(o.o_sample_diffuse(v3(n), u1, u2).t()), bits(list(out)))
+    for x, ws, wc in zip(live["dense_sincos_x"], live["dense_sincos_s"], live["dense_sincos_c"]):
+        a, b = f32(), f32()
+        o.o_sincos(float(x), C.byref(a), C.byref(b))
+        assert (bits([a.value]), bits([b.value])) == (bits([ws]), bits([wc]))
+        if r is not None:
+            c, d = f32(), f32()
+            r.ref_sincos(float(x), C.byref(c), C.byref(d))
+            assert (bits([c.value]), bits([d.value])) == (bits([ws]), bits([wc]))
+    for n, (u1, u2), want in zip(live["dense_diffuse_n"], live["dense_diffuse_u"], live["dense_diffuse_out"]):
+        u1, u2 = float(u1), float(u2)
+        assert np.array_equal(bits(o.o_sample_diffuse(v3(n), u1, u2).t()), bits(want))
+        if r is not None:
+            out = (f32 * 3)(); r.ref_sample_diffuse((f32 * 3)(*[float(x) for x in n]), u1, u2, out)
+            assert np.array_equal(bits(list(out)), bits(want))
 
 
 # ---------------------------------------------------------------------------------------- [PROBE]

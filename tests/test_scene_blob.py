@@ -281,15 +281,23 @@ def test_truncated_blob_against_the_reference_deserialiser():
 
 
 def test_real_scene_blobs_against_the_live_reference_deserialiser():
-    """Where oracle/_ref is built (the container that holds the reference checkout): the box scene's and
-    test_scene.dae's blobs through the reference reader, live."""
+    """The box scene's and test_scene.dae's blobs through the reference reader: what it found in them is stored in
+    tests/golden/ref_live_vectors.npz (generator tests/golden/gen_ref_live_vectors.py) beside a hash of the blob it
+    walked; where oracle/_ref is built the reference reader is also run live on today's blob."""
+    import hashlib
     import oracle_lib
+    live = np.load(__import__("pathlib").Path(__file__).parent / "golden" / "ref_live_vectors.npz")
     r = oracle_lib.ref_lib()
-    if r is None or not hasattr(r, "ref_walk_scene_blob"):
-        pytest.skip("oracle/_ref not built here (needs the reference checkout)")
-    for s in (irl.HostScene.builtin("box"), irl.HostScene.import_file(irl.REPO_ROOT / "assets" / "test_scene.dae", load_normals=True)):
+    if r is not None and not hasattr(r, "ref_walk_scene_blob"):
+        r = None
+    for name, s in (("box", irl.HostScene.builtin("box")),
+                    ("test_scene", irl.HostScene.import_file(irl.REPO_ROOT / "assets" / "test_scene.dae", load_normals=True))):
         blob = irl.serialise_scene(s.desc)
-        want, wsc, wused = oracle_lib.ref_walk_scene_blob(blob)
+        assert hashlib.sha256(blob.tobytes()).digest() == live[f"blob_{name}_sha256"].tobytes(), \
+            f"{name}: the writer's bytes changed - regenerate the goldens with the reference reader"
+        want, wsc, wused = [int(x) for x in live[f"blob_{name}_walk"]], [int(x) for x in live[f"blob_{name}_scalars"]], int(live[f"blob_{name}_used"])
+        if r is not None:
+            assert oracle_lib.ref_walk_scene_blob(blob) == (want, wsc, wused)
         walk, sc, used = _product_walk(blob)
         assert [w for w in walk if w is not None] == [w for w, g in zip(want, walk) if g is not None]
         assert sc == wsc and used == wused == blob.size
