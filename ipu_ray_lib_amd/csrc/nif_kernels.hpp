@@ -191,18 +191,32 @@ struct NifDevice {
   }
 };
 
-// sin and cos of a phase that is a binary16 value (|p| <= 65504). Cody-Waite reduction to
-// r = p - k*2pi (k = nearest integer of p/2pi, 2pi split in three parts so the products are exact for the
-// <= 11-bit significand of p and |k| < 2^14), then the hardware v_sin/v_cos on r/2pi. Absolute error
-// ~1e-6, far below the binary16 rounding (4.9e-4) applied to the result (NifModel.cpp:212-216).
+// sin and cos of a phase that is a binary16 value (|p| <= 65504), to within 1.2e-7 RELATIVE error (measured over every finite
+// binary16 phase on gfx950): Cody-Waite reduction r = p - k*pi/2 (k = nearest integer of p*2/pi, pi/2 in three parts, fused
+// steps), then the single-precision minimax polynomials of sin and cos on [-pi/4, pi/4] (Cephes sinf / cosf) and the quadrant's
+// swap and signs. The result is rounded to binary16 (NifModel.cpp:212-216), so it must be right relative to its own size: the
+// hardware v_sin / v_cos this replaced are accurate to ~3.6e-7 ABSOLUTE, which near a zero of sin or cos is several binary16
+// ulps: for 19 of the 55 300 (phase, sin | cos) pairs of the binary16 phases in [-4096, 0] (what u, v in [0, 1] give) its feature
+// was another binary16 value than the exact one's, up to 4 ulps away. With this routine a feature is the binary16 of the exact
+// value except where that lies within 2^-22 (relative) of a rounding midpoint, and it equals the oracle's (libm sinf / cosf, then
+// binary16) at every finite binary16 phase (tests/test_nif_exact.py).
 __device__ __forceinline__ void sincos_half_phase(float p, float& sn, float& cs) {
-  const float k = rintf(p * 0.15915494309189535f);
-  float r = fmaf(-k, 6.28125f, p);                       // 2pi = 6.28125 + 1.9350051879882812e-3 + 3.0199159819e-7
-  r = fmaf(-k, 1.9350051879882812e-3f, r);
-  r = fmaf(-k, 3.0199159819e-7f, r);
-  const float rev = r * 0.15915494309189535f;            // |rev| <= 0.5
-  sn = __builtin_amdgcn_sinf(rev);
-  cs = __builtin_amdgcn_cosf(rev);
+  const float k = rintf(p * 0.636619772367581343f);
+  float r = fmaf(-k, 1.5707962512969971f, p);          // pi/2 = 1.5707962512969971 + 7.5497894158615964e-8 + 5.3903029534742384e-15
+  r = fmaf(-k, 7.5497894158615964e-8f, r);
+  r = fmaf(-k, 5.3903029534742384e-15f, r);            // |r| <= pi/4 (+ a few ulps)
+  const float r2 = r * r;
+  float s = fmaf(r2, -1.9515295891e-4f, 8.3321608736e-3f);
+  s = fmaf(r2, s, -1.6666654611e-1f);
+  s = fmaf(r2 * r, s, r);
+  float c = fmaf(r2, 2.443315711809948e-5f, -1.388731625493765e-3f);
+  c = fmaf(r2, c, 4.166664568298827e-2f);
+  c = fmaf(r2, c, -0.5f);
+  c = fmaf(r2, c, 1.f);
+  const int q = (int)k;                                 // quadrant: sin(r + q pi/2) = {s, c, -s, -c}[q & 3], cos = {c, -s, -c, s}[q & 3]
+  const float s0 = (q & 1) ? c : s, c0 = (q & 1) ? s : c;
+  sn = (q & 2) ? -s0 : s0;
+  cs = ((q + 1) & 2) ? -c0 : c0;
 }
 
 // The activation image in LDS, k-chunk major: X[kc][ray][32 halves], kc = column / 32, and inside a ray's 64 bytes the four
