@@ -65,6 +65,19 @@ typedef struct {
 #define MI_INVALID_GEOM ((uint16_t)0xFFFF)
 #define MI_INVALID_PRIM ((uint32_t)0xFFFFFFFFu)
 
+/* Result of a closest-hit ray query (mi_query / mi_query_device). No reference POD: the fields are what
+ * CompactBvh::intersect (CompactBvh.hpp:80-139) determines for one ray. */
+typedef struct {
+  float    t;          /* hit distance; == ray.t_max on a miss                                          */
+  uint32_t prim_id;    /* reference primID (as mi_hit_record.prim_id); MI_INVALID_PRIM on a miss          */
+  uint16_t geom_id;    /* MI_INVALID_GEOM on a miss                                                     */
+  uint16_t flags;      /* MI_FLAG_ESCAPED on a miss, else 0                                             */
+  mi_vec3  normal;     /* Primitive::normal at origin + t*dir (Mesh.hpp:107-121, Primitives.hpp); 0 on a miss */
+  float    b1, b2;     /* barycentrics of a triangle hit as intersectTriangle computes them; 0 otherwise  */
+} mi_query_hit;                                                  /* 32 B */
+
+enum { MI_QUERY_CLOSEST = 0, MI_QUERY_ANY = 1 };
+
 typedef struct {
   float min_x, min_y, min_z;
   uint32_t prim_or_second_child;   /* leaf: primID; interior: index of second child (first child = this+1) */
@@ -157,6 +170,19 @@ int mi_render(mi_scene* scene, int mode, mi_trace_result* rays, size_t n, mi_ray
  * partial-sum buffers and may execute concurrently; renders with a NIF environment share the scene's slot scratch
  * and are chained with an event, so they execute one after the other whatever streams they were enqueued on. */
 int mi_render_device(mi_scene* scene, int mode, void* d_rays, size_t n, void* hip_stream);
+
+/* Ray queries: CompactBvh::intersect (MI_QUERY_CLOSEST) / CompactBvh::occluded (MI_QUERY_ANY), CompactBvh.hpp:33-139, for each
+ * of n caller-supplied rays with its own t_min / t_max - the reference's CPU path does the same with Embree's rtcIntersect1M /
+ * rtcOccluded1M. Same visit order, same acceptance (t > t_min && t < closest), same NaN and infinite-inverse behaviour; no shading.
+ * Device entry: d_rays = n mi_ray, d_out = n mi_query_hit (CLOSEST) or n uint8_t, 1 = occluded (ANY), DEVICE memory. Asynchronous
+ * on hip_stream (a hipStream_t as void*; NULL = the null stream); the scene waits for it when destroyed.
+ * Host entry: the same on HOST buffers, synchronous (copies + the device entry), in batches of mi_scene_set_ray_batch rays.
+ * n == 0 is a no-op. MI_ERR_INVALID_ARG, before any device work: a null scene or buffer, an unknown kind, a buffer that is not
+ * 16-byte aligned, or more rays in one launch (mi_query: in one batch) than the 32-bit work index allows (0xFFBFFFFF).
+ * Counters (mi_get_counters): casts += n; nodes visited and leaf tests too under option full_stats. Options: query_kernel,
+ * query_tune, and the arithmetic options double_fallback and fast, as for renders. */
+int mi_query_device(mi_scene* scene, int kind, const void* d_rays, void* d_out, size_t n, void* hip_stream);
+int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n);
 
 /* Replaces: IpuScene::getTraceTimeSecs (IpuScene.hpp:55). Wall time of the last mi_render. */
 double mi_trace_time_secs(const mi_scene* scene);
@@ -262,11 +288,14 @@ int mi_scene_set_ray_batch(mi_scene* scene, size_t rays_per_batch);
  *                                   per launch, not from the 84-byte record (default 1: a third of the HBM traffic)
  *   "cus"           0..4096         compute units the launch grids are sized for (0 = what the device reports; grids are
  *                                   units x workgroups resident per unit, asked of the runtime per kernel)
+ *   "query_kernel"  0 | 1           ray queries (mi_query*): one thread per ray (0, the default: measured faster) or K4, the
+ *                                   persistent phase-scheduled query kernel (1)
+ *   "query_tune"    "leafAt,dbl,maxExtra,burst,keep8"   scheduling weights of K4 (csrc/query_kernels.hpp QueryTune)
  * None of them changes a result bit. Two further keys select ARITHMETIC:
  *   "double_fallback" 0 | 1         the reference built with -DALLOW_DOUBLE_FALLBACK=1 (CMakeLists.txt:13,34-41; src/Mesh.cpp:38-51):
  *                                   edge functions that are exactly zero in binary32 are recomputed in binary64. Results are those
  *                                   of the reference's CPU path built the same way, bit for bit (default 0 = the reference default)
- *   "fast"            0 | 1         tolerance tier for plain path-trace renders of the default kernel: box test as FMAs, triangle
+ *   "fast"            0 | 1         tolerance tier for plain path-trace renders of the default kernel and for ray queries: box test as FMAs, triangle
  *                                   test contracted, v_rcp_f32 in the cast set-up. NOT bit-exact: first hits name the same primitive
  *                                   with distance / point within 1e-6; see tests/test_gpu_parity.py (test_fast_tier_...) for the
  *                                   stated tolerance. Never the default. */

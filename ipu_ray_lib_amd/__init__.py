@@ -39,12 +39,17 @@ GEOM_REF = np.dtype([("index", "<u2"), ("type", "u1"), ("pad", "u1")])
 SPHERE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("radius", "<f4")])
 DISC = np.dtype([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("r", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("cz", "<f4")])
 
-assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32
+# mi_query_hit: the result of a closest-hit ray query (IpuScene.intersect / query_device)
+QUERY_HIT = np.dtype([("t", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("normal", VEC3),
+                      ("b1", "<f4"), ("b2", "<f4")])
+
+assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
 assert BVH_NODE.itemsize == 24 and MATERIAL.itemsize == 36 and MESH_INFO.itemsize == 16 and GEOM_REF.itemsize == 4
 
 FLAG_ERROR, FLAG_ESCAPED = 1, 2
 INVALID_GEOM, INVALID_PRIM = 0xFFFF, 0xFFFFFFFF
 MODE_SHADOW_TRACE, MODE_PATH_TRACE = 0, 1
+QUERY_CLOSEST, QUERY_ANY = 0, 1
 
 MI_OK = 0
 
@@ -187,6 +192,8 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_scene_set_max_nif_batch.argtypes = [C.c_void_p, C.c_size_t]
         lib.mi_scene_set_ray_batch.argtypes = [C.c_void_p, C.c_size_t]
         lib.mi_nif_infer_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
         lib.mi_group_destroy.argtypes = [C.c_void_p]
         lib.mi_group_destroy.restype = None
@@ -320,6 +327,13 @@ def aligned_bytes(n: int, align: int = 16) -> np.ndarray:
     raw = np.zeros(n + align, np.uint8)
     off = (-raw.ctypes.data) % align
     return raw[off:off + n]
+
+
+def _aligned_copy(a: np.ndarray) -> np.ndarray:
+    """A C-contiguous copy of `a` at a 16-byte aligned address (the query entries' buffer rule)."""
+    out = aligned_bytes(a.size * a.dtype.itemsize).view(a.dtype)
+    out[...] = a.reshape(-1)
+    return out
 
 
 def serialise_scene(desc: SceneDesc) -> np.ndarray:
@@ -459,6 +473,53 @@ class IpuScene:
     def run_device(self, d_rays_ptr: int, n: int, mode: int, stream: int = 0):
         """Trace a DEVICE-resident ray stream (e.g. a torch uint8 tensor's data_ptr) asynchronously."""
         self._check(self._lib.mi_render_device(self._h, mode, C.c_void_p(d_rays_ptr), n, C.c_void_p(stream)))
+
+    # -- ray queries (mi_query / mi_query_device): CompactBvh::intersect / ::occluded per given ray, no shading --------------
+    def _query_host(self, kind: int, rays: np.ndarray, out: np.ndarray) -> np.ndarray:
+        assert rays.dtype == RAY and rays.ndim == 1
+        src = rays if (rays.flags["C_CONTIGUOUS"] and rays.ctypes.data % 16 == 0) else _aligned_copy(rays)
+        self._check(self._lib.mi_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
+        return out
+
+    def intersect(self, rays: np.ndarray) -> np.ndarray:
+        """Closest hit of every ray (a RAY array, host memory): a QUERY_HIT array. Synchronous; batched by setRayBatch."""
+        return self._query_host(QUERY_CLOSEST, rays, aligned_bytes(rays.size * QUERY_HIT.itemsize).view(QUERY_HIT))
+
+    def occluded(self, rays: np.ndarray) -> np.ndarray:
+        """Whether anything is hit with tMin < t < tMax, for every ray (a RAY array, host memory): a bool array."""
+        return self._query_host(QUERY_ANY, rays, aligned_bytes(rays.size)).view(np.bool_)
+
+    def query_device(self, kind: int, d_rays: int, d_out: int, n: int, stream: int = 0):
+        """mi_query_device on device pointers (n RAY records in, n QUERY_HIT records or n bytes out), asynchronous on `stream`."""
+        self._check(self._lib.mi_query_device(self._h, int(kind), C.c_void_p(d_rays), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
+
+    def cast(self, origins, directions, t_min=0.0, t_max=float("inf"), any_hit: bool = False) -> dict:
+        """Torch convenience over mi_query_device: float32 device tensors of shape [N, 3] (t_min / t_max: numbers or [N]
+        tensors), enqueued on torch.cuda.current_stream(). Returns device tensors: closest hit {"t" [N], "prim_id" [N] int32,
+        "geom_id" [N] int32 (-1 on a miss, for both), "normal" [N, 3], "bary" [N, 2] (b1, b2)}; any hit {"occluded" [N] bool}."""
+        import torch
+        o = origins.to(torch.float32)
+        d = directions.to(torch.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape or not o.is_cuda or d.device != o.device:
+            raise ValueError("cast: origins and directions must be [N, 3] tensors on one GPU")
+        n = o.shape[0]
+
+        def column(x):
+            x = torch.as_tensor(x, dtype=torch.float32, device=o.device)
+            return x.expand(n).reshape(n, 1)
+
+        rays = torch.cat([o, column(t_min), d, column(t_max)], dim=1).contiguous()      # [N, 8] = n mi_ray
+        stream = torch.cuda.current_stream(o.device).cuda_stream
+        if any_hit:
+            out = torch.empty(n, dtype=torch.uint8, device=o.device)
+            self.query_device(QUERY_ANY, rays.data_ptr(), out.data_ptr(), n, stream)
+            return {"occluded": out.bool()}
+        raw = torch.empty((n, 8), dtype=torch.float32, device=o.device)
+        self.query_device(QUERY_CLOSEST, rays.data_ptr(), raw.data_ptr(), n, stream)
+        words = raw.view(torch.int32)
+        halves = raw.view(torch.int16)
+        return {"t": raw[:, 0], "prim_id": words[:, 1], "geom_id": halves[:, 4].to(torch.int32),
+                "normal": raw[:, 3:6], "bary": raw[:, 6:8]}
 
     def nif_infer_device(self, d_u: int, d_v: int, d_bgr: int, n: int, stream: int = 0):
         self._check(self._lib.mi_nif_infer_device(self._h, C.c_void_p(d_u), C.c_void_p(d_v), C.c_void_p(d_bgr), n, C.c_void_p(stream)))

@@ -16,6 +16,7 @@
 #include "ray_math.h"
 #include "trace_kernels.hpp"
 #include "trace_wavefront.hpp"
+#include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
 // MI_RAYLIB_VARIANTS=1 (libmi_raylib_variants.so, the test build): the kernel families that were built, measured and not
 // made the default - LDS-staged nodes (kernel 2), the path pool (kernel 3), the speculative walk (spec), the 4-wave and
 // the runtime-weights instantiations (waves, tune), the register-resident MLP kernel K3r (nif_shape r8 / r8s) - stay
@@ -44,6 +45,9 @@ static_assert(offsetof(mi_trace_result, u) == 12 && offsetof(mi_trace_result, h)
 static_assert(offsetof(mi_hit_record, prim_id) == 32 && offsetof(mi_hit_record, normal) == 36 &&
               offsetof(mi_hit_record, throughput) == 48 && offsetof(mi_hit_record, geom_id) == 60 &&
               offsetof(mi_hit_record, flags) == 62, "HitRecord offsets");
+static_assert(sizeof(mi_query_hit) == 32 && offsetof(mi_query_hit, prim_id) == 4 && offsetof(mi_query_hit, geom_id) == 8 &&
+              offsetof(mi_query_hit, flags) == 10 && offsetof(mi_query_hit, normal) == 12 && offsetof(mi_query_hit, b1) == 24 &&
+              offsetof(mi_query_hit, b2) == 28, "mi_query_hit layout");
 
 namespace {
 
@@ -139,6 +143,8 @@ struct SceneOptions {
   // the two options that select ARITHMETIC (every other option leaves every result bit alone):
   bool doubleFallback = false;     // "double_fallback": the reference's ALLOW_DOUBLE_FALLBACK=1 build (CMakeLists.txt:13,34-41; Mesh.cpp:38-51), bit-exact to the oracle in that mode
   bool fast = false;               // "fast": the tolerance tier (FMA box / triangle tests; plain path-trace renders of the default kernel only)
+  int queryKernel = 0;             // "query_kernel": ray queries (mi_query*) run the one-thread-per-ray kernel (0, the default: measured faster, DESIGN.md §6 "K4") or K4 (1, query_kernels.hpp)
+  QueryTune queryTune = kDefaultQueryTune;   // "query_tune": K4's scheduling weights leafAt,dbl,maxExtra,burst,keep8
 
   // Every key takes values from a stated domain; anything else leaves the option as it was and returns false
   // (mi_scene_set_option then reports MI_ERR_INVALID_ARG, as include/mi_raylib.h promises).
@@ -214,6 +220,15 @@ struct SceneOptions {
     if (key == "nif_split") { if (!number(v, 0, 1024, q)) return false; nifSplit = (uint32_t)q; return true; }
     if (key == "nif_trace_wgs") { if (!number(v, 0, 16, q)) return false; nifTraceWgs = (uint32_t)q; return true; }
     if (key == "coords") return flag01(v, coords);
+    if (key == "query_kernel") { if (!number(v, 0, 1, q)) return false; queryKernel = (int)q; return true; }
+    if (key == "query_tune") {      // leafAt,dbl,maxExtra,burst,keep8
+      unsigned a, b, c, dd, e;
+      char tail = 0;
+      if (sscanf(v, "%u,%u,%u,%u,%u%c", &a, &b, &c, &dd, &e, &tail) != 5) return false;
+      if (b == 0 || dd == 0 || e > 8 || c > 64) return false;
+      queryTune = {a, b, c, dd, e};
+      return true;
+    }
     if (key == "lean_hit") return flag01(v, leanHit);
     if (key == "leaf_rot") return flag01(v, leafRot);
     if (key == "double_fallback") {
@@ -318,6 +333,8 @@ struct mi_scene {
   float hdriRotationDegrees = 0.f;
   size_t maxNifBatch = 0;
   size_t rayBatch = 0;               // rays per mi_render batch (0 = the whole stream in one batch)
+  // mi_query's pipeline: two device ray / result buffers, kept between calls (on the same two streams as mi_render's)
+  void* d_qRays[2] = {nullptr, nullptr}; void* d_qOut[2] = {nullptr, nullptr}; size_t qCap[2] = {0, 0};
   NifDevice nif;
   // scratch for the per-sample NIF loop
   // NIF renders: per-(sample, pixel) slots of one launch. TWO sets, so that the trace launch of sample batch b + 1 (into the
@@ -361,6 +378,7 @@ struct mi_scene {
     if (splitFirst) (void)hipEventDestroy(splitFirst);
     if (d_segTotal) (void)hipFree(d_segTotal);
     for (LaunchSlot& l : slots) { if (l.lastWork) (void)hipEventDestroy(l.lastWork); if (l.d_workCounter) (void)hipFree(l.d_workCounter); if (l.d_segPart) (void)hipFree(l.d_segPart); if (l.d_coords) (void)hipFree(l.d_coords); if (l.d_poolScratch) (void)hipFree(l.d_poolScratch); }
+    for (int i = 0; i < 2; ++i) { if (d_qRays[i]) (void)hipFree(d_qRays[i]); if (d_qOut[i]) (void)hipFree(d_qOut[i]); }
     for (int i = 0; i < 2; ++i) { if (d_batch[i]) (void)hipFree(d_batch[i]); if (pipeStream[i]) (void)hipStreamDestroy(pipeStream[i]); }
     if (nifDone) (void)hipEventDestroy(nifDone);
     for (auto& e : nifTimes) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -933,6 +951,60 @@ void launchRender(mi_scene& S, int mode, mi_trace_result* d_rays, size_t n, hipS
   HIP_CHECK(hipEventRecord(S.slotFor(stream).lastWork, stream));      // (~mi_scene waits for it)
 }
 
+// Ray queries (mi_query_device): closest hit (MI_QUERY_CLOSEST, n mi_query_hit) or any hit (MI_QUERY_ANY, n bytes) of n
+// caller-supplied rays. Option query_kernel picks the one-thread-per-ray kernel (0) or K4 (1); full_stats, double_fallback and
+// fast pick the build, as for renders (double_fallback has no instrumented build: it takes precedence, as in shadow-trace renders).
+// Records the slot's lastWork event: ~mi_scene waits for the launch.
+void launchQuery(mi_scene& S, int kind, const mi_ray* d_rays, void* d_out, size_t n, hipStream_t stream) {
+  if (n == 0) return;
+  if (n > kMaxWorkItems) throw ArgError("mi_query: more rays than one launch indexes (kMaxWorkItems)");
+  const uint32_t cnt = (uint32_t)n;
+  LaunchSlot& slot = S.slotFor(stream);
+  const DeviceScene dsv = S.ds;      // (queries always start at the root: root_start assumes tMin = 0, tMax = inf)
+  const bool any = kind == MI_QUERY_ANY;
+  if (S.opt.queryKernel == 0) {
+    const dim3 block(256), grid((cnt + 255) / 256);
+    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_rays, d_out, cnt); };
+#define MI_QP(A) do { if (S.opt.doubleFallback) go(query_plain_kernel<A, false, true, false>); \
+                      else if (S.opt.fast) go(query_plain_kernel<A, false, false, true>); \
+                      else if (S.opt.fullStats) go(query_plain_kernel<A, true, false, false>); \
+                      else go(query_plain_kernel<A, false, false, false>); } while (0)
+    if (any) MI_QP(true); else MI_QP(false);
+#undef MI_QP
+  } else {
+    HIP_CHECK(hipMemsetAsync(slot.d_workCounter, 0, sizeof(uint32_t), stream));
+    // persistent grid: as many workgroups as stay resident, never more than the batch has rays for
+    auto go = [&](auto kern) {
+      const uint32_t perUnit = S.residentBlocks(reinterpret_cast<const void*>(kern), 256, 0);
+      const uint32_t wgs = (uint32_t)std::min<uint64_t>((cnt + 255) / 256, (uint64_t)S.cus() * perUnit);
+      if (S.opt.sayGrid) fprintf(stderr, "mi_raylib: query grid %u workgroups = %u units x %u resident\n", wgs, S.cus(), perUnit);
+      hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), 0, stream, dsv, d_rays, d_out, cnt, slot.d_workCounter, S.opt.queryTune);
+    };
+#define MI_QW(A) do { if (S.opt.doubleFallback) go(query_wave_kernel<A, false, true, false>); \
+                      else if (S.opt.fast) go(query_wave_kernel<A, false, false, true>); \
+                      else if (S.opt.fullStats) go(query_wave_kernel<A, true, false, false>); \
+                      else go(query_wave_kernel<A, false, false, false>); } while (0)
+    if (any) MI_QW(true); else MI_QW(false);
+#undef MI_QW
+  }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
+}
+
+// Argument rules shared by the two query entries; touches neither the scene nor a device.
+bool queryArgsBad(const char* fn, const mi_scene* scene, int kind, const void* rays, const void* out, size_t n, size_t limit) {
+  const char* why = nullptr;
+  if (!scene) why = "null scene";
+  else if (kind != MI_QUERY_CLOSEST && kind != MI_QUERY_ANY) why = "unknown query kind";
+  else if (n == 0) return false;
+  else if (!rays || !out) why = "null buffer";
+  else if ((uintptr_t)rays % 16 || (uintptr_t)out % 16) why = "buffers must be 16-byte aligned";
+  else if (n > limit) why = "more rays than one launch indexes (kMaxWorkItems)";
+  if (!why) return false;
+  g_err = std::string(fn) + ": " + why;
+  return true;
+}
+
 // One wave that samples the work counter of `hip_stream`'s persistent launches `n` times, `period_ticks` (100-MHz ticks) apart, into
 // d_samples as pairs {s_memrealtime, counter}: how fast a launch hands its work units out over its life - the ramp at its start, the
 // moment the queue runs empty, the drain behind it (tools/launch_progress.py). It runs on a stream of the scene's own beside the launch it
@@ -1079,6 +1151,53 @@ int mi_render(mi_scene* scene, int mode, mi_trace_result* rays, size_t n, mi_ray
       scene->traceTimeSecs = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     } catch (...) { (void)hipDeviceSynchronize(); cleanup(); throw; }
     cleanup();
+  });
+}
+
+int mi_query_device(mi_scene* scene, int kind, const void* d_rays, void* d_out, size_t n, void* hip_stream) {
+  if (queryArgsBad("mi_query_device", scene, kind, d_rays, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    launchQuery(*scene, kind, static_cast<const mi_ray*>(d_rays), d_out, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n) {
+  if (queryArgsBad("mi_query", scene, kind, rays, out, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  // (the host stream is cut into batches of mi_scene_set_ray_batch rays: the work-index limit applies per batch)
+  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
+  if (batch > kMaxWorkItems) { g_err = "mi_query: more rays per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    // batches through two slots (device buffers + streams kept by the scene), as mi_render: upload, query and download of batch
+    // b + 1 are enqueued on the other stream while batch b runs
+    const size_t outSize = kind == MI_QUERY_ANY ? 1 : sizeof(mi_query_hit);
+    const size_t numBatches = (n + batch - 1) / batch;
+    const int slots = numBatches > 1 ? 2 : 1;
+    try {
+      for (int i = 0; i < slots; ++i) {
+        if (scene->qCap[i] < batch) {
+          if (scene->d_qRays[i] || scene->d_qOut[i]) HIP_CHECK(hipDeviceSynchronize());
+          for (void** p : {&scene->d_qRays[i], &scene->d_qOut[i]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+          scene->qCap[i] = 0;
+          HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * sizeof(mi_ray)));
+          HIP_CHECK(hipMalloc(&scene->d_qOut[i], batch * sizeof(mi_query_hit)));      // (room for either kind)
+          scene->qCap[i] = batch;
+        }
+        if (!scene->pipeStream[i]) HIP_CHECK(hipStreamCreateWithFlags(&scene->pipeStream[i], hipStreamNonBlocking));
+      }
+      for (size_t b = 0; b < numBatches; ++b) {
+        const int i = (int)(b % slots);
+        hipStream_t st = scene->pipeStream[i];
+        const size_t first = b * batch, cnt = std::min(batch, n - first);
+        HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], rays + first, cnt * sizeof(mi_ray), hipMemcpyHostToDevice, st));
+        launchQuery(*scene, kind, static_cast<const mi_ray*>(scene->d_qRays[i]), scene->d_qOut[i], cnt, st);
+        HIP_CHECK(hipMemcpyAsync(static_cast<char*>(out) + first * outSize, scene->d_qOut[i], cnt * outSize, hipMemcpyDeviceToHost, st));
+      }
+      for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
+    } catch (...) { (void)hipDeviceSynchronize(); throw; }
   });
 }
 

@@ -1,0 +1,75 @@
+"""Ray batches for ray queries, built on the host with numpy alone (no oracle): a scene's primary camera rays, cosine-distributed
+diffuse bounce rays from their first hits, and shadow rays from those hits to a point light. tools/bench_query.py measures the
+query kernels on them; tests/test_query_gpu.py checks them at scale."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import RAY, INVALID_PRIM
+
+RAY_EPSILON = np.float32(5.9604644775390625e-08 * 1500.0)       # ray_math.h kRayEpsilon (precision_utils.hpp)
+LIGHT = np.array([18.0, 257.0, -1060.0], np.float32)            # the reference's shadow-trace light (trace.cpp:247)
+
+
+def _vec(a: np.ndarray, field: str) -> np.ndarray:
+    return np.stack([a[field][c] for c in "xyz"], 1).astype(np.float32)
+
+
+def make_rays(origins: np.ndarray, directions: np.ndarray, t_min=0.0, t_max=np.inf) -> np.ndarray:
+    """A RAY array from [N, 3] origins and directions."""
+    n = len(origins)
+    r = np.zeros(n, RAY)
+    for k, c in enumerate("xyz"):
+        r["origin"][c] = origins[:, k]
+        r["direction"][c] = directions[:, k]
+    r["tMin"] = t_min
+    r["tMax"] = t_max
+    return r
+
+
+def primary_rays(host_scene) -> np.ndarray:
+    """The scene's camera rays (initPerspectiveRayStream without jitter, mi_init_ray_stream) as RAY records."""
+    s = host_scene.init_ray_stream()
+    return make_rays(_vec(s["h"]["r"], "origin"), _vec(s["h"]["r"], "direction"))
+
+
+def offset_origin(p: np.ndarray, d: np.ndarray, n: np.ndarray) -> np.ndarray:
+    """Render.hpp:29-33 (ray_math.h offset_origin) in binary32."""
+    m = (np.float32(1) + np.abs(p).min(axis=1)) * RAY_EPSILON * np.copysign(np.float32(1), (n * d).sum(axis=1, dtype=np.float32))
+    return (p + n * m[:, None].astype(np.float32)).astype(np.float32)
+
+
+def hit_points(rays: np.ndarray, hits: np.ndarray):
+    """(mask of rays that hit, hit points, normals facing the incoming ray) from a closest-hit query's QUERY_HIT results."""
+    hit = hits["primID"] != INVALID_PRIM
+    o, d = _vec(rays, "origin")[hit], _vec(rays, "direction")[hit]
+    p = (o + d * hits["t"][hit][:, None]).astype(np.float32)
+    n = _vec(hits, "normal")[hit]
+    n = np.where(((n * d).sum(axis=1) > 0)[:, None], -n, n).astype(np.float32)
+    return hit, p, n
+
+
+def bounce_rays(rays: np.ndarray, hits: np.ndarray, per_hit: int = 1, seed: int = 0) -> np.ndarray:
+    """Cosine-distributed diffuse bounce rays, `per_hit` per hit, leaving the hit points offset as offset_origin does."""
+    _, p, n = hit_points(rays, hits)
+    p, n = np.repeat(p, per_hit, 0), np.repeat(n, per_hit, 0)
+    rng = np.random.default_rng(seed)
+    u1, u2 = rng.random(len(p), np.float32), rng.random(len(p), np.float32)
+    r, phi = np.sqrt(u1), np.float32(2 * np.pi) * u2
+    local = np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(np.maximum(0, 1 - u1))], 1).astype(np.float32)
+    # an orthonormal frame around n
+    a = np.where((np.abs(n[:, 0]) > 0.9)[:, None], np.array([0, 1, 0], np.float32), np.array([1, 0, 0], np.float32))
+    t = np.cross(a, n); t /= np.linalg.norm(t, axis=1, keepdims=True)
+    b = np.cross(n, t)
+    d = (t * local[:, :1] + b * local[:, 1:2] + n * local[:, 2:3]).astype(np.float32)
+    d /= np.linalg.norm(d, axis=1, keepdims=True).astype(np.float32)
+    return make_rays(offset_origin(p, d, n), d)
+
+
+def shadow_rays(rays: np.ndarray, hits: np.ndarray, light=LIGHT) -> np.ndarray:
+    """Any-hit rays from the hit points to a point light (Render.hpp:37-72): t_max = the distance to the light."""
+    _, p, n = hit_points(rays, hits)
+    off = (np.asarray(light, np.float32)[None, :] - p).astype(np.float32)
+    dist = np.sqrt((off * off).sum(axis=1)).astype(np.float32)
+    d = (off / dist[:, None]).astype(np.float32)
+    return make_rays(offset_origin(p, d, n), d, 0.0, dist)
