@@ -13,7 +13,7 @@
 // same arithmetic, so they write the same bytes (and, in the exact tiers, the oracle's).
 #pragma once
 
-#include "trace_wavefront.hpp"     // fast_box_setup, lane_rank, PH_*
+#include "trace_wavefront.hpp"     // lane_rank, PH_*
 
 namespace mi {
 
@@ -61,106 +61,11 @@ __device__ __forceinline__ void store_query_hit(const DeviceScene& sc, mi_query_
   q[0] = w0; q[1] = w1;
 }
 
-// FAST tier box test (trace_wavefront.hpp, nodeBodyT with FAST): three pairs of FMAs on (plane, 1/d, -o/d), the far side widened
-// by slabPad; tMin instead of the path tracer's 0. Shared by both query kernels so that they agree bit for bit in this tier too.
-__device__ __forceinline__ bool box_hit_fast(const GNode& nd, f3 inv, f3 oi, float slabPad, float tMin, float tCur) {
-  const float ax = __builtin_fmaf(nd.minx, inv.x, oi.x), bx = __builtin_fmaf(nd.maxx, inv.x, oi.x);
-  const float ay = __builtin_fmaf(nd.miny, inv.y, oi.y), by = __builtin_fmaf(nd.maxy, inv.y, oi.y);
-  const float az = __builtin_fmaf(nd.minz, inv.z, oi.z), bz = __builtin_fmaf(nd.maxz, inv.z, oi.z);
-  const float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tMin));
-  const float t1 = fminf(__builtin_fmaf(fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)), kSlabScale, slabPad), tCur);
-  return !(t0 > t1);
-}
-
-// Exact box test (CompactBVH2Node.cpp:5-22, intersectRaySlab CompactBVH2Node.hpp:14-50) in the min / max form of K1w: with no NaN
-// among the slab products, tMin and tCur, the reference's ordered compare / selects ARE min / max and the far side may be scaled
-// once (trace_wavefront.hpp). `literal` lanes - a non-finite origin, direction or reciprocal, or a NaN tMin / tMax: NaN can
-// then arise - redo the test with the reference's literal sequence, as traverse<> evaluates it.
-__device__ __forceinline__ bool box_hit_exact(const GNode& nd, f3 o, f3 inv, float tMin, float tCur, bool literal) {
-  const float ax = (nd.minx - o.x) * inv.x, bx = (nd.maxx - o.x) * inv.x;
-  const float ay = (nd.miny - o.y) * inv.y, by = (nd.maxy - o.y) * inv.y;
-  const float az = (nd.minz - o.z) * inv.z, bz = (nd.maxz - o.z) * inv.z;
-  float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), tMin));
-  float t1 = fminf(fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)) * kSlabScale, tCur);
-  if (literal) {
-    t0 = tMin; t1 = tCur;
-    { float tmin = ax, tmax = bx; if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; } tmax *= kSlabScale; t0 = tmin > t0 ? tmin : t0; t1 = tmax < t1 ? tmax : t1; }
-    { float tmin = ay, tmax = by; if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; } tmax *= kSlabScale; t0 = tmin > t0 ? tmin : t0; t1 = tmax < t1 ? tmax : t1; }
-    { float tmin = az, tmax = bz; if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; } tmax *= kSlabScale; t0 = tmin > t0 ? tmin : t0; t1 = tmax < t1 ? tmax : t1; }
-  }
-  return !(t0 > t1);
-}
-
-// Whether a cast needs the literal box test (box_hit_exact): the min / max form is only valid when nothing can be NaN. With a
-// finite origin and finite direction components, 1/d is never 0, so (plane - o) * (1/d) is never inf * 0.
-__device__ __forceinline__ bool needs_literal_box(f3 o, f3 d, f3 inv, float tMin, float tMax) {
-  return !(fabsf(inv.x) < kInf && fabsf(inv.y) < kInf && fabsf(inv.z) < kInf && fabsf(o.x) < kInf && fabsf(o.y) < kInf && fabsf(o.z) < kInf &&
-           fabsf(d.x) < kInf && fabsf(d.y) < kInf && fabsf(d.z) < kInf) | (tMin != tMin) | (tMax != tMax);
-}
-
-// One primitive test at leaf node `leaf` (Mesh.cpp:6-104, Primitives.cpp:24-67) and the reference's acceptance
-// t > tMin && t < closest (CompactBvh.hpp:124 / :60). ROT: the record of the cast's shear axis from GLeafRot (the vertices arrive
-// rotated; exact, trace_kernels.hpp intersect_triangle PRE). Returns whether the hit is accepted; t and the barycentrics in t, b.
-template <bool DF, bool FAST, bool ROT>
-__device__ __forceinline__ bool leaf_test(const DeviceScene& sc, uint32_t leaf, f3 o, f3 d, const Shear& sh, float tMin, float tCur, float& tOut, float& b0, float& b1, float& b2) {
-  GLeaf L;
-  if constexpr (ROT) {
-    const GLeafBlock B = *reinterpret_cast<const GLeafBlock*>(reinterpret_cast<const char*>(sc.leavesRot) + (size_t)leaf * sizeof(GLeafRot) + sh.kz * sizeof(GLeafBlock));
-    L.type = B.type;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) L.f[q] = B.f[q];
-  } else {
-    const GLeaf& G = sc.leaves[leaf];
-    L.type = G.type;
-#pragma unroll
-    for (int q = 0; q < 9; ++q) L.f[q] = G.f[q];
-  }
-  float t;
-  bool cand;
-  b0 = b1 = b2 = 0.f;
-  const uint32_t kind = leaf_kind(L);
-  if (kind == LEAF_TRI) {
-    const f3 p0 = mk(L.f[0], L.f[1], L.f[2]), p1 = mk(L.f[3], L.f[4], L.f[5]), p2 = mk(L.f[6], L.f[7], L.f[8]);
-    if constexpr (FAST) t = intersect_triangle_fast(p0, p1, p2, o, sh, b0, b1, b2);
-    else if constexpr (ROT) t = intersect_triangle<DF, true>(p0, p1, p2, permute_kz(o, sh.kz), sh, b0, b1, b2);
-    else t = intersect_triangle<DF>(p0, p1, p2, o, sh, b0, b1, b2);
-    cand = t > 0.f && t < kInf;                 // Mesh.hpp:93
-  } else if (kind == LEAF_SPHERE) {
-    t = intersect_sphere(L, o, d, tMin);
-    cand = true;                                // Failed() carries t = 0, rejected by t > tMin
-  } else {
-    t = intersect_disc(L, o, d);
-    cand = true;
-  }
-  tOut = t;
-  return cand & (t > tMin) & (t < tCur);
-}
-
-// The FAST tier's walk for the one-thread-per-ray kernel: traverse<> with the tier's cast set-up, box test and triangle test.
-template <bool ANY_HIT, bool STATS>
-__device__ __forceinline__ bool traverse_fast(const DeviceScene& sc, f3 o, f3 d, float tMin, float tMax, Hit& hit, CastStats& cs) {
-  f3 inv = fast_inverse(d), oi;
-  const Shear sh = make_shear_fast(d, inv);
-  float slabPad;
-  fast_box_setup(o, inv, oi, slabPad);
-  hit.t = tMax; hit.leaf = kNoLeaf; hit.geomID = 0xFFFFu; hit.b0 = hit.b1 = hit.b2 = 0.f;
-  uint32_t i = 0;
-  while (i < sc.numNodes) {
-    const GNode nd = sc.nodes[i];
-    if (STATS) cs.nodes++;
-    const bool boxHit = box_hit_fast(nd, inv, oi, slabPad, tMin, hit.t);
-    const bool isLeaf = node_is_leaf(nd);
-    if (boxHit && isLeaf) {
-      if (STATS) cs.leaves++;
-      float t, b0, b1, b2;
-      if (leaf_test<false, true, false>(sc, i, o, d, sh, tMin, hit.t, t, b0, b1, b2)) {
-        if (ANY_HIT) return true;
-        hit.t = t; hit.leaf = i; hit.b0 = b0; hit.b1 = b1; hit.b2 = b2;
-      }
-    }
-    i = (boxHit && !isLeaf) ? i + 1 : (nd.link >> 5);
-  }
-  return hit.leaf != kNoLeaf;
+// Whether a query cast needs the literal box test (box_hit_span in trace_kernels.hpp): the path tracer's condition, and besides
+// a non-finite direction (its reciprocal is then 0, and (plane - o) * 0 is NaN for an infinite plane distance) or a NaN tMin / tMax.
+__device__ __forceinline__ bool query_needs_literal_box(f3 o, f3 d, f3 inv, float tMin, float tMax) {
+  const bool pathTracer = needs_literal_box(o, inv);
+  return pathTracer | !(fabsf(d.x) < kInf && fabsf(d.y) < kInf && fabsf(d.z) < kInf) | (tMin != tMin) | (tMax != tMax);
 }
 
 // ---- query_kernel = 0: one thread per ray --------------------------------------------------------------------------
@@ -171,9 +76,7 @@ __global__ void __launch_bounds__(256) query_plain_kernel(DeviceScene sc, const 
   if (idx < n) {
     const QueryRay r = load_query_ray(rays, idx);
     Hit hit;
-    bool found;
-    if constexpr (FAST) found = traverse_fast<ANY_HIT, STATS>(sc, r.o, r.d, r.tMin, r.tMax, hit, cs);
-    else found = traverse<ANY_HIT, STATS, DF>(sc, r.o, r.d, r.tMin, r.tMax, hit, cs);
+    const bool found = traverse<ANY_HIT, STATS, DF, FAST>(sc, r.o, r.d, r.tMin, r.tMax, hit, cs);
     if constexpr (ANY_HIT) static_cast<uint8_t*>(out)[idx] = found ? 1u : 0u;
     else store_query_hit(sc, static_cast<mi_query_hit*>(out), idx, r.o, r.d, hit);
   }
@@ -202,7 +105,7 @@ __global__ void __launch_bounds__(256) query_wave_kernel(DeviceScene sc, const m
   auto nodeStep = [&]() {
     const GNode nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + node);
     if (STATS) cs.nodes++;
-    const bool boxHit = FAST ? box_hit_fast(nd, inv, oi, slabPad, tMin, hit.t) : box_hit_exact(nd, o, inv, tMin, hit.t, literal);
+    const bool boxHit = FAST ? box_hit_fast(nd, inv, oi, slabPad, tMin, hit.t) : box_hit_exact(nd, o, inv, tMin, hit.t, literal);    // box test: see box_hit_* in trace_kernels.hpp
     // one select (GNode: a leaf's hit successor is its link with kLeafFlag: "stop, test the primitive of the node before it")
     node = boxHit ? nd.hit : nd.link;
     if (node & kLeafFlag) { node &= ~kLeafFlag; ph = PH_LEAF; }
@@ -235,7 +138,7 @@ __global__ void __launch_bounds__(256) query_wave_kernel(DeviceScene sc, const m
           const QueryRay r = load_query_ray(rays, idx);
           ray = idx; o = r.o; d = r.d; tMin = r.tMin;
           if constexpr (FAST) { inv = fast_inverse(d); sh = make_shear_fast(d, inv); fast_box_setup(o, inv, oi, slabPad); }
-          else { inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z); sh = make_shear(d, inv); literal = needs_literal_box(o, d, inv, r.tMin, r.tMax); }
+          else { inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z); sh = make_shear(d, inv); literal = query_needs_literal_box(o, d, inv, r.tMin, r.tMax); }
           hit.t = r.tMax; hit.leaf = kNoLeaf; hit.b0 = hit.b1 = hit.b2 = 0.f;
           node = 0;
           ++casts;
@@ -267,7 +170,9 @@ __global__ void __launch_bounds__(256) query_wave_kernel(DeviceScene sc, const m
           if (STATS) cs.leaves++;
           const uint32_t atLeaf = (node >> 5) - 1u;
           float t, b0, b1, b2;
-          const bool accept = leaf_test<DF, FAST, ROT>(sc, atLeaf, o, d, sh, tMin, hit.t, t, b0, b1, b2);
+          bool accept;
+          if constexpr (ROT) accept = prim_hit<DF, false, true>(sc.leavesRot[atLeaf].b[sh.kz], o, d, sh, tMin, hit.t, t, b0, b1, b2);
+          else accept = prim_hit<DF, FAST>(sc.leaves[atLeaf], o, d, sh, tMin, hit.t, t, b0, b1, b2);
           if (ANY_HIT) {
             hit.leaf = accept ? atLeaf : hit.leaf;
             ph = (accept || node >= numNodes) ? PH_SHADE : PH_NODE;

@@ -63,6 +63,7 @@ __host__ __device__ __forceinline__ uint32_t leaf_geom(const GLeaf& L) { return 
 struct __attribute__((aligned(8))) GLeafBlock { uint32_t type; float f[9]; };
 struct __attribute__((aligned(128))) GLeafRot { GLeafBlock b[3]; uint32_t pad[2]; };
 static_assert(sizeof(GLeafBlock) == 40 && sizeof(GLeafRot) == 128, "GLeafRot: three 40-byte blocks in a 128-byte line");
+__device__ __forceinline__ uint32_t leaf_kind(const GLeafBlock& B) { return B.type & 0xFFFFu; }
 
 struct DeviceScene {
   const GNode* nodes;        uint32_t numNodes;
@@ -136,6 +137,20 @@ __device__ __forceinline__ Shear make_shear_fast(f3 d, f3 inv) {
   s.sx = -comp(d, kx) * s.sz;
   s.sy = -comp(d, ky) * s.sz;
   return s;
+}
+
+// FAST tier, per cast: the constant terms of the box test's FMAs (-o/d) and the pad of its far side. An axis the ray runs
+// parallel to (v_rcp_f32 of a zero component: infinite) would make them inf - inf = NaN, and every box would then read as
+// hit (fminf / fmaxf drop a NaN): correct, but such a ray walked the whole BVH. A large finite stand-in for 1/d gives what
+// the slab test means for a parallel ray - no constraint when the origin lies between the planes (-huge, +huge), a miss
+// otherwise - through the same FMAs, and that axis is left out of the pad (its cancellation error is beside the point: the
+// products are huge either way). The shear keeps the true reciprocal (make_shear_fast is called before this).
+__device__ __forceinline__ void fast_box_setup(f3 o, f3& inv, f3& oi, float& slabPad) {
+  const float big = 1e18f;
+  const bool px = !(fabsf(inv.x) < big), py = !(fabsf(inv.y) < big), pz = !(fabsf(inv.z) < big);
+  inv = mk(px ? copysignf(big, inv.x) : inv.x, py ? copysignf(big, inv.y) : inv.y, pz ? copysignf(big, inv.z) : inv.z);
+  oi = mk(-(o.x * inv.x), -(o.y * inv.y), -(o.z * inv.z));
+  slabPad = 4.8e-7f * fmaxf(fmaxf(px ? 0.f : fabsf(oi.x), py ? 0.f : fabsf(oi.y)), pz ? 0.f : fabsf(oi.z));
 }
 
 __device__ __forceinline__ f3 permute_kz(f3 p, uint32_t kz) {
@@ -244,8 +259,9 @@ __device__ __forceinline__ float intersect_triangle_fast(f3 p0, f3 p1, f3 p2, f3
   return miss ? 0.f : t;
 }
 
-// Primitives.cpp:24-47
-__device__ __forceinline__ float intersect_sphere(const GLeaf& L, f3 o, f3 d, float tMin) {
+// Primitives.cpp:24-47 (Rec: GLeaf, or the GLeafBlock of a GLeafRot: the same type and nine floats)
+template <class Rec>
+__device__ __forceinline__ float intersect_sphere(const Rec& L, f3 o, f3 d, float tMin) {
   const float radius2 = L.f[4];
   const f3 f = mk(L.f[0], L.f[1], L.f[2]) - o;
   const float rd2 = 1.f / sqnorm(d);
@@ -265,7 +281,8 @@ __device__ __forceinline__ float intersect_sphere(const GLeaf& L, f3 o, f3 d, fl
 }
 
 // Primitives.cpp:49-67
-__device__ __forceinline__ float intersect_disc(const GLeaf& L, f3 o, f3 d) {
+template <class Rec>
+__device__ __forceinline__ float intersect_disc(const Rec& L, f3 o, f3 d) {
   const f3 n = mk(L.f[0], L.f[1], L.f[2]), c = mk(L.f[3], L.f[4], L.f[5]);
   const float r2 = L.f[6];
   const float angle = dot(n, d);
@@ -281,6 +298,103 @@ __device__ __forceinline__ float intersect_disc(const GLeaf& L, f3 o, f3 d) {
   return 0.f;
 }
 
+// ---- the box test and the primitive test: one copy for every kernel that walks the BVH ------------------------------
+// Box test: CompactBVH2Node.cpp:5-22 + intersectRaySlab (CompactBVH2Node.hpp:14-50). Per axis the reference computes the
+// slab products (plane - o) * (1/d) of the node's min and max plane (box_hit_products), orders them with a compare and
+// swap, scales the far one by kSlabScale and narrows [t0, t1] with an ordered compare / select on each side; the box is
+// hit when !(t0 > t1). Evaluating all three slabs before that one test is the same predicate as the reference's per-axis
+// early outs, since t0 only grows and t1 only shrinks across the axes.
+//   box_hit_literal_axis  that sequence for one axis, literally: it is exact for every input, NaN included.
+//   box_hit_span          the min / max form. With no NaN among the slab products, tMin and tCur the ordered compare /
+//                         selects ARE min / max: swap(tmin, tmax) = (min, max), "t0 = tmin > t0 ? tmin : t0" = max,
+//                         "t1 = tmax < t1 ? tmax : t1" = min, in any axis order; the sign of a zero never reaches the
+//                         result (only t0 > t1 is used). The far side is scaled ONCE: x -> fl(x * kSlabScale) is monotone
+//                         non-decreasing, so min(fl(bx*s), fl(by*s), fl(bz*s)) == fl(min(bx, by, bz) * s) bit for bit.
+//                         `literal` lanes - a ray for which a product or a bound can be NaN (needs_literal_box) - redo the
+//                         test with the literal sequence, so NaN cases stay bit-identical too.
+// FAST (the tolerance tier, box_hit_products_fast): the products as fma(plane, 1/d, -o/d) (fast_box_setup). That carries an
+// ABSOLUTE error of about eps * |o/d| (the two terms cancel), far more than the eps * |t| of the exact tier's products and
+// more than the 1 + 2 gamma(3) scale covers, so a thin box far from the origin could be missed falsely. The far side is
+// therefore widened by 8 eps * max |o/d| (slabPad, per cast) - inside the instruction that applies the scale, so the test
+// stays as cheap and errs on the side of visiting. (On the box scene the pad changes nothing measurable: the tier's
+// differences from the exact one come from the reference's own knife-edge self-intersections) No literal
+// fallback: with fminf / fmaxf a NaN product drops out.
+struct Slabs { float ax, bx, ay, by, az, bz; };      // per axis: the slab products of the min and the max plane
+struct BoxSpan { float t0, t1; };
+__device__ __forceinline__ bool box_hit(const BoxSpan& s) { return !(s.t0 > s.t1); }
+
+__device__ __forceinline__ Slabs box_hit_products(const GNode& nd, f3 o, f3 inv) {
+  return {(nd.minx - o.x) * inv.x, (nd.maxx - o.x) * inv.x, (nd.miny - o.y) * inv.y, (nd.maxy - o.y) * inv.y, (nd.minz - o.z) * inv.z, (nd.maxz - o.z) * inv.z};
+}
+__device__ __forceinline__ Slabs box_hit_products_fast(const GNode& nd, f3 inv, f3 oi) {
+  return {__builtin_fmaf(nd.minx, inv.x, oi.x), __builtin_fmaf(nd.maxx, inv.x, oi.x), __builtin_fmaf(nd.miny, inv.y, oi.y),
+          __builtin_fmaf(nd.maxy, inv.y, oi.y), __builtin_fmaf(nd.minz, inv.z, oi.z), __builtin_fmaf(nd.maxz, inv.z, oi.z)};
+}
+
+__device__ __forceinline__ void box_hit_literal_axis(float tmin, float tmax, float& t0, float& t1) {
+  if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; }
+  tmax *= kSlabScale;
+  t0 = tmin > t0 ? tmin : t0;
+  t1 = tmax < t1 ? tmax : t1;
+}
+
+template <bool FAST>
+__device__ __forceinline__ BoxSpan box_hit_span(const Slabs& s, float tMin, float tCur, float slabPad, bool literal) {
+  BoxSpan r;
+  r.t0 = fmaxf(fmaxf(fminf(s.ax, s.bx), fminf(s.ay, s.by)), fmaxf(fminf(s.az, s.bz), tMin));
+  r.t1 = FAST ? fminf(__builtin_fmaf(fminf(fminf(fmaxf(s.ax, s.bx), fmaxf(s.ay, s.by)), fmaxf(s.az, s.bz)), kSlabScale, slabPad), tCur)
+              : fminf(fminf(fminf(fmaxf(s.ax, s.bx), fmaxf(s.ay, s.by)), fmaxf(s.az, s.bz)) * kSlabScale, tCur);
+  if (!FAST && literal) {
+    r.t0 = tMin; r.t1 = tCur;
+    box_hit_literal_axis(s.ax, s.bx, r.t0, r.t1);
+    box_hit_literal_axis(s.ay, s.by, r.t0, r.t1);
+    box_hit_literal_axis(s.az, s.bz, r.t0, r.t1);
+  }
+  return r;
+}
+
+__device__ __forceinline__ bool box_hit_exact(const GNode& nd, f3 o, f3 inv, float tMin, float tCur, bool literal) {
+  return box_hit(box_hit_span<false>(box_hit_products(nd, o, inv), tMin, tCur, 0.f, literal));
+}
+__device__ __forceinline__ bool box_hit_fast(const GNode& nd, f3 inv, f3 oi, float slabPad, float tMin, float tCur) {
+  return box_hit(box_hit_span<true>(box_hit_products_fast(nd, inv, oi), tMin, tCur, slabPad, false));
+}
+
+// Whether a path-tracing cast (tMin = 0, tMax = +inf) needs the literal box test: with a finite origin and a finite
+// reciprocal direction no slab product can be NaN. A zero or denormal direction component, or a non-finite origin, makes it needed.
+__device__ __forceinline__ bool needs_literal_box(f3 o, f3 inv) {
+  return !(fabsf(inv.x) < kInf && fabsf(inv.y) < kInf && fabsf(inv.z) < kInf && fabsf(o.x) < kInf && fabsf(o.y) < kInf && fabsf(o.z) < kInf);
+}
+
+// Where a primitive test needs the ray's direction: the value itself, or a callable that fetches it (only spheres and discs
+// need it, so a kernel that keeps the direction out of registers loads it in that branch alone).
+__device__ __forceinline__ f3 ray_dir(f3 d) { return d; }
+template <class F> __device__ __forceinline__ f3 ray_dir(const F& load) { return load(); }
+
+// The primitive test on a leaf record the caller has loaded (Mesh.cpp:6-104, Primitives.cpp:24-67) and the reference's
+// acceptance t > tMin && t < closest (CompactBvh.hpp:124 / :60). Rec: GLeaf, or for ROT the GLeafBlock of the cast's shear
+// axis (the vertices arrive rotated: intersect_triangle PRE). Returns whether the hit is accepted, with t and the barycentrics
+// (0 for spheres and discs).
+template <bool DF = false, bool FAST = false, bool ROT = false, class Rec, class Dir>
+__device__ __forceinline__ bool prim_hit(const Rec& L, f3 o, const Dir& d, const Shear& sh, float tMin, float tCur, float& t, float& b0, float& b1, float& b2) {
+  static_assert(!(FAST && ROT), "the FAST triangle test has no pre-rotated form");
+  b0 = b1 = b2 = 0.f;
+  bool cand;
+  if (leaf_kind(L) == LEAF_TRI) {
+    const f3 p0 = mk(L.f[0], L.f[1], L.f[2]), p1 = mk(L.f[3], L.f[4], L.f[5]), p2 = mk(L.f[6], L.f[7], L.f[8]);
+    if constexpr (ROT) t = intersect_triangle<DF, true>(p0, p1, p2, permute_kz(o, sh.kz), sh, b0, b1, b2);
+    else if constexpr (FAST) t = intersect_triangle_fast(p0, p1, p2, o, sh, b0, b1, b2);
+    else t = intersect_triangle<DF>(p0, p1, p2, o, sh, b0, b1, b2);
+    cand = t > 0.f && t < kInf;                 // Mesh.hpp:93
+  } else {
+    const f3 dir = ray_dir(d);
+    if (leaf_kind(L) == LEAF_SPHERE) t = intersect_sphere(L, o, dir, tMin);    // Failed() carries t = 0, rejected by t > tMin
+    else t = intersect_disc(L, o, dir);
+    cand = true;
+  }
+  return cand & (t > tMin) & (t < tCur);
+}
+
 struct Hit {
   float t;            // closest t so far (starts at ray.tMax)
   uint32_t leaf;      // 0xFFFFFFFF = none
@@ -290,60 +404,36 @@ struct Hit {
 
 struct CastStats { uint32_t nodes, leaves; };
 
-// CompactBvh::intersect (ANY_HIT=false, CompactBvh.hpp:80-139) / ::occluded (ANY_HIT=true, :33-78).
-// Box test: CompactBVH2Node.cpp:5-22 + intersectRaySlab (CompactBVH2Node.hpp:14-50). All three
-// slabs are evaluated before the single t0>t1 test; since t0 only grows and t1 only shrinks across
-// the axes, that is the same predicate as the reference's per-axis early outs.
-template <bool ANY_HIT, bool STATS, bool DF = false>
+// CompactBvh::intersect (ANY_HIT=false, CompactBvh.hpp:80-139) / ::occluded (ANY_HIT=true, :33-78). FAST: the tolerance
+// tier's cast set-up, box test and triangle test. Box test: see box_hit_* above; the exact tiers run the literal sequence
+// axis by axis, every lane, so nothing decides per cast which form applies.
+template <bool ANY_HIT, bool STATS, bool DF = false, bool FAST = false>
 __device__ __forceinline__ bool traverse(const DeviceScene& sc, f3 o, f3 d, float tMin, float tMax, Hit& hit, CastStats& cs) {
-  const f3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
-  const Shear sh = make_shear(d);
+  f3 inv = FAST ? fast_inverse(d) : mk(1.f / d.x, 1.f / d.y, 1.f / d.z), oi = mk(0.f, 0.f, 0.f);
+  const Shear sh = FAST ? make_shear_fast(d, inv) : make_shear(d);
+  float slabPad = 0.f;
+  if constexpr (FAST) fast_box_setup(o, inv, oi, slabPad);
   hit.t = tMax; hit.leaf = 0xFFFFFFFFu; hit.geomID = 0xFFFFu; hit.b0 = hit.b1 = hit.b2 = 0.f;
   const uint32_t numNodes = sc.numNodes;
   uint32_t i = 0;
   while (i < numNodes) {
     const GNode nd = sc.nodes[i];
     if (STATS) cs.nodes++;
-    float t0 = tMin, t1 = hit.t;
-    {
-      float tmin = (nd.minx - o.x) * inv.x, tmax = (nd.maxx - o.x) * inv.x;
-      if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; }
-      tmax *= kSlabScale;
-      t0 = tmin > t0 ? tmin : t0;
-      t1 = tmax < t1 ? tmax : t1;
+    bool boxHit;
+    if constexpr (FAST) boxHit = box_hit_fast(nd, inv, oi, slabPad, tMin, hit.t);
+    else {
+      float t0 = tMin, t1 = hit.t;
+      box_hit_literal_axis((nd.minx - o.x) * inv.x, (nd.maxx - o.x) * inv.x, t0, t1);
+      box_hit_literal_axis((nd.miny - o.y) * inv.y, (nd.maxy - o.y) * inv.y, t0, t1);
+      box_hit_literal_axis((nd.minz - o.z) * inv.z, (nd.maxz - o.z) * inv.z, t0, t1);
+      boxHit = !(t0 > t1);
     }
-    {
-      float tmin = (nd.miny - o.y) * inv.y, tmax = (nd.maxy - o.y) * inv.y;
-      if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; }
-      tmax *= kSlabScale;
-      t0 = tmin > t0 ? tmin : t0;
-      t1 = tmax < t1 ? tmax : t1;
-    }
-    {
-      float tmin = (nd.minz - o.z) * inv.z, tmax = (nd.maxz - o.z) * inv.z;
-      if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; }
-      tmax *= kSlabScale;
-      t0 = tmin > t0 ? tmin : t0;
-      t1 = tmax < t1 ? tmax : t1;
-    }
-    const bool boxHit = !(t0 > t1);
     const bool isLeaf = node_is_leaf(nd);
     if (boxHit && isLeaf) {
       if (STATS) cs.leaves++;
       const GLeaf L = sc.leaves[i];               // (leaves[] is indexed by node)
-      float t, b0 = 0.f, b1 = 0.f, b2 = 0.f;
-      bool cand;
-      if (leaf_kind(L) == LEAF_TRI) {
-        t = intersect_triangle<DF>(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), o, sh, b0, b1, b2);
-        cand = t > 0.f && t < kInf;                 // Mesh.hpp:93
-      } else if (leaf_kind(L) == LEAF_SPHERE) {
-        t = intersect_sphere(L, o, d, tMin);
-        cand = true;                                // Failed() carries t = 0, rejected by t > tMin below
-      } else {
-        t = intersect_disc(L, o, d);
-        cand = true;
-      }
-      if (cand && t > tMin && t < hit.t) {          // CompactBvh.hpp:124 / :60 (hit.t == ray.tMax for any-hit)
+      float t, b0, b1, b2;
+      if (prim_hit<DF, FAST>(L, o, d, sh, tMin, hit.t, t, b0, b1, b2)) {      // (hit.t == ray.tMax for any-hit)
         if (ANY_HIT) return true;
         hit.t = t; hit.leaf = i; hit.geomID = leaf_geom(L); hit.b0 = b0; hit.b1 = b1; hit.b2 = b2;
       }

@@ -245,22 +245,7 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES_PER_SIMD) path_trace_pool_ke
       auto nodeBodyT = [&](auto exactTag) -> bool {
         GNode nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + (node << 5));
         if (STATS) cs.nodes++;
-        // Box test (CompactBVH2Node.cpp:5-22, intersectRaySlab CompactBVH2Node.hpp:14-50); min/max form and the
-        // literal fallback exactly as in trace_wavefront.hpp
-        const float ax = (nd.minx - o.x) * inv.x, bx = (nd.maxx - o.x) * inv.x;
-        const float ay = (nd.miny - o.y) * inv.y, by = (nd.maxy - o.y) * inv.y;
-        const float az = (nd.minz - o.z) * inv.z, bz = (nd.maxz - o.z) * inv.z;
-        float t0 = fmaxf(fmaxf(fminf(ax, bx), fminf(ay, by)), fmaxf(fminf(az, bz), 0.f));
-        float t1 = fminf(fminf(fminf(fmaxf(ax, bx), fmaxf(ay, by)), fmaxf(az, bz)) * kSlabScale, hit.t);
-        if constexpr (decltype(exactTag)::value) {
-          if (exactSlab) {
-            t0 = 0.f; t1 = hit.t;
-            { float tmin = ax, tmax = bx; if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; } tmax *= kSlabScale; t0 = tmin > t0 ? tmin : t0; t1 = tmax < t1 ? tmax : t1; }
-            { float tmin = ay, tmax = by; if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; } tmax *= kSlabScale; t0 = tmin > t0 ? tmin : t0; t1 = tmax < t1 ? tmax : t1; }
-            { float tmin = az, tmax = bz; if (tmin > tmax) { const float s = tmin; tmin = tmax; tmax = s; } tmax *= kSlabScale; t0 = tmin > t0 ? tmin : t0; t1 = tmax < t1 ? tmax : t1; }
-          }
-        }
-        const bool boxHit = !(t0 > t1);
+        const bool boxHit = box_hit_exact(nd, o, inv, 0.f, hit.t, decltype(exactTag)::value && exactSlab);      // box test: see box_hit_* in trace_kernels.hpp
         const bool isLeaf = node_is_leaf(nd);
         pendLeaf = node;                                          // (leaves[] is indexed by node)
         node = (boxHit && !isLeaf) ? node + 1 : (nd.link >> 5);          // (a lane that waits for a primitive test already stands at the node behind it)
@@ -299,19 +284,9 @@ __global__ void __launch_bounds__(64 * WAVES, WAVES_PER_SIMD) path_trace_pool_ke
           if (ph == PP_LEAF) {
             if (STATS) cs.leaves++;
             const GLeaf L = sc.leaves[pendLeaf];
-            float t, b0 = 0.f, b1 = 0.f, b2 = 0.f;
-            bool cand;
-            const uint32_t kind = leaf_kind(L);
-            if (kind == LEAF_TRI) {
-              t = intersect_triangle(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), o, sh, b0, b1, b2);
-              cand = t > 0.f && t < kInf;
-            } else {
-              const f3 d = mk(SF(PW_D, slot), SF(PW_D + 1, slot), SF(PW_D + 2, slot));      // (only spheres and discs need the direction itself)
-              if (kind == LEAF_SPHERE) t = intersect_sphere(L, o, d, 0.f);
-              else t = intersect_disc(L, o, d);
-              cand = true;
-            }
-            if (cand && t > 0.f && t < hit.t) { hit.t = t; hit.leaf = pendLeaf; hit.b0 = b0; hit.b1 = b1; hit.b2 = b2; }
+            const auto dir = [&] { return mk(SF(PW_D, slot), SF(PW_D + 1, slot), SF(PW_D + 2, slot)); };      // (only spheres and discs need the direction itself)
+            float t, b0, b1, b2;
+            if (prim_hit(L, o, dir, sh, 0.f, hit.t, t, b0, b1, b2)) { hit.t = t; hit.leaf = pendLeaf; hit.b0 = b0; hit.b1 = b1; hit.b2 = b2; }
             ph = (node >= numNodes) ? PP_FIN : PP_NODE;
           }
           if (tune.leafThenNode) {

@@ -90,20 +90,6 @@ struct WaveExtras {
 // from ex.slotColor. FIXED_TUNE: the scheduling weights are the compile-time defaults (kDefaultTune) instead of the
 // `tune` argument. The two default-path instantiations (<.., 0, true> and <.., 1, true>) carry neither the other mode's
 // code nor the ten weights in scalar registers: no scalar spills (33 before), -2.5 % frame time.
-// FAST tier, per cast: the constant terms of the box test's FMAs (-o/d) and the pad of its far side. An axis the ray runs
-// parallel to (v_rcp_f32 of a zero component: infinite) would make them inf - inf = NaN, and every box would then read as
-// hit (fminf / fmaxf drop a NaN): correct, but such a ray walked the whole BVH. A large finite stand-in for 1/d gives what
-// the slab test means for a parallel ray - no constraint when the origin lies between the planes (-huge, +huge), a miss
-// otherwise - through the same FMAs, and that axis is left out of the pad (its cancellation error is beside the point: the
-// products are huge either way). The shear keeps the true reciprocal (make_shear_fast is called before this).
-__device__ __forceinline__ void fast_box_setup(f3 o, f3& inv, f3& oi, float& slabPad) {
-  const float big = 1e18f;
-  const bool px = !(fabsf(inv.x) < big), py = !(fabsf(inv.y) < big), pz = !(fabsf(inv.z) < big);
-  inv = mk(px ? copysignf(big, inv.x) : inv.x, py ? copysignf(big, inv.y) : inv.y, pz ? copysignf(big, inv.z) : inv.z);
-  oi = mk(-(o.x * inv.x), -(o.y * inv.y), -(o.z * inv.z));
-  slabPad = 4.8e-7f * fmaxf(fmaxf(px ? 0.f : fabsf(oi.x), py ? 0.f : fabsf(oi.y)), pz ? 0.f : fabsf(oi.z));
-}
-
 // How many lanes below this one are set in `mask` (v_mbcnt: no per-lane bit mask held in registers across the kernel).
 __device__ __forceinline__ uint32_t lane_rank(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -338,7 +324,8 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
           if (LDS_NODES && node < (ldsNodeCount << 5)) nd = *reinterpret_cast<const GNode*>(dynLds + node);
           else nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + node);
           if (STATS) cs.nodes++;
-          // Box test (CompactBVH2Node.cpp:5-22, intersectRaySlab CompactBVH2Node.hpp:14-50).
+          // Box test (CompactBVH2Node.cpp:5-22, intersectRaySlab CompactBVH2Node.hpp:14-50): box_hit_span of trace_kernels.hpp,
+          // spelled out here because hipcc schedules this kernel differently when the same arithmetic comes through the helper.
           // Fast form: with finite origin and finite inverse direction no slab product can be NaN, and for
           // non-NaN values the reference's ordered compare/selects ARE min/max: swap(tmin,tmax) = (min,max),
           // "t0 = tmin > t0 ? tmin : t0" = max, "t1 = tmax < t1 ? tmax : t1" = min, in any axis order; the
