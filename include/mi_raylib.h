@@ -184,6 +184,39 @@ int mi_render_device(mi_scene* scene, int mode, void* d_rays, size_t n, void* hi
 int mi_query_device(mi_scene* scene, int kind, const void* d_rays, void* d_out, size_t n, void* hip_stream);
 int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n);
 
+/* Geometry updates: new positions for the primitives of a live scene, the topology kept - triangles, geometry list, materials and
+ * the BVH's shape - and every BVH box recomputed on the device (a refit: Embree's RTC_BUILD_QUALITY_REFIT commit, OptiX's
+ * OPTIX_BUILD_OPERATION_UPDATE). Any pointer may be NULL = keep; a non-NULL array must have exactly the scene's count (a NULL array
+ * must come with count 0). mesh_normals only for scenes created with normals.
+ * Result. The nodes are those mi_refit_compact_bvh (mi_scene_host.h) computes from the moved arrays, byte for byte, and every render
+ * and query afterwards equals that of a scene freshly created from the moved arrays and those nodes, bit for bit. A refit keeps the
+ * old topology, so under large motion boxes overlap more and traces slow down; a rebuild is a new mi_scene_create.
+ * Ordering. The update waits for all work already enqueued on the scene, on any stream (renders and queries), before it overwrites a
+ * device record: a render or query enqueued before the update sees the old geometry, whatever its stream.
+ * Synchronous return. The update returns once the new geometry is in place; work enqueued after it returns sees it. It reads back
+ * one small record (the refusal flag and the root box). mi_scene_update_device takes DEVICE arrays and does its kernels and copies on
+ * hip_stream (a hipStream_t as void*; NULL = the null stream), then waits for that stream only; mi_scene_update takes HOST arrays.
+ * Refusal. MI_ERR_INVALID_ARG leaves the scene unchanged - every record, node and later result: a null scene or update, a count
+ * that differs from the scene's (or a count without its array), normals for a scene without normals, a resulting node box that
+ * is not finite, an extent above 65504 - exactly when mi_scene_create from the moved arrays and the refit nodes would fail.
+ * Counters, options and the NIF environment are untouched; a scene made by mi_scene_create_from_blob updates the same way.
+ * The first update builds the refit's device tables (about 100 bytes per node); a scene never updated allocates nothing for them.
+ * mi_scene_get_bvh copies the scene's current compact nodes to `out` (HOST memory, capacity nodes); *num_nodes = the node count
+ * (out == NULL: only the count). */
+typedef struct {
+  const mi_vec3*   mesh_verts;   uint32_t num_verts;
+  const mi_vec3*   mesh_normals; uint32_t num_normals;   /* only for scenes created with normals */
+  const mi_sphere* spheres;      uint32_t num_spheres;
+  const mi_disc*   discs;        uint32_t num_discs;
+} mi_geometry_update;
+
+int mi_scene_update(mi_scene* scene, const mi_geometry_update* host_arrays);                            /* host memory */
+int mi_scene_update_device(mi_scene* scene, const mi_geometry_update* device_arrays, void* hip_stream); /* device memory */
+int mi_scene_get_bvh(mi_scene* scene, mi_bvh_node* out, uint32_t capacity, uint32_t* num_nodes);       /* current compact nodes, host out */
+/* Measurement only (tools/bench_refit.py): the last update's pass times in milliseconds from HIP events on its stream,
+ * out = {leaf boxes, interior boxes, record rewrite and copies}; zeros unless scene option "refit_timing" is 1. */
+int mi_get_refit_timing(mi_scene* scene, double out[3]);
+
 /* Replaces: IpuScene::getTraceTimeSecs (IpuScene.hpp:55). Wall time of the last mi_render. */
 double mi_trace_time_secs(const mi_scene* scene);
 
@@ -282,6 +315,7 @@ int mi_scene_set_ray_batch(mi_scene* scene, size_t rays_per_batch);
  *   "nif_trace_wgs" 0..16           with nif_overlap: workgroups per compute unit of a trace launch that runs beside the previous batch's MLP
  *                                   (0 = all that stay resident, the default)
  *   "nif_timing"    0 | 1           bracket every MLP launch of a NIF render with HIP events (mi_get_nif_timing)
+ *   "refit_timing"  0 | 1           bracket the passes of mi_scene_update* with HIP events (mi_get_refit_timing)
  *   "leaf_rot"      0 | 1           scenes without vertex normals: the default kernel reads primitive records pre-rotated for the cast's shear axis (default 1)
  *   "lean_hit"      0 | 1           scenes without vertex normals run the build of the default kernel that carries no barycentrics (default 1)
  *   "coords"        0 | 1           (pixel, segment) work units read the pixel's (u, v) from a compact copy of the stream gathered once
@@ -324,7 +358,8 @@ int mi_nif_infer_device(mi_scene* scene, const float* d_u, const float* d_v, flo
  * `transport`: 0 = RCCL as soon as more than one device takes part (peer copies otherwise), 1 = RCCL always, 2 = peer
  * copies only. RCCL is loaded with dlopen when the first group needs it.
  * mi_group_scene hands out a replica's scene for the per-scene setters (mi_scene_set_nif, mi_scene_set_option, ...),
- * which must be applied to every replica alike. */
+ * which must be applied to every replica alike. The same holds for geometry updates: mi_scene_update / mi_scene_update_device on
+ * every replica's scene, with the same arrays (there is no group-level update entry). */
 typedef struct mi_group mi_group;
 int mi_group_create(const mi_scene_desc* desc, const int32_t* devices, uint32_t num_replicas, int32_t transport, mi_group** out);
 void mi_group_destroy(mi_group* group);

@@ -51,6 +51,15 @@ int mi_build_compact_bvh(const float* lower, const float* upper, const uint16_t*
                          const uint32_t* prim_ids, uint32_t n,
                          mi_bvh_node* nodes, uint32_t* num_nodes, uint32_t* max_leaf_depth);
 
+/* Refit: the topology of desc->bvh_nodes (desc->num_nodes nodes: links, geomIDs, primIDs) kept, every box recomputed from desc's
+ * geometry arrays - a leaf's the box of its primitive (a triangle's three vertices grown from an empty box, a sphere's or disc's
+ * centre +- radius), an interior node's the union of its two children's - and encoded as mi_build_compact_bvh encodes it.
+ * Writes desc->num_nodes nodes to `out` (which may alias desc->bvh_nodes). Fails with the builder's message ("Cannot compress BVH
+ * bounds into fp16 (half)", MI_ERR_IO) on an extent above 65504, and with MI_ERR_INVALID_ARG on a node box that is not finite
+ * (what mi_scene_create refuses) or an index out of range; `out` is then partly written. The reference the device refit
+ * (mi_scene_update, mi_raylib.h) is checked against, and the way to build the fresh scene an updated one must equal. */
+int mi_refit_compact_bvh(const mi_scene_desc* desc, mi_bvh_node* out);
+
 /* initPerspectiveRayStream(rayStream, image, data, nullptr) + zeroRgb: window_w*window_h rays in
  * row-major window order, origin 0, un-jittered pinhole directions, u=row, v=col. */
 int mi_init_ray_stream(const mi_scene_desc* desc, mi_trace_result* rays, size_t capacity);

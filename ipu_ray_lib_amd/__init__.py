@@ -91,6 +91,14 @@ class SceneDesc(C.Structure):
         return int(self.window_w) * int(self.window_h)
 
 
+class GeometryUpdate(C.Structure):
+    """mi_geometry_update (include/mi_raylib.h): new positions for a live scene's primitives; NULL = keep."""
+    _fields_ = [("mesh_verts", C.c_void_p), ("num_verts", C.c_uint32),
+                ("mesh_normals", C.c_void_p), ("num_normals", C.c_uint32),
+                ("spheres", C.c_void_p), ("num_spheres", C.c_uint32),
+                ("discs", C.c_void_p), ("num_discs", C.c_uint32)]
+
+
 class NifDesc(C.Structure):
     """mi_nif_desc (include/mi_scene_host.h)."""
     _fields_ = [("num_layers", C.c_uint32), ("kernels", C.POINTER(C.POINTER(C.c_float))),
@@ -130,6 +138,7 @@ def host_lib() -> C.CDLL:
         lib.mi_host_scene_destroy.restype = None
         lib.mi_build_compact_bvh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                              C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.mi_refit_compact_bvh.argtypes = [C.POINTER(SceneDesc), C.c_void_p]
         lib.mi_init_ray_stream.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_size_t]
         lib.mi_scale_rgb.argtypes = [C.c_void_p, C.c_size_t, C.c_float]
         lib.mi_scale_rgb.restype = None
@@ -193,6 +202,9 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_scene_set_ray_batch.argtypes = [C.c_void_p, C.c_size_t]
         lib.mi_nif_infer_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_scene_update.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate)]
+        lib.mi_scene_update_device.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_void_p]
+        lib.mi_scene_get_bvh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.mi_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
         lib.mi_group_destroy.argtypes = [C.c_void_p]
@@ -334,6 +346,27 @@ def _aligned_copy(a: np.ndarray) -> np.ndarray:
     out = aligned_bytes(a.size * a.dtype.itemsize).view(a.dtype)
     out[...] = a.reshape(-1)
     return out
+
+
+def refit_compact_bvh(desc: SceneDesc) -> np.ndarray:
+    """mi_refit_compact_bvh: desc's BVH topology with every box recomputed from desc's arrays (a BVH_NODE array). The host reference
+    of IpuScene.update_geometry; raises RaylibError where mi_scene_update refuses (a box that is not finite, an extent above 65504)."""
+    out = np.zeros(desc.num_nodes, dtype=BVH_NODE)
+    _check_host(host_lib().mi_refit_compact_bvh(C.byref(desc), out.ctypes.data))
+    return out
+
+
+def _geometry_array(a, dtype, width):
+    """A C-contiguous `dtype` array from a `dtype` array or an [n, width] float32 array (None stays None)."""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.dtype != dtype:
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != width:
+            raise ValueError(f"expected a {dtype} array or an [n, {width}] float32 array, got shape {a.shape}")
+        return a.view(dtype).reshape(-1)
+    return np.ascontiguousarray(a).reshape(-1)
 
 
 def serialise_scene(desc: SceneDesc) -> np.ndarray:
@@ -520,6 +553,49 @@ class IpuScene:
         halves = raw.view(torch.int16)
         return {"t": raw[:, 0], "prim_id": words[:, 1], "geom_id": halves[:, 4].to(torch.int32),
                 "normal": raw[:, 3:6], "bary": raw[:, 6:8]}
+
+    # -- geometry updates (mi_scene_update*): new primitive positions, the BVH refit on the device ------------------------------------
+    def update_geometry(self, vertices=None, normals=None, spheres=None, discs=None) -> "IpuScene":
+        """New positions for the scene's primitives, HOST arrays: VEC3 / SPHERE / DISC arrays or [n, 3] / [n, 4] / [n, 7] float32
+        (None = keep; a given array has exactly the scene's count). Synchronous; work enqueued before sees the old geometry."""
+        arrs = [_geometry_array(vertices, VEC3, 3), _geometry_array(normals, VEC3, 3), _geometry_array(spheres, SPHERE, 4),
+                _geometry_array(discs, DISC, 7)]
+        u = GeometryUpdate()
+        for (ptr, cnt), a in zip((("mesh_verts", "num_verts"), ("mesh_normals", "num_normals"), ("spheres", "num_spheres"),
+                                  ("discs", "num_discs")), arrs):
+            if a is not None:
+                setattr(u, ptr, a.ctypes.data)
+                setattr(u, cnt, a.size)
+        self._check(self._lib.mi_scene_update(self._h, C.byref(u)))
+        return self
+
+    def update_geometry_device(self, vertices=None, normals=None, spheres=None, discs=None) -> "IpuScene":
+        """The same from contiguous float32 CUDA tensors ([n, 3] / [n, 3] / [n, 4] / [n, 7]), on torch.cuda.current_stream()."""
+        import torch
+        u = GeometryUpdate()
+        keep = []
+        dev = None
+        for (ptr, cnt, width), t in zip((("mesh_verts", "num_verts", 3), ("mesh_normals", "num_normals", 3), ("spheres", "num_spheres", 4),
+                                         ("discs", "num_discs", 7)), (vertices, normals, spheres, discs)):
+            if t is None:
+                continue
+            if not t.is_cuda or t.dtype != torch.float32 or t.ndim != 2 or t.shape[1] != width or not t.is_contiguous():
+                raise ValueError(f"update_geometry_device: {ptr} must be a contiguous float32 CUDA tensor of shape [n, {width}]")
+            dev = t.device
+            keep.append(t)
+            setattr(u, ptr, t.data_ptr())
+            setattr(u, cnt, t.shape[0])
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None else 0
+        self._check(self._lib.mi_scene_update_device(self._h, C.byref(u), C.c_void_p(stream)))
+        return self
+
+    def bvh_nodes(self) -> np.ndarray:
+        """The scene's current compact BVH nodes (mi_scene_get_bvh): a BVH_NODE array."""
+        n = C.c_uint32()
+        self._check(self._lib.mi_scene_get_bvh(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=BVH_NODE)
+        self._check(self._lib.mi_scene_get_bvh(self._h, out.ctypes.data, out.size, C.byref(n)))
+        return out
 
     def nif_infer_device(self, d_u: int, d_v: int, d_bgr: int, n: int, stream: int = 0):
         self._check(self._lib.mi_nif_infer_device(self._h, C.c_void_p(d_u), C.c_void_p(d_v), C.c_void_p(d_bgr), n, C.c_void_p(stream)))

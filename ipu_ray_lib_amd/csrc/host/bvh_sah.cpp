@@ -18,12 +18,15 @@
 #include <numeric>
 #include <queue>
 #include <stdexcept>
+#include <string>
 
 #include "scene_types.hpp"
 
 namespace mi::host {
 
 namespace {
+
+const char* const kHalfBoundsError = "Cannot compress BVH bounds into fp16 (half)";
 
 struct TreeNode {
   Bounds box;
@@ -195,12 +198,8 @@ struct Reinserter {
 
 mi_bvh_node toCompact(const TreeNode& t, const std::vector<BuildPrim>& prims) {
   mi_bvh_node c;
-  c.min_x = t.box.lo.x; c.min_y = t.box.lo.y; c.min_z = t.box.lo.z;
-  const float dx = t.box.hi.x - t.box.lo.x, dy = t.box.hi.y - t.box.lo.y, dz = t.box.hi.z - t.box.lo.z;
-  const float maxHalf = 65504.f;
-  if (dx > maxHalf || dy > maxHalf || dz > maxHalf)
-    throw std::runtime_error("Cannot compress BVH bounds into fp16 (half)");
-  c.dx = half_not_smaller(dx); c.dy = half_not_smaller(dy); c.dz = half_not_smaller(dz);
+  Box3 b; b.lo = t.box.lo; b.hi = t.box.hi;
+  if (box_encode(b, c.min_x, c.min_y, c.min_z, c.dx, c.dy, c.dz) == kBoxTooLarge) throw std::runtime_error(kHalfBoundsError);
   if (t.prim >= 0) { c.geom_id = prims[t.prim].geomID; c.prim_or_second_child = prims[t.prim].primID; }
   else { c.geom_id = MI_INVALID_GEOM; c.prim_or_second_child = 0; }
   return c;
@@ -260,6 +259,58 @@ void buildCompactBvh(const std::vector<BuildPrim>& prims, std::vector<mi_bvh_nod
   }
   nodes.reserve(2 * prims.size() - 1);
   flatten(b, root, nodes, 1, maxDepth);
+}
+
+// mi_refit_compact_bvh (include/mi_scene_host.h): the topology of desc.bvh_nodes kept, every box recomputed from desc's arrays.
+// Children follow their parent in preorder, so one pass from the last node to the first sees both children of a node
+// before the node: a leaf gets its primitive's box, an interior node the union of its first and second child's boxes, and
+// both are encoded as toCompact encodes them. The reference for the device refit (refit_kernels.hpp).
+void refitCompactBvh(const mi_scene_desc& d, mi_bvh_node* out) {
+  auto need = [](bool ok, const char* what) { if (!ok) throw std::invalid_argument(std::string("mi_refit_compact_bvh: ") + what); };
+  const uint32_t N = d.num_nodes;
+  need(N == 0 || d.bvh_nodes, "bvh_nodes is null");
+  need(d.num_geometry == 0 || d.geometry, "geometry is null");
+  need(d.num_meshes == 0 || (d.mesh_info && d.mesh_tris && d.mesh_verts), "mesh arrays are null");
+  need(d.num_spheres == 0 || d.spheres, "spheres is null");
+  need(d.num_discs == 0 || d.discs, "discs is null");
+  std::vector<Box3> box(N);
+  for (uint32_t i = N; i-- > 0;) {
+    const mi_bvh_node& n = d.bvh_nodes[i];
+    Box3 b;
+    if (n.geom_id != MI_INVALID_GEOM) {
+      need(n.geom_id < d.num_geometry, "leaf geomID out of range");
+      const mi_geom_ref& r = d.geometry[n.geom_id];
+      need(r.type <= 2 && r.index < (r.type == 0 ? d.num_meshes : r.type == 1 ? d.num_spheres : d.num_discs), "geometry index out of range");
+      if (r.type == 0) {
+        const mi_mesh_info& m = d.mesh_info[r.index];
+        need(n.prim_or_second_child < m.num_triangles && (uint64_t)m.first_index + m.num_triangles <= d.num_tris, "leaf primID out of range");
+        f3 p[3];
+        for (int k = 0; k < 3; ++k) {
+          const uint32_t v = d.mesh_tris[3 * ((size_t)m.first_index + n.prim_or_second_child) + k];
+          need(v < m.num_vertices && (uint64_t)m.first_vertex + v < d.num_verts, "triangle vertex index out of range");
+          const mi_vec3& q = d.mesh_verts[m.first_vertex + v];
+          p[k] = mk(q.x, q.y, q.z);
+        }
+        b = triangle_box(p[0], p[1], p[2]);
+      } else if (r.type == 1) {
+        const mi_sphere& s = d.spheres[r.index];
+        b = ball_box(s.x, s.y, s.z, s.radius);
+      } else {
+        const mi_disc& c = d.discs[r.index];
+        b = ball_box(c.cx, c.cy, c.cz, c.r);
+      }
+    } else {
+      const uint32_t second = n.prim_or_second_child;
+      need(i + 1 < N && second > i + 1 && second < N, "BVH is not a depth-first BVH2 (bad second child index)");
+      b = box_union(box[i + 1], box[second]);
+    }
+    box[i] = b;
+    mi_bvh_node c = n;
+    const uint32_t code = box_encode(b, c.min_x, c.min_y, c.min_z, c.dx, c.dy, c.dz);
+    if (code == kBoxTooLarge) throw std::runtime_error(kHalfBoundsError);
+    if (code == kBoxNotFinite) throw std::invalid_argument("mi_refit_compact_bvh: a node box is not finite");
+    out[i] = c;
+  }
 }
 
 }  // namespace mi::host

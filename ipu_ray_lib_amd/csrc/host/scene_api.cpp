@@ -140,6 +140,11 @@ int mi_build_compact_bvh(const float* lower, const float* upper, const uint16_t*
   });
 }
 
+int mi_refit_compact_bvh(const mi_scene_desc* desc, mi_bvh_node* out) {
+  if (!desc || (!out && desc->num_nodes)) { g_err = "mi_refit_compact_bvh: null argument"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { refitCompactBvh(*desc, out); });
+}
+
 // initPerspectiveRayStream with gen == nullptr, then zeroRgb (src/app_utils.cpp:19-53)
 int mi_init_ray_stream(const mi_scene_desc* d, mi_trace_result* rays, size_t capacity) {
   if (!d || !rays) { g_err = "null argument"; return MI_ERR_INVALID_ARG; }

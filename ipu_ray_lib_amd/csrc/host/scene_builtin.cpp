@@ -194,22 +194,21 @@ PackedScene packScene(const SceneDescription& scene) {
       const auto& m = scene.meshes[ref.index];
       for (uint32_t t = 0; t < m.indices.size() / 3; ++t) {
         BuildPrim bp; bp.geomID = (uint16_t)g; bp.primID = t;
-        bp.box.grow(m.vertices[m.indices[3 * t]]);
-        bp.box.grow(m.vertices[m.indices[3 * t + 1]]);
-        bp.box.grow(m.vertices[m.indices[3 * t + 2]]);
+        const Box3 b = triangle_box(m.vertices[m.indices[3 * t]], m.vertices[m.indices[3 * t + 1]], m.vertices[m.indices[3 * t + 2]]);
+        bp.box.lo = b.lo; bp.box.hi = b.hi;
         prims.push_back(bp);
       }
     } else if (ref.type == 1) {
       const auto& s = scene.spheres[ref.index];
       BuildPrim bp; bp.geomID = (uint16_t)g; bp.primID = 0;
-      bp.box.lo = mk(s.x - s.radius, s.y - s.radius, s.z - s.radius);   // Primitives.hpp:53-56
-      bp.box.hi = mk(s.x + s.radius, s.y + s.radius, s.z + s.radius);
+      const Box3 b = ball_box(s.x, s.y, s.z, s.radius);                  // Primitives.hpp:53-56
+      bp.box.lo = b.lo; bp.box.hi = b.hi;
       prims.push_back(bp);
     } else {
       const auto& c = scene.discs[ref.index];
       BuildPrim bp; bp.geomID = (uint16_t)g; bp.primID = 0;
-      bp.box.lo = mk(c.cx - c.r, c.cy - c.r, c.cz - c.r);               // Primitives.hpp:77-81
-      bp.box.hi = mk(c.cx + c.r, c.cy + c.r, c.cz + c.r);
+      const Box3 b = ball_box(c.cx, c.cy, c.cz, c.r);                   // Primitives.hpp:77-81
+      bp.box.lo = b.lo; bp.box.hi = b.hi;
       prims.push_back(bp);
     }
   }

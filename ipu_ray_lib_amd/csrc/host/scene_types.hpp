@@ -96,6 +96,7 @@ struct BuildPrim { Bounds box; uint16_t geomID; uint32_t primID; };
 
 // bvh_sah.cpp
 void buildCompactBvh(const std::vector<BuildPrim>& prims, std::vector<mi_bvh_node>& nodes, uint32_t& maxDepth);
+void refitCompactBvh(const mi_scene_desc& desc, mi_bvh_node* out);
 
 // glb_reader.cpp: meshes of a glTF-binary file with node transforms baked in, file order kept
 std::vector<TriMesh> loadGlbMeshes(const std::string& path, bool loadNormals);

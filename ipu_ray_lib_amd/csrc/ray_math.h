@@ -77,10 +77,10 @@ MI_HD float half_bits_to_float(uint16_t h) {
 #endif
 }
 
-#if !defined(__HIP_DEVICE_COMPILE__)
-// float -> half, round to nearest even (host only: used when packing BVH nodes)
-inline uint16_t float_to_half_bits(float f) {
-  uint32_t x; memcpy(&x, &f, 4);
+// float -> half, round to nearest even, in integer code (not the hardware conversion): the BVH builder packs nodes with it on
+// the host and the refit kernels (refit_kernels.hpp) repack them on the device, and both must produce the same bits
+MI_HD uint16_t float_to_half_bits(float f) {
+  uint32_t x; __builtin_memcpy(&x, &f, 4);
   const uint16_t sign = (uint16_t)((x >> 16) & 0x8000u);
   x &= 0x7FFFFFFFu;
   if (x >= 0x7F800000u) return (uint16_t)(sign | 0x7C00u | (x > 0x7F800000u ? 0x200u : 0u));
@@ -99,12 +99,49 @@ inline uint16_t float_to_half_bits(float f) {
   return (uint16_t)(sign | q);
 }
 // precision_utils.hpp:39-47
-inline uint16_t half_not_smaller(float f) {
+MI_HD uint16_t half_not_smaller(float f) {
   uint16_t h = float_to_half_bits(f);
   if (half_bits_to_float(h) < f) h = (uint16_t)(h + 1);
   return h;
 }
-#endif
+
+// ---- BVH node boxes ------------------------------------------------------------------------------
+// One definition of a primitive's box, of the union of two boxes and of the compact node's encoding, for the host builder
+// (host/bvh_sah.cpp, host/scene_builtin.cpp), the host refit (mi_refit_compact_bvh) and the device refit (refit_kernels.hpp).
+// min / max are the compare / select of Bounds::grow (host/scene_types.hpp), never fminf / v_min_f32: those differ from it on
+// signed zeros and NaNs. A NaN coordinate is ignored unless every point has one (the box then stays empty: +inf / -inf).
+struct Box3 { f3 lo, hi; };
+MI_HD Box3 box_empty() { Box3 b; b.lo = mk(kInf, kInf, kInf); b.hi = mk(-kInf, -kInf, -kInf); return b; }
+MI_HD void box_grow(Box3& b, f3 p) {
+  b.lo.x = p.x < b.lo.x ? p.x : b.lo.x; b.lo.y = p.y < b.lo.y ? p.y : b.lo.y; b.lo.z = p.z < b.lo.z ? p.z : b.lo.z;
+  b.hi.x = p.x > b.hi.x ? p.x : b.hi.x; b.hi.y = p.y > b.hi.y ? p.y : b.hi.y; b.hi.z = p.z > b.hi.z ? p.z : b.hi.z;
+}
+// InnerNode::setBounds (embree_utils/node.hpp:56-70) as the builder forms it: grow(first.lo), grow(first.hi), grow(second.lo), grow(second.hi)
+MI_HD Box3 box_union(const Box3& a, const Box3& b) {
+  Box3 u = box_empty();
+  box_grow(u, a.lo); box_grow(u, a.hi); box_grow(u, b.lo); box_grow(u, b.hi);
+  return u;
+}
+MI_HD Box3 triangle_box(f3 p0, f3 p1, f3 p2) { Box3 b = box_empty(); box_grow(b, p0); box_grow(b, p1); box_grow(b, p2); return b; }
+// sphere: centre +- radius (Primitives.hpp:53-56); disc: centre +- r (Primitives.hpp:77-81)
+MI_HD Box3 ball_box(float x, float y, float z, float r) { Box3 b; b.lo = mk(x - r, y - r, z - r); b.hi = mk(x + r, y + r, z + r); return b; }
+
+// The compact node's box (CompactBVH2Node.hpp:52-85, src/CompactBvhBuild.cpp:5-32): min as binary32, extents hi - lo rounded UP
+// to binary16. Returns kBoxOk, kBoxTooLarge (an extent above 65504: the builder throws) or kBoxNotFinite (a min or an extent that
+// is not finite: mi_scene_create refuses the node); the fields are written in every case.
+enum : uint32_t { kBoxOk = 0, kBoxTooLarge = 1, kBoxNotFinite = 2 };
+constexpr float kMaxHalf = 65504.f;
+MI_HD uint32_t box_encode(const Box3& b, float& mx, float& my, float& mz, uint16_t& dx, uint16_t& dy, uint16_t& dz) {
+  mx = b.lo.x; my = b.lo.y; mz = b.lo.z;
+  const float ex = b.hi.x - b.lo.x, ey = b.hi.y - b.lo.y, ez = b.hi.z - b.lo.z;
+  dx = half_not_smaller(ex); dy = half_not_smaller(ey); dz = half_not_smaller(ez);
+  if (ex > kMaxHalf || ey > kMaxHalf || ez > kMaxHalf) return kBoxTooLarge;
+  uint32_t bx, by, bz;
+  __builtin_memcpy(&bx, &mx, 4); __builtin_memcpy(&by, &my, 4); __builtin_memcpy(&bz, &mz, 4);
+  const bool minBad = (bx & 0x7F800000u) == 0x7F800000u || (by & 0x7F800000u) == 0x7F800000u || (bz & 0x7F800000u) == 0x7F800000u;
+  const bool extBad = (dx & 0x7C00u) == 0x7C00u || (dy & 0x7C00u) == 0x7C00u || (dz & 0x7C00u) == 0x7C00u;
+  return (minBad || extBad) ? kBoxNotFinite : kBoxOk;
+}
 
 // ---- sincos: ext/math/sincos.cpp:236-355 (ACC5, ABSERR, MOD360, flg=0) ---------------------------
 // `tbl` = 92 floats, sin(i degrees); lives in LDS on the device, static storage on the host.

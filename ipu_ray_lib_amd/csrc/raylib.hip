@@ -17,6 +17,7 @@
 #include "trace_kernels.hpp"
 #include "trace_wavefront.hpp"
 #include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
+#include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 // MI_RAYLIB_VARIANTS=1 (libmi_raylib_variants.so, the test build): the kernel families that were built, measured and not
 // made the default - LDS-staged nodes (kernel 2), the path pool (kernel 3), the speculative walk (spec), the 4-wave and
 // the runtime-weights instantiations (waves, tune), the register-resident MLP kernel K3r (nif_shape r8 / r8s) - stay
@@ -137,6 +138,7 @@ struct SceneOptions {
                                    // in a NODE turn. Measured neutral (config 5: NODE turns 11.0 -> 3.4 per 64 casts, SHADE turns 1.2 -> 2.1 at lower occupancy, frame +-0.05 %,
                                    // profiles/r05_config5_launch_ab.txt): off by default, kept for A/B; results are the same either way
   bool nifTiming = false;          // "nif_timing": HIP events round every MLP launch of a NIF render (mi_get_nif_timing)
+  bool refitTiming = false;        // "refit_timing": HIP events round the passes of mi_scene_update* (mi_get_refit_timing)
   uint32_t nifGenerations = kNifGenerations;   // MI_RAYLIB_NIF_GENERATIONS / "nif_generations": MLP workgroups launched per resident slot (nif_launch_mlp; measurement knob)
   bool rootStart = true;           // MI_RAYLIB_NO_ROOT_START / "root_start": a cast whose origin lies strictly inside the root's box starts at node 1
   bool sayGrid = false;            // MI_RAYLIB_SAY_GRID / "say_grid": print every persistent launch's grid to stderr (what the runtime said stays resident)
@@ -212,6 +214,7 @@ struct SceneOptions {
     if (key == "nif_spl") { if (!number(v, 0, kNifSplMax, q)) return false; nifSamplesPerLaunch = (uint32_t)q; return true; }
     if (key == "pin") return flag01(v, pin);
     if (key == "nif_timing") return flag01(v, nifTiming);
+    if (key == "refit_timing") return flag01(v, refitTiming);
     if (key == "nif_generations") { if (!number(v, 1, 4096, q)) return false; nifGenerations = (uint32_t)q; return true; }
     if (key == "root_start") return flag01(v, rootStart);
     if (key == "say_grid") return flag01(v, sayGrid);
@@ -358,6 +361,25 @@ struct mi_scene {
   uint32_t scratchAsked = 0;                                  // the MI_RAYLIB_NIF_SPL value they were sized under (0 = default)
   bool scratchOneSet = false;                                 // two slot sets did not fit the memory budget: this render runs without the overlap
   std::vector<std::pair<hipEvent_t, hipEvent_t>> nifTimes;    // option "nif_timing": events round the MLP launches since the last mi_get_nif_timing
+  // mi_scene_update: what a refit needs, kept on the HOST at create (the device holds only records derived from it), and the
+  // device tables the first update builds (refitTables; a scene that is never updated allocates nothing for them)
+  struct Refit {
+    std::vector<mi_bvh_node> nodes;                           // the compact nodes at create: the topology, and mi_scene_get_bvh before an update
+    std::vector<mi_geom_ref> geometry; std::vector<mi_mesh_info> meshInfo; std::vector<uint16_t> tris;
+    std::vector<mi_vec3> verts; std::vector<mi_sphere> spheres; std::vector<mi_disc> discs;   // the geometry at create (-> d_verts ... at the first update)
+    uint32_t numVerts = 0, numNormals = 0, numSpheres = 0, numDiscs = 0;
+    bool ready = false;
+    RefitPrim* d_prims = nullptr;                             // [node]: what its box is computed from
+    uint32_t* d_order = nullptr;                              // node indices by height (leaves first)
+    std::vector<uint32_t> levelStart; uint32_t* d_levelStart = nullptr;   // [height]: first entry of that height in d_order; [H + 1] = numNodes
+    uint32_t topFirst = 0;                                    // heights topFirst .. H run in one workgroup (refit_top_kernel)
+    RefitBox* d_boxes = nullptr;                              // float boxes (scratch)
+    mi_bvh_node* d_cnodes[2] = {nullptr, nullptr}; int live = -1;   // compact nodes: the scene's current ones (live; -1 = nodes[]) and the scratch
+    uint32_t* d_err = nullptr;                                // pass 1 / 2 error bits (1 << kBoxTooLarge, 1 << kBoxNotFinite)
+    mi_vec3* d_verts = nullptr; mi_sphere* d_spheres = nullptr; mi_disc* d_discs = nullptr;   // the current geometry
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // option "refit_timing": round passes 1, 2 and 4
+    double ms[3] = {0, 0, 0};                                 // the last update's {leaf, interior, write} pass times
+  } refit;
 
   ~mi_scene() {
     (void)hipSetDevice(device);
@@ -382,6 +404,7 @@ struct mi_scene {
     for (int i = 0; i < 2; ++i) { if (d_batch[i]) (void)hipFree(d_batch[i]); if (pipeStream[i]) (void)hipStreamDestroy(pipeStream[i]); }
     if (nifDone) (void)hipEventDestroy(nifDone);
     for (auto& e : nifTimes) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
+    for (hipEvent_t e : refit.ev) if (e) (void)hipEventDestroy(e);
     nif.release();
   }
   void freeNifSlots() {
@@ -572,6 +595,157 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
   S.keep(S.d_counters);
   HIP_CHECK(hipMemset(S.d_counters, 0, 32 * sizeof(unsigned long long)));
   ds.counters = S.d_counters;
+
+  // what a later mi_scene_update needs, on the host: the topology and the geometry as created (validated above)
+  mi_scene::Refit& R = S.refit;
+  R.nodes.assign(d.bvh_nodes, d.bvh_nodes + N);
+  R.geometry.assign(d.geometry, d.geometry + d.num_geometry);
+  R.meshInfo.assign(d.mesh_info, d.mesh_info + d.num_meshes);
+  R.tris.assign(d.mesh_tris, d.mesh_tris + (d.num_meshes ? 3 * (size_t)d.num_tris : 0));
+  R.verts.assign(d.mesh_verts, d.mesh_verts + (d.num_meshes ? d.num_verts : 0));
+  R.spheres.assign(d.spheres, d.spheres + d.num_spheres);
+  R.discs.assign(d.discs, d.discs + d.num_discs);
+  R.numVerts = d.num_meshes ? d.num_verts : 0; R.numNormals = d.num_normals; R.numSpheres = d.num_spheres; R.numDiscs = d.num_discs;
+}
+
+// ---- geometry updates (mi_scene_update*, refit_kernels.hpp) -------------------------------------------------------------------
+// The refit's device tables, built on the first update from what buildDeviceScene kept: per node what its box is computed from,
+// the nodes bucketed by height (leaf 0, interior 1 + the higher child), scratch for the float boxes, two compact arrays (the
+// current one and the one a refit writes), and the current geometry.
+void refitTables(mi_scene& S) {
+  mi_scene::Refit& R = S.refit;
+  if (R.ready) return;
+  const uint32_t N = (uint32_t)R.nodes.size();
+  std::vector<RefitPrim> prims(N);
+  std::vector<uint32_t> height(N, 0);
+  for (uint32_t i = N; i-- > 0;) {
+    const mi_bvh_node& n = R.nodes[i];
+    RefitPrim p{0u, 0u, 0u, REFIT_INTERIOR};
+    if (n.geom_id == MI_INVALID_GEOM) {
+      p.a = n.prim_or_second_child;
+      height[i] = 1 + std::max(height[i + 1], height[p.a]);
+    } else {
+      const mi_geom_ref& r = R.geometry[n.geom_id];
+      if (r.type == 0) {
+        const mi_mesh_info& m = R.meshInfo[r.index];
+        const size_t base = 3 * ((size_t)m.first_index + n.prim_or_second_child);
+        p = {m.first_vertex + R.tris[base], m.first_vertex + R.tris[base + 1], m.first_vertex + R.tris[base + 2], REFIT_TRI};
+      } else {
+        p = {r.index, 0u, 0u, r.type == 1 ? (uint32_t)REFIT_SPHERE : (uint32_t)REFIT_DISC};
+      }
+    }
+    prims[i] = p;
+  }
+  const uint32_t H = N ? height[0] : 0;
+  R.levelStart.assign(H + 2, 0);
+  for (uint32_t i = 0; i < N; ++i) ++R.levelStart[height[i] + 1];
+  for (uint32_t h = 0; h <= H; ++h) R.levelStart[h + 1] += R.levelStart[h];
+  std::vector<uint32_t> order(N), at(R.levelStart.begin(), R.levelStart.end() - 1);
+  for (uint32_t i = 0; i < N; ++i) order[at[height[i]]++] = i;
+  // the top levels that fit one workgroup's threads go to refit_top_kernel: one launch for them, not one per level
+  R.topFirst = H + 1;
+  while (R.topFirst > 1 && R.levelStart[R.topFirst] - R.levelStart[R.topFirst - 1] <= kRefitTopThreads) --R.topFirst;
+  R.d_prims = S.keep(upload(prims));
+  R.d_order = S.keep(upload(order));
+  R.d_levelStart = S.keep(upload(R.levelStart));
+  R.d_cnodes[0] = S.keep(upload(R.nodes));
+  R.d_cnodes[1] = S.keep(upload(R.nodes));
+  if (N) HIP_CHECK(hipMalloc(&R.d_boxes, (size_t)N * sizeof(RefitBox)));
+  S.keep(R.d_boxes);
+  HIP_CHECK(hipMalloc(&R.d_err, sizeof(uint32_t)));
+  S.keep(R.d_err);
+  R.d_verts = S.keep(upload(R.verts));
+  R.d_spheres = S.keep(upload(R.spheres));
+  R.d_discs = S.keep(upload(R.discs));
+  // (the device copies are the current geometry from now on)
+  R.verts = {}; R.spheres = {}; R.discs = {};
+  R.ready = true;
+}
+
+// Argument rules of the two update entries: the first three touch neither the scene nor a device.
+void updateArgs(const char* fn, const mi_scene* S, const mi_geometry_update* u) {
+  auto bad = [&](const char* why) { throw ArgError(std::string(fn) + ": " + why); };
+  if (!S) bad("null scene");
+  if (!u) bad("null update");
+  if ((!u->mesh_verts && u->num_verts) || (!u->mesh_normals && u->num_normals) || (!u->spheres && u->num_spheres) || (!u->discs && u->num_discs))
+    bad("a count without its array");
+  const mi_scene::Refit& R = S->refit;
+  if (u->mesh_verts && u->num_verts != R.numVerts) bad("num_verts differs from the scene's vertex count");
+  if (u->mesh_normals && R.numNormals == 0) bad("normals given to a scene created without normals");
+  if (u->mesh_normals && u->num_normals != R.numNormals) bad("num_normals differs from the scene's normal count");
+  if (u->spheres && u->num_spheres != R.numSpheres) bad("num_spheres differs from the scene's sphere count");
+  if (u->discs && u->num_discs != R.numDiscs) bad("num_discs differs from the scene's disc count");
+}
+
+// The update proper, on DEVICE arrays (NULL = keep), on `stream`: passes 1 - 3 (scratch only, then the read-back that decides),
+// then - behind everything already enqueued on the scene - pass 4 and the copies into the current geometry. Returns when it is
+// all in place; on a refused box nothing of the scene has changed.
+void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
+  refitTables(S);
+  mi_scene::Refit& R = S.refit;
+  DeviceScene& ds = S.ds;
+  const uint32_t N = ds.numNodes;
+  RefitGeom g;
+  g.verts = u.mesh_verts ? (const mi_vec3*)u.mesh_verts : R.d_verts;
+  g.spheres = u.spheres ? u.spheres : R.d_spheres;
+  g.discs = u.discs ? u.discs : R.d_discs;
+  g.normals = u.mesh_normals;
+  const int scratch = R.live == 0 ? 1 : 0;
+  mi_bvh_node* cn = R.d_cnodes[scratch];
+  mi_bvh_node root{};
+  const bool timing = S.opt.refitTiming && N;
+  if (timing && !R.ev[0]) for (hipEvent_t& e : R.ev) HIP_CHECK(hipEventCreate(&e));
+  if (N) {
+    HIP_CHECK(hipMemsetAsync(R.d_err, 0, sizeof(uint32_t), stream));
+    const uint32_t leaves = R.levelStart[1];
+    if (timing) HIP_CHECK(hipEventRecord(R.ev[0], stream));
+    hipLaunchKernelGGL(refit_leaf_kernel, dim3((leaves + 255) / 256), dim3(256), 0, stream, R.d_order, leaves, R.d_prims, g, R.d_boxes, cn, R.d_err);
+    if (timing) HIP_CHECK(hipEventRecord(R.ev[1], stream));
+    for (uint32_t h = 1; h < R.topFirst; ++h) {
+      const uint32_t cnt = R.levelStart[h + 1] - R.levelStart[h];
+      hipLaunchKernelGGL(refit_level_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream, R.d_order, R.levelStart[h], cnt, R.d_prims, R.d_boxes, cn, R.d_err);
+    }
+    const uint32_t H = (uint32_t)R.levelStart.size() - 2;
+    if (R.topFirst <= H)
+      hipLaunchKernelGGL(refit_top_kernel, dim3(1), dim3(kRefitTopThreads), 0, stream, R.d_order, R.d_levelStart, R.topFirst, H, R.d_prims, R.d_boxes, cn, R.d_err);
+    HIP_CHECK(hipGetLastError());
+    if (timing) HIP_CHECK(hipEventRecord(R.ev[2], stream));
+    uint32_t err = 0;
+    HIP_CHECK(hipMemcpyAsync(&err, R.d_err, sizeof err, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(&root, cn, sizeof root, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (timing) {
+      float a = 0.f, b = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&a, R.ev[0], R.ev[1])); HIP_CHECK(hipEventElapsedTime(&b, R.ev[1], R.ev[2]));
+      R.ms[0] = a; R.ms[1] = b;
+    }
+    // (an empty leaf box - every point NaN on an axis - also makes its parent's extent infinite: the leaf is named first)
+    if (err & (1u << kBoxNotFinite)) throw ArgError("mi_scene_update: a node box is not finite; the scene is unchanged");
+    if (err) throw ArgError("mi_scene_update: a node extent is above 65504 (Cannot compress BVH bounds into fp16 (half)); the scene is unchanged");
+  }
+  // from here on the scene changes: after everything already enqueued on it, on any stream
+  for (LaunchSlot& l : S.slots) if (l.stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, l.lastWork, 0));
+  if (N) {
+    if (timing) HIP_CHECK(hipEventRecord(R.ev[3], stream));
+    hipLaunchKernelGGL(refit_write_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, N, R.d_prims, cn, g, const_cast<GNode*>(ds.nodes),
+                       const_cast<GLeaf*>(ds.leaves), const_cast<GLeafRot*>(ds.leavesRot), const_cast<float*>(ds.leafNormals));
+    HIP_CHECK(hipGetLastError());
+  }
+  if (u.mesh_verts && R.numVerts) HIP_CHECK(hipMemcpyAsync(R.d_verts, u.mesh_verts, (size_t)R.numVerts * sizeof(mi_vec3), hipMemcpyDeviceToDevice, stream));
+  if (u.spheres && R.numSpheres) HIP_CHECK(hipMemcpyAsync(R.d_spheres, u.spheres, (size_t)R.numSpheres * sizeof(mi_sphere), hipMemcpyDeviceToDevice, stream));
+  if (u.discs && R.numDiscs) HIP_CHECK(hipMemcpyAsync(R.d_discs, u.discs, (size_t)R.numDiscs * sizeof(mi_disc), hipMemcpyDeviceToDevice, stream));
+  if (u.mesh_normals && ds.meshNormals)
+    HIP_CHECK(hipMemcpyAsync(const_cast<mi_vec3*>(ds.meshNormals), u.mesh_normals, (size_t)R.numNormals * sizeof(mi_vec3), hipMemcpyDeviceToDevice, stream));
+  if (timing) HIP_CHECK(hipEventRecord(R.ev[1], stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (timing) { float w = 0.f; HIP_CHECK(hipEventElapsedTime(&w, R.ev[3], R.ev[1])); R.ms[2] = w; }
+  if (!N) return;
+  R.live = scratch;
+  if (N > 1) {      // the root's box as buildDeviceScene sets it (root_start)
+    ds.rootLoX = root.min_x; ds.rootHiX = root.min_x + half_bits_to_float(root.dx);
+    ds.rootLoY = root.min_y; ds.rootHiY = root.min_y + half_bits_to_float(root.dy);
+    ds.rootLoZ = root.min_z; ds.rootHiZ = root.min_z + half_bits_to_float(root.dz);
+  }
 }
 
 // Slots per pixel per launch in NIF renders: 48 B each (u, v, bgr, colour, throughput, list entry), and TWO sets of them when
@@ -1083,6 +1257,63 @@ int mi_scene_create_from_blob(const uint8_t* blob, size_t size, const mi_scene_d
 }
 
 void mi_scene_destroy(mi_scene* scene) { delete scene; }
+
+int mi_scene_update_device(mi_scene* scene, const mi_geometry_update* device_arrays, void* hip_stream) {
+  return guarded([&] {
+    updateArgs("mi_scene_update_device", scene, device_arrays);
+    HIP_CHECK(hipSetDevice(scene->device));
+    refitScene(*scene, *device_arrays, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_scene_update(mi_scene* scene, const mi_geometry_update* host_arrays) {
+  std::vector<void*> staged;
+  const int rc = guarded([&] {
+    updateArgs("mi_scene_update", scene, host_arrays);
+    HIP_CHECK(hipSetDevice(scene->device));
+    // the given arrays to the device, then the device entry's work on the null stream
+    auto stage = [&](const void* p, size_t bytes) -> const void* {
+      if (!p || !bytes) return p;
+      void* d = nullptr;
+      HIP_CHECK(hipMalloc(&d, bytes));
+      staged.push_back(d);
+      HIP_CHECK(hipMemcpy(d, p, bytes, hipMemcpyHostToDevice));
+      return d;
+    };
+    mi_geometry_update u = *host_arrays;
+    u.mesh_verts = (const mi_vec3*)stage(u.mesh_verts, (size_t)u.num_verts * sizeof(mi_vec3));
+    u.mesh_normals = (const mi_vec3*)stage(u.mesh_normals, (size_t)u.num_normals * sizeof(mi_vec3));
+    u.spheres = (const mi_sphere*)stage(u.spheres, (size_t)u.num_spheres * sizeof(mi_sphere));
+    u.discs = (const mi_disc*)stage(u.discs, (size_t)u.num_discs * sizeof(mi_disc));
+    refitScene(*scene, u, nullptr);
+  });
+  for (void* d : staged) (void)hipFree(d);
+  return rc;
+}
+
+int mi_get_refit_timing(mi_scene* scene, double out[3]) {
+  if (!scene || !out) { g_err = "mi_get_refit_timing: null argument"; return MI_ERR_INVALID_ARG; }
+  for (int i = 0; i < 3; ++i) out[i] = scene->refit.ms[i];
+  g_err.clear();
+  return MI_OK;
+}
+
+int mi_scene_get_bvh(mi_scene* scene, mi_bvh_node* out, uint32_t capacity, uint32_t* num_nodes) {
+  if (!scene || !num_nodes) { g_err = "mi_scene_get_bvh: null argument"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    const mi_scene::Refit& R = scene->refit;
+    const uint32_t N = (uint32_t)R.nodes.size();
+    *num_nodes = N;
+    if (!out) return;
+    if (capacity < N) throw ArgError("mi_scene_get_bvh: capacity is smaller than the scene's node count");
+    if (R.live >= 0) {
+      HIP_CHECK(hipSetDevice(scene->device));
+      HIP_CHECK(hipMemcpy(out, R.d_cnodes[R.live], (size_t)N * sizeof(mi_bvh_node), hipMemcpyDeviceToHost));
+    } else if (N) {
+      memcpy(out, R.nodes.data(), (size_t)N * sizeof(mi_bvh_node));
+    }
+  });
+}
 
 int mi_render_device(mi_scene* scene, int mode, void* d_rays, size_t n, void* hip_stream) {
   if (!scene || (!d_rays && n)) { g_err = "mi_render_device: null argument"; return MI_ERR_INVALID_ARG; }
