@@ -105,9 +105,9 @@ def _render(sc, desc, mode):
     return rays
 
 
-def _check_renders(dev, fresh, desc, what, kernels=(0, 1), oracle=True):
+def _check_renders(dev, fresh, desc, what, kernels=(0, 1), oracle=True, frame=(64, 64, 16)):
     """Path-trace and shadow-trace frames of dev equal fresh's (and the oracle's) bit for bit."""
-    d = _frame(desc)
+    d = _frame(desc, *frame)
     for k in kernels:
         dev.set_option("kernel", k); fresh.set_option("kernel", k)
         a, b = _render(dev, d, irl.MODE_PATH_TRACE), _render(fresh, d, irl.MODE_PATH_TRACE)
