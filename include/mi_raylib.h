@@ -190,7 +190,7 @@ int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n)
  * must come with count 0). mesh_normals only for scenes created with normals.
  * Result. The nodes are those mi_refit_compact_bvh (mi_scene_host.h) computes from the moved arrays, byte for byte, and every render
  * and query afterwards equals that of a scene freshly created from the moved arrays and those nodes, bit for bit. A refit keeps the
- * old topology, so under large motion boxes overlap more and traces slow down; a rebuild is a new mi_scene_create.
+ * old topology, so under large motion boxes overlap more and traces slow down; mi_scene_rebuild (below) gives the scene a new one.
  * Ordering. The update waits for all work already enqueued on the scene, on any stream (renders and queries), before it overwrites a
  * device record: a render or query enqueued before the update sees the old geometry, whatever its stream.
  * Synchronous return. The update returns once the new geometry is in place; work enqueued after it returns sees it. It reads back
@@ -216,6 +216,36 @@ int mi_scene_get_bvh(mi_scene* scene, mi_bvh_node* out, uint32_t capacity, uint3
 /* Measurement only (tools/bench_refit.py): the last update's pass times in milliseconds from HIP events on its stream,
  * out = {leaf boxes, interior boxes, record rewrite and copies}; zeros unless scene option "refit_timing" is 1. */
 int mi_get_refit_timing(mi_scene* scene, double out[3]);
+
+/* Rebuild the BVH topology of a live scene from its CURRENT geometry, on the device (Embree's RTC_BUILD_QUALITY_LOW rebuild next
+ * to its refit, OptiX's BUILD next to UPDATE): a linear BVH - Morton keys of the primitive centroids, a radix sort, Karras' 2012
+ * hierarchy - over the primitives in canonical order (geometry 0 .. G - 1, inside a mesh triangle 0 .. T - 1). The node count
+ * stays 2 P - 1 (one primitive per leaf); everything attached to the scene stays: NIF weights, options, counters, launch slots.
+ * Result. The nodes are those mi_build_lbvh_compact (mi_scene_host.h) computes from the scene's current arrays, byte for byte,
+ * whatever topology or history the scene had (rebuilding twice is the identity); *max_leaf_depth (may be NULL) is the twin's depth;
+ * every render and query afterwards equals that of a scene freshly created from the current arrays and those nodes, bit for bit.
+ * An LBVH costs more box tests per cast than the host builder's tree: the rebuild is for a scene whose refitted
+ * tree has degraded, not a better tree for a static one.
+ * Ordering. The rebuild waits for all work already enqueued on the scene, on any stream (renders and queries), before it overwrites
+ * a device record: a render or query enqueued before the rebuild sees the old tree, whatever its stream.
+ * Synchronous return. The rebuild returns once the new tree is in place; work enqueued after it returns sees it. It reads back two
+ * small records (where the tree's depths start; the refusal flag and the root box). Its kernels run on hip_stream (a hipStream_t as
+ * void*; NULL = the null stream), and it waits for that stream only.
+ * Refusal. MI_ERR_INVALID_ARG leaves the scene unchanged - every record, node and later result: a null scene, a scene whose BVH does
+ * not hold every primitive in exactly one leaf, a resulting node box that is not finite, an extent above 65504 - exactly when
+ * mi_scene_create from the current arrays and the twin's nodes would fail. (Geometry that came in through mi_scene_update* has
+ * passed the same checks; a scene created with nodes that do not bound its geometry can be refused.)
+ * A scene of 0 nodes is a no-op (depth 0), one primitive keeps its single leaf root (depth 1). Counters, options and the NIF
+ * environment are untouched; a scene made by mi_scene_create_from_blob rebuilds the same way. mi_scene_get_bvh returns the rebuilt
+ * nodes. The first rebuild builds the canonical primitive table and the passes' scratch (about 110 bytes per primitive, plus the
+ * update's tables); a scene never rebuilt allocates nothing for them. The refit's tables of the new topology are not built by the
+ * rebuild: the first mi_scene_update* after a rebuild reads the compact nodes back once and derives them on the host, as the first
+ * update of a scene does. */
+int mi_scene_rebuild(mi_scene* scene, void* hip_stream, uint32_t* max_leaf_depth /* may be NULL */);
+/* Measurement only (tools/bench_rebuild.py): the last rebuild's pass times in milliseconds from HIP events on its stream, out =
+ * {primitive boxes + scene box + keys, key sort, hierarchy + depths + depth sort (with the first read-back), level boxes,
+ * preorder indices, scatter + copies}; zeros unless scene option "rebuild_timing" is 1. */
+int mi_get_rebuild_timing(mi_scene* scene, double out[6]);
 
 /* Replaces: IpuScene::getTraceTimeSecs (IpuScene.hpp:55). Wall time of the last mi_render. */
 double mi_trace_time_secs(const mi_scene* scene);
@@ -316,6 +346,7 @@ int mi_scene_set_ray_batch(mi_scene* scene, size_t rays_per_batch);
  *                                   (0 = all that stay resident, the default)
  *   "nif_timing"    0 | 1           bracket every MLP launch of a NIF render with HIP events (mi_get_nif_timing)
  *   "refit_timing"  0 | 1           bracket the passes of mi_scene_update* with HIP events (mi_get_refit_timing)
+ *   "rebuild_timing" 0 | 1          bracket the passes of mi_scene_rebuild with HIP events (mi_get_rebuild_timing)
  *   "leaf_rot"      0 | 1           scenes without vertex normals: the default kernel reads primitive records pre-rotated for the cast's shear axis (default 1)
  *   "lean_hit"      0 | 1           scenes without vertex normals run the build of the default kernel that carries no barycentrics (default 1)
  *   "coords"        0 | 1           (pixel, segment) work units read the pixel's (u, v) from a compact copy of the stream gathered once
@@ -359,7 +390,8 @@ int mi_nif_infer_device(mi_scene* scene, const float* d_u, const float* d_v, flo
  * copies only. RCCL is loaded with dlopen when the first group needs it.
  * mi_group_scene hands out a replica's scene for the per-scene setters (mi_scene_set_nif, mi_scene_set_option, ...),
  * which must be applied to every replica alike. The same holds for geometry updates: mi_scene_update / mi_scene_update_device on
- * every replica's scene, with the same arrays (there is no group-level update entry). */
+ * every replica's scene, with the same arrays (there is no group-level update entry), and for mi_scene_rebuild: call it on every
+ * replica's scene (the result is a function of the geometry alone, so the replicas stay alike). */
 typedef struct mi_group mi_group;
 int mi_group_create(const mi_scene_desc* desc, const int32_t* devices, uint32_t num_replicas, int32_t transport, mi_group** out);
 void mi_group_destroy(mi_group* group);

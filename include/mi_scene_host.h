@@ -60,6 +60,19 @@ int mi_build_compact_bvh(const float* lower, const float* upper, const uint16_t*
  * (mi_scene_update, mi_raylib.h) is checked against, and the way to build the fresh scene an updated one must equal. */
 int mi_refit_compact_bvh(const mi_scene_desc* desc, mi_bvh_node* out);
 
+/* Rebuild: a linear BVH (LBVH) over desc's primitives from desc's geometry arrays; desc's own bvh_nodes are ignored. The primitives
+ * are taken in canonical order - geometry 0 .. num_geometry - 1, inside a mesh triangle 0 .. T - 1 -, keyed by the 63-bit Morton code
+ * of their box centroid (lo + hi) * .5f quantised to 21 bits per axis inside the scene box, sorted by (key, canonical index), hung
+ * into Karras' 2012 hierarchy (equal keys split by sorted position: coincident primitives give a balanced subtree), boxed bottom-up
+ * as mi_refit_compact_bvh boxes them, each pair of children ordered by the builder's rule (box centre nearer the origin first, the
+ * lower-key child on a tie) and laid out depth-first. `out` must hold 2 P - 1 nodes for P primitives (what the scene's own BVH
+ * holds); *num_nodes = 2 P - 1 (0 for an empty scene) and *max_leaf_depth = the deepest leaf with the root at 1, at most
+ * 63 + 32 + 1. Fails as mi_refit_compact_bvh fails, with the same messages: "Cannot compress BVH bounds into fp16 (half)"
+ * (MI_ERR_IO) on an extent above 65504, MI_ERR_INVALID_ARG on a node box that is not finite or an index out of range. The twin
+ * of the device rebuild (mi_scene_rebuild, mi_raylib.h), whose nodes equal these byte for byte, and the way to build the fresh
+ * scene a rebuilt one must equal. */
+int mi_build_lbvh_compact(const mi_scene_desc* desc, mi_bvh_node* out, uint32_t* num_nodes, uint32_t* max_leaf_depth);
+
 /* initPerspectiveRayStream(rayStream, image, data, nullptr) + zeroRgb: window_w*window_h rays in
  * row-major window order, origin 0, un-jittered pinhole directions, u=row, v=col. */
 int mi_init_ray_stream(const mi_scene_desc* desc, mi_trace_result* rays, size_t capacity);

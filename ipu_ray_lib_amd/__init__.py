@@ -139,6 +139,7 @@ def host_lib() -> C.CDLL:
         lib.mi_build_compact_bvh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                              C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.mi_refit_compact_bvh.argtypes = [C.POINTER(SceneDesc), C.c_void_p]
+        lib.mi_build_lbvh_compact.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.mi_init_ray_stream.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_size_t]
         lib.mi_scale_rgb.argtypes = [C.c_void_p, C.c_size_t, C.c_float]
         lib.mi_scale_rgb.restype = None
@@ -204,6 +205,8 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         lib.mi_scene_update.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate)]
         lib.mi_scene_update_device.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_void_p]
+        lib.mi_scene_rebuild.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.mi_get_rebuild_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.mi_scene_get_bvh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.mi_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
@@ -354,6 +357,18 @@ def refit_compact_bvh(desc: SceneDesc) -> np.ndarray:
     out = np.zeros(desc.num_nodes, dtype=BVH_NODE)
     _check_host(host_lib().mi_refit_compact_bvh(C.byref(desc), out.ctypes.data))
     return out
+
+
+def build_lbvh(desc: SceneDesc):
+    """mi_build_lbvh_compact: (nodes, max leaf depth) of the LBVH over desc's primitives, from desc's geometry arrays (desc's own
+    nodes are ignored). The host twin of IpuScene.rebuild_bvh; raises RaylibError where mi_scene_rebuild refuses."""
+    geometry = HostScene._view(None, desc.geometry, desc.num_geometry, GEOM_REF)
+    info = HostScene._view(None, desc.mesh_info, desc.num_meshes, MESH_INFO)
+    prims = sum(int(info[g["index"]]["numTriangles"]) if g["type"] == 0 and g["index"] < info.size else 1 for g in geometry)
+    out = np.zeros(max(2 * prims - 1, 1), dtype=BVH_NODE)
+    n, depth = C.c_uint32(), C.c_uint32()
+    _check_host(host_lib().mi_build_lbvh_compact(C.byref(desc), out.ctypes.data, C.byref(n), C.byref(depth)))
+    return out[:n.value].copy(), depth.value
 
 
 def _geometry_array(a, dtype, width):
@@ -588,6 +603,24 @@ class IpuScene:
         stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None else 0
         self._check(self._lib.mi_scene_update_device(self._h, C.byref(u), C.c_void_p(stream)))
         return self
+
+    def rebuild_bvh(self, stream=None) -> int:
+        """mi_scene_rebuild: a new BVH topology from the scene's current geometry, built on the device (an LBVH; build_lbvh is its
+        host twin). `stream`: a raw hipStream_t as an int, default torch.cuda.current_stream() when torch is loaded, else the
+        null stream. Synchronous. Returns the maximal leaf depth (root = 1)."""
+        if stream is None:
+            import sys
+            torch = sys.modules.get("torch")
+            stream = torch.cuda.current_stream().cuda_stream if torch is not None and torch.cuda.is_available() else 0
+        depth = C.c_uint32()
+        self._check(self._lib.mi_scene_rebuild(self._h, C.c_void_p(stream), C.byref(depth)))
+        return depth.value
+
+    def rebuild_timing(self) -> list:
+        """mi_get_rebuild_timing: the last rebuild's pass times in ms (zeros unless option "rebuild_timing" is 1)."""
+        out = (C.c_double * 6)()
+        self._check(self._lib.mi_get_rebuild_timing(self._h, out))
+        return list(out)
 
     def bvh_nodes(self) -> np.ndarray:
         """The scene's current compact BVH nodes (mi_scene_get_bvh): a BVH_NODE array."""

@@ -145,6 +145,18 @@ int mi_refit_compact_bvh(const mi_scene_desc* desc, mi_bvh_node* out) {
   return guarded([&] { refitCompactBvh(*desc, out); });
 }
 
+int mi_build_lbvh_compact(const mi_scene_desc* desc, mi_bvh_node* out, uint32_t* num_nodes, uint32_t* max_leaf_depth) {
+  if (!desc || !out || !num_nodes || !max_leaf_depth) { g_err = "mi_build_lbvh_compact: null argument"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    std::vector<mi_bvh_node> nodes;
+    uint32_t depth = 0;
+    buildLbvhCompact(*desc, nodes, depth);
+    if (!nodes.empty()) memcpy(out, nodes.data(), nodes.size() * sizeof(mi_bvh_node));
+    *num_nodes = (uint32_t)nodes.size();
+    *max_leaf_depth = depth;
+  });
+}
+
 // initPerspectiveRayStream with gen == nullptr, then zeroRgb (src/app_utils.cpp:19-53)
 int mi_init_ray_stream(const mi_scene_desc* d, mi_trace_result* rays, size_t capacity) {
   if (!d || !rays) { g_err = "null argument"; return MI_ERR_INVALID_ARG; }

@@ -97,6 +97,8 @@ struct BuildPrim { Bounds box; uint16_t geomID; uint32_t primID; };
 // bvh_sah.cpp
 void buildCompactBvh(const std::vector<BuildPrim>& prims, std::vector<mi_bvh_node>& nodes, uint32_t& maxDepth);
 void refitCompactBvh(const mi_scene_desc& desc, mi_bvh_node* out);
+// lbvh.cpp: the host twin of mi_scene_rebuild
+void buildLbvhCompact(const mi_scene_desc& desc, std::vector<mi_bvh_node>& nodes, uint32_t& maxDepth);
 
 // glb_reader.cpp: meshes of a glTF-binary file with node transforms baked in, file order kept
 std::vector<TriMesh> loadGlbMeshes(const std::string& path, bool loadNormals);

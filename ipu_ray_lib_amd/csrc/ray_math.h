@@ -143,6 +143,94 @@ MI_HD uint32_t box_encode(const Box3& b, float& mx, float& my, float& mz, uint16
   return (minBad || extBad) ? kBoxNotFinite : kBoxOk;
 }
 
+// ---- LBVH: Morton keys and Karras' hierarchy -------------------------------------------------------------------------------
+// One definition for the host twin (host/lbvh.cpp, mi_build_lbvh_compact) and the device rebuild (rebuild_kernels.hpp,
+// mi_scene_rebuild): both must produce the same tree. Every float step is one rounded binary32 (or binary64) operation.
+//
+// A centroid component quantised to 21 bits inside the scene box [lo, lo + ext]: the correctly rounded quotient (c - lo) / ext,
+// scaled by 2^21 (exact), truncated, clamped to [0, 2^21 - 1]. An axis of zero (or not positive, or NaN) extent maps to 0, and so
+// does a quotient that is negative or NaN.
+constexpr uint32_t kMortonBits = 21;
+MI_HD uint32_t lbvh_quantise(float c, float lo, float ext) {
+  if (!(ext > 0.f)) return 0u;
+  const float t = (c - lo) / ext;
+  const float s = t * 2097152.f;
+  if (!(s >= 0.f)) return 0u;
+  if (s >= 2097151.f) return 2097151u;
+  return (uint32_t)s;
+}
+// bit i of v -> bit 3 i
+MI_HD uint64_t morton_spread21(uint32_t v) {
+  uint64_t x = v & 0x1FFFFFu;
+  x = (x | (x << 32)) & 0x001F00000000FFFFull;
+  x = (x | (x << 16)) & 0x001F0000FF0000FFull;
+  x = (x | (x << 8)) & 0x100F00F00F00F00Full;
+  x = (x | (x << 4)) & 0x10C30C30C30C30C3ull;
+  x = (x | (x << 2)) & 0x1249249249249249ull;
+  return x;
+}
+// The 63-bit key of a primitive box inside the scene box: x in the highest bit of every triple.
+MI_HD uint64_t lbvh_key(const Box3& prim, const Box3& scene) {
+  const f3 c = (prim.lo + prim.hi) * .5f;
+  const f3 ext = scene.hi - scene.lo;
+  return (morton_spread21(lbvh_quantise(c.x, scene.lo.x, ext.x)) << 2) | (morton_spread21(lbvh_quantise(c.y, scene.lo.y, ext.y)) << 1) |
+         morton_spread21(lbvh_quantise(c.z, scene.lo.z, ext.z));
+}
+// The scene box's accumulation: lo against lo, hi against hi (compare / select), so that an empty box (+inf / -inf) is neutral - a
+// reduction pads with empty boxes, and box_grow with an empty box's corners as points would not be.
+MI_HD Box3 box_merge(Box3 a, const Box3& b) {
+  a.lo.x = b.lo.x < a.lo.x ? b.lo.x : a.lo.x; a.lo.y = b.lo.y < a.lo.y ? b.lo.y : a.lo.y; a.lo.z = b.lo.z < a.lo.z ? b.lo.z : a.lo.z;
+  a.hi.x = b.hi.x > a.hi.x ? b.hi.x : a.hi.x; a.hi.y = b.hi.y > a.hi.y ? b.hi.y : a.hi.y; a.hi.z = b.hi.z > a.hi.z ? b.hi.z : a.hi.z;
+  return a;
+}
+// The scene box without signed zeros (x + 0 = +0 for either zero): a reduction may meet the zeros in any order.
+MI_HD Box3 lbvh_scene_box(Box3 b) {
+  b.lo = b.lo + mk(0.f, 0.f, 0.f); b.hi = b.hi + mk(0.f, 0.f, 0.f);
+  return b;
+}
+MI_HD int lbvh_clz64(uint64_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __clzll((long long)x);
+#else
+  return x ? __builtin_clzll(x) : 64;
+#endif
+}
+// delta(i, j) of the sorted keys: the length of the common prefix of key i and key j, equal keys going on with the common prefix of
+// the sorted positions themselves (so that a run of equal keys becomes a balanced subtree, not a chain); -1 outside [0, n).
+MI_HD int lbvh_delta(const uint64_t* keys, uint32_t n, uint32_t i, int64_t j) {
+  if (j < 0 || j >= (int64_t)n) return -1;
+  const uint64_t x = keys[i] ^ keys[j];
+  return x ? lbvh_clz64(x) : 64 + lbvh_clz64((uint64_t)i ^ (uint64_t)j);
+}
+// Karras 2012, interior node i of n - 1 over n >= 2 sorted keys: the range [first, last] of sorted positions below it and the
+// position `split` its two children part at - the first child covers [first, split] (the leaf `split` when first == split), the
+// second [split + 1, last] (the leaf `last` when split + 1 == last). An interior child has the index of its split-side end:
+// `split` for the first, split + 1 for the second.
+MI_HD void lbvh_node(const uint64_t* keys, uint32_t n, uint32_t i, uint32_t& first, uint32_t& last, uint32_t& split) {
+  const int d = lbvh_delta(keys, n, i, (int64_t)i + 1) - lbvh_delta(keys, n, i, (int64_t)i - 1) >= 0 ? 1 : -1;
+  const int dmin = lbvh_delta(keys, n, i, (int64_t)i - d);
+  int64_t lmax = 2;
+  while (lbvh_delta(keys, n, i, (int64_t)i + lmax * d) > dmin) lmax *= 2;
+  int64_t l = 0;
+  for (int64_t t = lmax / 2; t >= 1; t /= 2)
+    if (lbvh_delta(keys, n, i, (int64_t)i + (l + t) * d) > dmin) l += t;
+  const int64_t j = (int64_t)i + l * d;
+  const int dnode = lbvh_delta(keys, n, i, j);
+  int64_t s = 0;
+  for (int64_t t = (l + 1) / 2;; t = (t + 1) / 2) {
+    if (lbvh_delta(keys, n, i, (int64_t)i + (s + t) * d) > dnode) s += t;
+    if (t == 1) break;
+  }
+  const int64_t g = (int64_t)i + s * d + (d < 0 ? -1 : 0);
+  first = (uint32_t)(d > 0 ? (int64_t)i : j); last = (uint32_t)(d > 0 ? j : (int64_t)i); split = (uint32_t)g;
+}
+// The host builder's child-order rule (host/bvh_sah.cpp): the squared distance of a box's centre from the origin, the centre in
+// binary32, the squares and sums in binary64. The child with the smaller value goes first.
+MI_HD double box_centre_dist2(const Box3& b) {
+  const f3 c = (b.lo + b.hi) * .5f;
+  return (double)c.x * c.x + (double)c.y * c.y + (double)c.z * c.z;
+}
+
 // ---- sincos: ext/math/sincos.cpp:236-355 (ACC5, ABSERR, MOD360, flg=0) ---------------------------
 // `tbl` = 92 floats, sin(i degrees); lives in LDS on the device, static storage on the host.
 MI_HD void sincos_deg_table(float x, const float* tbl, float& s, float& c) {

@@ -18,6 +18,8 @@
 #include "trace_wavefront.hpp"
 #include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
+#include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
+#include <rocprim/device/device_radix_sort.hpp>   // the rebuild's two sorts (header-only, compiled for gfx950 with the rest of this file)
 // MI_RAYLIB_VARIANTS=1 (libmi_raylib_variants.so, the test build): the kernel families that were built, measured and not
 // made the default - LDS-staged nodes (kernel 2), the path pool (kernel 3), the speculative walk (spec), the 4-wave and
 // the runtime-weights instantiations (waves, tune), the register-resident MLP kernel K3r (nif_shape r8 / r8s) - stay
@@ -139,6 +141,7 @@ struct SceneOptions {
                                    // profiles/r05_config5_launch_ab.txt): off by default, kept for A/B; results are the same either way
   bool nifTiming = false;          // "nif_timing": HIP events round every MLP launch of a NIF render (mi_get_nif_timing)
   bool refitTiming = false;        // "refit_timing": HIP events round the passes of mi_scene_update* (mi_get_refit_timing)
+  bool rebuildTiming = false;      // "rebuild_timing": HIP events round the passes of mi_scene_rebuild (mi_get_rebuild_timing)
   uint32_t nifGenerations = kNifGenerations;   // MI_RAYLIB_NIF_GENERATIONS / "nif_generations": MLP workgroups launched per resident slot (nif_launch_mlp; measurement knob)
   bool rootStart = true;           // MI_RAYLIB_NO_ROOT_START / "root_start": a cast whose origin lies strictly inside the root's box starts at node 1
   bool sayGrid = false;            // MI_RAYLIB_SAY_GRID / "say_grid": print every persistent launch's grid to stderr (what the runtime said stays resident)
@@ -215,6 +218,7 @@ struct SceneOptions {
     if (key == "pin") return flag01(v, pin);
     if (key == "nif_timing") return flag01(v, nifTiming);
     if (key == "refit_timing") return flag01(v, refitTiming);
+    if (key == "rebuild_timing") return flag01(v, rebuildTiming);
     if (key == "nif_generations") { if (!number(v, 1, 4096, q)) return false; nifGenerations = (uint32_t)q; return true; }
     if (key == "root_start") return flag01(v, rootStart);
     if (key == "say_grid") return flag01(v, sayGrid);
@@ -364,7 +368,10 @@ struct mi_scene {
   // mi_scene_update: what a refit needs, kept on the HOST at create (the device holds only records derived from it), and the
   // device tables the first update builds (refitTables; a scene that is never updated allocates nothing for them)
   struct Refit {
-    std::vector<mi_bvh_node> nodes;                           // the compact nodes at create: the topology, and mi_scene_get_bvh before an update
+    std::vector<mi_bvh_node> nodes;                           // the compact nodes the tables below were built from: those at create (mi_scene_get_bvh before an update), or
+                                                              // the rebuilt ones, read back by the first update after a rebuild (stale: not read back yet)
+    bool stale = false; uint32_t levelCap = 0;                // levelCap: entries d_levelStart holds
+    std::vector<uint32_t> matIds;                             // per geometry (a rebuild writes leaf records)
     std::vector<mi_geom_ref> geometry; std::vector<mi_mesh_info> meshInfo; std::vector<uint16_t> tris;
     std::vector<mi_vec3> verts; std::vector<mi_sphere> spheres; std::vector<mi_disc> discs;   // the geometry at create (-> d_verts ... at the first update)
     uint32_t numVerts = 0, numNormals = 0, numSpheres = 0, numDiscs = 0;
@@ -380,6 +387,21 @@ struct mi_scene {
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // option "refit_timing": round passes 1, 2 and 4
     double ms[3] = {0, 0, 0};                                 // the last update's {leaf, interior, write} pass times
   } refit;
+  // mi_scene_rebuild: the canonical primitive table and the scratch of the passes (rebuild_kernels.hpp), built at the first
+  // rebuild (rebuildTables; a scene that is never rebuilt allocates nothing for them)
+  struct Rebuild {
+    bool ready = false;
+    uint32_t numPrims = 0;
+    RebuildPrim* d_canon = nullptr;
+    RefitBox* d_primBoxes = nullptr; RefitBox* d_parts = nullptr; RefitBox* d_sceneBox = nullptr;
+    uint64_t* d_keys[2] = {nullptr, nullptr}; uint32_t* d_vals[2] = {nullptr, nullptr};        // the Morton sort's double buffers
+    uint32_t* d_depth[2] = {nullptr, nullptr}; uint32_t* d_ids[2] = {nullptr, nullptr};        // the depth sort's
+    uint2* d_child = nullptr; uint2* d_range = nullptr; uint32_t* d_parent = nullptr; uint8_t* d_swapped = nullptr; uint32_t* d_index = nullptr;
+    uint32_t* d_levelStart = nullptr;                         // [kRebuildMaxDepth + 2]
+    void* d_sortTmp = nullptr; size_t sortTmpBytes = 0;
+    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // option "rebuild_timing"
+    double ms[6] = {0, 0, 0, 0, 0, 0};                        // the last rebuild's {boxes + keys, sort, hierarchy + depths, level boxes, preorder, scatter}
+  } rebuild;
 
   ~mi_scene() {
     (void)hipSetDevice(device);
@@ -405,6 +427,7 @@ struct mi_scene {
     if (nifDone) (void)hipEventDestroy(nifDone);
     for (auto& e : nifTimes) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (hipEvent_t e : refit.ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : rebuild.ev) if (e) (void)hipEventDestroy(e);
     nif.release();
   }
   void freeNifSlots() {
@@ -600,6 +623,7 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
   mi_scene::Refit& R = S.refit;
   R.nodes.assign(d.bvh_nodes, d.bvh_nodes + N);
   R.geometry.assign(d.geometry, d.geometry + d.num_geometry);
+  R.matIds.assign(d.mat_ids, d.mat_ids + d.num_geometry);
   R.meshInfo.assign(d.mesh_info, d.mesh_info + d.num_meshes);
   R.tris.assign(d.mesh_tris, d.mesh_tris + (d.num_meshes ? 3 * (size_t)d.num_tris : 0));
   R.verts.assign(d.mesh_verts, d.mesh_verts + (d.num_meshes ? d.num_verts : 0));
@@ -614,8 +638,10 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
 // current one and the one a refit writes), and the current geometry.
 void refitTables(mi_scene& S) {
   mi_scene::Refit& R = S.refit;
-  if (R.ready) return;
+  if (R.ready && !R.stale) return;
   const uint32_t N = (uint32_t)R.nodes.size();
+  // after a rebuild (rebuildScene): the new topology is on the device only - read it back once, and derive the tables again
+  if (R.stale && N) HIP_CHECK(hipMemcpy(R.nodes.data(), R.d_cnodes[R.live], (size_t)N * sizeof(mi_bvh_node), hipMemcpyDeviceToHost));
   std::vector<RefitPrim> prims(N);
   std::vector<uint32_t> height(N, 0);
   for (uint32_t i = N; i-- > 0;) {
@@ -645,9 +671,22 @@ void refitTables(mi_scene& S) {
   // the top levels that fit one workgroup's threads go to refit_top_kernel: one launch for them, not one per level
   R.topFirst = H + 1;
   while (R.topFirst > 1 && R.levelStart[R.topFirst] - R.levelStart[R.topFirst - 1] <= kRefitTopThreads) --R.topFirst;
+  if (R.levelStart.size() > R.levelCap) {      // (a rebuilt tree may be higher than the one before: room to spare, the old array goes with the scene)
+    R.levelCap = 2 * (uint32_t)R.levelStart.size();
+    HIP_CHECK(hipMalloc(&R.d_levelStart, R.levelCap * sizeof(uint32_t)));
+    S.keep(R.d_levelStart);
+  }
+  HIP_CHECK(hipMemcpy(R.d_levelStart, R.levelStart.data(), R.levelStart.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  if (R.ready) {                               // the same node count: the tables' arrays are reused
+    if (N) {
+      HIP_CHECK(hipMemcpy(R.d_prims, prims.data(), (size_t)N * sizeof(RefitPrim), hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(R.d_order, order.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    R.stale = false;
+    return;
+  }
   R.d_prims = S.keep(upload(prims));
   R.d_order = S.keep(upload(order));
-  R.d_levelStart = S.keep(upload(R.levelStart));
   R.d_cnodes[0] = S.keep(upload(R.nodes));
   R.d_cnodes[1] = S.keep(upload(R.nodes));
   if (N) HIP_CHECK(hipMalloc(&R.d_boxes, (size_t)N * sizeof(RefitBox)));
@@ -746,6 +785,163 @@ void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
     ds.rootLoY = root.min_y; ds.rootHiY = root.min_y + half_bits_to_float(root.dy);
     ds.rootLoZ = root.min_z; ds.rootHiZ = root.min_z + half_bits_to_float(root.dz);
   }
+}
+
+// ---- topology rebuild (mi_scene_rebuild, rebuild_kernels.hpp) ---------------------------------------------------------------------
+template <class K>
+void rebuildSort(mi_scene::Rebuild& B, K* keys[2], uint32_t* vals[2], uint32_t n, unsigned endBit, hipStream_t stream, K*& keysOut, uint32_t*& valsOut) {
+  rocprim::double_buffer<K> kb(keys[0], keys[1]);
+  rocprim::double_buffer<uint32_t> vb(vals[0], vals[1]);
+  size_t bytes = B.sortTmpBytes;
+  HIP_CHECK(rocprim::radix_sort_pairs(B.d_sortTmp, bytes, kb, vb, n, 0u, endBit, stream));
+  keysOut = kb.current(); valsOut = vb.current();
+}
+template <class K>
+size_t rebuildSortBytes(uint32_t n, unsigned endBit) {
+  rocprim::double_buffer<K> kb(nullptr, nullptr);
+  rocprim::double_buffer<uint32_t> vb(nullptr, nullptr);
+  size_t bytes = 0;
+  HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, kb, vb, n, 0u, endBit, (hipStream_t) nullptr));
+  return bytes;
+}
+
+// The canonical primitive table (geometry 0 .. G - 1, inside a mesh triangle 0 .. T - 1) and the passes' scratch, at the first rebuild.
+void rebuildTables(mi_scene& S) {
+  mi_scene::Rebuild& B = S.rebuild;
+  if (B.ready) return;
+  const mi_scene::Refit& R = S.refit;
+  std::vector<RebuildPrim> canon;
+  for (uint32_t g = 0; g < (uint32_t)R.geometry.size(); ++g) {
+    const mi_geom_ref& r = R.geometry[g];
+    if (r.type == 0) {
+      const mi_mesh_info& m = R.meshInfo[r.index];
+      for (uint32_t t = 0; t < m.num_triangles; ++t) {
+        const size_t base = 3 * ((size_t)m.first_index + t);
+        canon.push_back({m.first_vertex + R.tris[base], m.first_vertex + R.tris[base + 1], m.first_vertex + R.tris[base + 2], REFIT_TRI, g, t, (uint32_t)base, R.matIds[g]});
+      }
+    } else {
+      canon.push_back({r.index, 0u, 0u, r.type == 1 ? (uint32_t)REFIT_SPHERE : (uint32_t)REFIT_DISC, g, 0u, 0u, R.matIds[g]});
+    }
+  }
+  const size_t P = canon.size(), N = R.nodes.size();
+  if (N != (P ? 2 * P - 1 : 0)) throw ArgError("mi_scene_rebuild: the scene's BVH does not hold every primitive exactly once (one leaf per primitive is what a rebuild keeps)");
+  B.numPrims = (uint32_t)P;
+  if (P) {
+    const uint32_t I = (uint32_t)P - 1;
+    auto alloc = [&](auto*& p, size_t count) { HIP_CHECK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(*p))); S.keep(p); };
+    B.d_canon = S.keep(upload(canon));
+    alloc(B.d_primBoxes, P); alloc(B.d_parts, kRebuildParts); alloc(B.d_sceneBox, 1);
+    for (int k = 0; k < 2; ++k) { alloc(B.d_keys[k], P); alloc(B.d_vals[k], P); alloc(B.d_depth[k], I); alloc(B.d_ids[k], I); }
+    alloc(B.d_child, I); alloc(B.d_range, I); alloc(B.d_parent, N); alloc(B.d_swapped, I); alloc(B.d_index, N);
+    alloc(B.d_levelStart, kRebuildMaxDepth + 2);
+    B.sortTmpBytes = std::max(rebuildSortBytes<uint64_t>((uint32_t)P, 3 * kMortonBits), rebuildSortBytes<uint32_t>(std::max(I, 1u), 8));
+    HIP_CHECK(hipMalloc(&B.d_sortTmp, std::max<size_t>(B.sortTmpBytes, 16)));
+    S.keep(B.d_sortTmp);
+  }
+  B.ready = true;
+}
+
+// The rebuild proper on `stream`: passes 1 - 8 (scratch only, then the read-back that decides), then - behind everything already
+// enqueued on the scene - the scatter over the live records. Returns when it is all in place; on a refused box nothing of the
+// scene has changed. Returns the maximal leaf depth (root = 1).
+uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
+  const uint32_t N = S.ds.numNodes;
+  if (!N) return 0;
+  // the current geometry and the two compact arrays on the device, the float-box scratch, the error word: the update's tables, built
+  // once (tables an earlier rebuild left stale stay stale: only an update needs them, and a rebuild reads nothing of them)
+  if (!S.refit.ready) refitTables(S);
+  rebuildTables(S);
+  mi_scene::Refit& R = S.refit;
+  mi_scene::Rebuild& B = S.rebuild;
+  DeviceScene& ds = S.ds;
+  const uint32_t P = B.numPrims, I = P - 1;
+  RefitGeom g;
+  g.verts = R.d_verts; g.spheres = R.d_spheres; g.discs = R.d_discs;
+  g.normals = ds.hasNormals ? ds.meshNormals : nullptr;
+  const int scratch = R.live == 0 ? 1 : 0;
+  const bool timing = S.opt.rebuildTiming;
+  if (timing && !B.ev[0]) for (hipEvent_t& e : B.ev) HIP_CHECK(hipEventCreate(&e));
+  auto mark = [&](int k) { if (timing) HIP_CHECK(hipEventRecord(B.ev[k], stream)); };
+  auto blocks = [](uint32_t n) { return dim3((n + 255) / 256); };
+  RebuildTree t;
+  t.numPrims = P; t.child = B.d_child; t.range = B.d_range; t.parent = B.d_parent; t.swapped = B.d_swapped; t.boxes = R.d_boxes; t.index = B.d_index;
+
+  HIP_CHECK(hipMemsetAsync(R.d_err, 0, sizeof(uint32_t), stream));
+  mark(0);
+  const uint32_t parts = std::min((P + 255) / 256, kRebuildParts);
+  hipLaunchKernelGGL(rebuild_prim_kernel, dim3(parts), dim3(256), 0, stream, P, B.d_canon, g, B.d_primBoxes, B.d_parts, R.d_err);
+  hipLaunchKernelGGL(rebuild_scene_kernel, dim3(1), dim3(kRebuildParts), 0, stream, B.d_parts, parts, B.d_sceneBox);
+  hipLaunchKernelGGL(rebuild_key_kernel, blocks(P), dim3(256), 0, stream, P, B.d_primBoxes, B.d_sceneBox, B.d_keys[0], B.d_vals[0]);
+  HIP_CHECK(hipGetLastError());
+  mark(1);
+  uint64_t* keys = nullptr; uint32_t* sorted = nullptr;
+  rebuildSort<uint64_t>(B, B.d_keys, B.d_vals, P, 3 * kMortonBits, stream, keys, sorted);
+  t.sorted = sorted;
+  mark(2);
+  hipLaunchKernelGGL(rebuild_hierarchy_kernel, blocks(P), dim3(256), 0, stream, keys, B.d_primBoxes, t);
+  uint32_t levelStart[kRebuildMaxDepth + 2] = {0};
+  uint32_t* order = nullptr;
+  if (I) {
+    hipLaunchKernelGGL(rebuild_depth_kernel, blocks(I), dim3(256), 0, stream, I, B.d_parent, B.d_depth[0], B.d_ids[0]);
+    HIP_CHECK(hipGetLastError());
+    uint32_t* depth = nullptr;
+    rebuildSort<uint32_t>(B, B.d_depth, B.d_ids, I, 8, stream, depth, order);
+    HIP_CHECK(hipMemsetAsync(B.d_levelStart, 0, sizeof levelStart, stream));
+    hipLaunchKernelGGL(rebuild_levels_kernel, blocks(I), dim3(256), 0, stream, I, depth, B.d_levelStart);
+    HIP_CHECK(hipGetLastError());
+    // the host launches one kernel per depth: it needs to know where the depths start
+    HIP_CHECK(hipMemcpyAsync(levelStart, B.d_levelStart, sizeof levelStart, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+  }
+  mark(3);
+  const uint32_t D = levelStart[kRebuildMaxDepth + 1];           // the deepest interior node
+  if (I) {
+    if (D >= kRebuildMaxDepth) throw DeviceError("mi_scene_rebuild: interior depth out of range");
+    // depths 0 .. top go to the one-workgroup kernel: from the root down, every level of at most kRefitTopThreads nodes
+    uint32_t top = 0;
+    while (top < D && levelStart[top + 2] - levelStart[top + 1] <= kRefitTopThreads) ++top;
+    for (uint32_t d = D; d > top; --d) {
+      const uint32_t cnt = levelStart[d + 1] - levelStart[d];
+      hipLaunchKernelGGL(rebuild_level_kernel, blocks(cnt), dim3(256), 0, stream, order, levelStart[d], cnt, t, R.d_err);
+    }
+    hipLaunchKernelGGL(rebuild_top_kernel, dim3(1), dim3(kRefitTopThreads), 0, stream, order, B.d_levelStart, top, t, R.d_err);
+    HIP_CHECK(hipGetLastError());
+  }
+  mark(4);
+  hipLaunchKernelGGL(rebuild_preorder_kernel, blocks(N), dim3(256), 0, stream, t);
+  HIP_CHECK(hipGetLastError());
+  mark(5);
+  uint32_t err = 0;
+  RefitBox rootBox{};
+  HIP_CHECK(hipMemcpyAsync(&err, R.d_err, sizeof err, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(&rootBox, R.d_boxes, sizeof rootBox, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (err & (1u << kBoxNotFinite)) throw ArgError("mi_scene_rebuild: a node box is not finite; the scene is unchanged");
+  if (err) throw ArgError("mi_scene_rebuild: a node extent is above 65504 (Cannot compress BVH bounds into fp16 (half)); the scene is unchanged");
+  // from here on the scene changes: after everything already enqueued on it, on any stream
+  for (LaunchSlot& l : S.slots) if (l.stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, l.lastWork, 0));
+  hipLaunchKernelGGL(rebuild_scatter_kernel, blocks(N), dim3(256), 0, stream, t, B.d_canon, g, R.d_cnodes[scratch], const_cast<GNode*>(ds.nodes),
+                     const_cast<GLeaf*>(ds.leaves), const_cast<GLeafRot*>(ds.leavesRot), const_cast<float*>(ds.leafNormals));
+  HIP_CHECK(hipGetLastError());
+  // both compact arrays carry the topology (a refit keeps the links and geomIDs of the array it writes)
+  HIP_CHECK(hipMemcpyAsync(R.d_cnodes[1 - scratch], R.d_cnodes[scratch], (size_t)N * sizeof(mi_bvh_node), hipMemcpyDeviceToDevice, stream));
+  mark(6);
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (timing)
+    for (int k = 0; k < 6; ++k) { float w = 0.f; HIP_CHECK(hipEventElapsedTime(&w, B.ev[k], B.ev[k + 1])); B.ms[k] = w; }
+  R.live = scratch;
+  R.stale = true;                  // the refit's tables follow at the next update (refitTables)
+  ds.rootInterior = 0;
+  if (N > 1) {                     // the root's box as buildDeviceScene sets it (root_start)
+    Box3 rb; rb.lo = mk(rootBox.lx, rootBox.ly, rootBox.lz); rb.hi = mk(rootBox.hx, rootBox.hy, rootBox.hz);
+    mi_bvh_node root{};
+    box_encode(rb, root.min_x, root.min_y, root.min_z, root.dx, root.dy, root.dz);
+    ds.rootLoX = root.min_x; ds.rootHiX = root.min_x + half_bits_to_float(root.dx);
+    ds.rootLoY = root.min_y; ds.rootHiY = root.min_y + half_bits_to_float(root.dy);
+    ds.rootLoZ = root.min_z; ds.rootHiZ = root.min_z + half_bits_to_float(root.dz);
+    ds.rootInterior = 1u;
+  }
+  return I ? D + 2 : 1u;
 }
 
 // Slots per pixel per launch in NIF renders: 48 B each (u, v, bgr, colour, throughput, list entry), and TWO sets of them when
@@ -1289,6 +1485,22 @@ int mi_scene_update(mi_scene* scene, const mi_geometry_update* host_arrays) {
   });
   for (void* d : staged) (void)hipFree(d);
   return rc;
+}
+
+int mi_scene_rebuild(mi_scene* scene, void* hip_stream, uint32_t* max_leaf_depth) {
+  return guarded([&] {
+    if (!scene) throw ArgError("mi_scene_rebuild: null scene");
+    HIP_CHECK(hipSetDevice(scene->device));
+    const uint32_t depth = rebuildScene(*scene, (hipStream_t)hip_stream);
+    if (max_leaf_depth) *max_leaf_depth = depth;
+  });
+}
+
+int mi_get_rebuild_timing(mi_scene* scene, double out[6]) {
+  if (!scene || !out) { g_err = "mi_get_rebuild_timing: null argument"; return MI_ERR_INVALID_ARG; }
+  for (int i = 0; i < 6; ++i) out[i] = scene->rebuild.ms[i];
+  g_err.clear();
+  return MI_OK;
 }
 
 int mi_get_refit_timing(mi_scene* scene, double out[3]) {
