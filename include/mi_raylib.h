@@ -237,15 +237,39 @@ int mi_get_refit_timing(mi_scene* scene, double out[3]);
  * passed the same checks; a scene created with nodes that do not bound its geometry can be refused.)
  * A scene of 0 nodes is a no-op (depth 0), one primitive keeps its single leaf root (depth 1). Counters, options and the NIF
  * environment are untouched; a scene made by mi_scene_create_from_blob rebuilds the same way. mi_scene_get_bvh returns the rebuilt
- * nodes. The first rebuild builds the canonical primitive table and the passes' scratch (about 110 bytes per primitive, plus the
- * update's tables); a scene never rebuilt allocates nothing for them. The refit's tables of the new topology are not built by the
- * rebuild: the first mi_scene_update* after a rebuild reads the compact nodes back once and derives them on the host, as the first
- * update of a scene does. */
+ * nodes. The first rebuild builds the canonical primitive table and the passes' scratch (about 135 bytes per primitive, plus the
+ * update's tables); a scene never rebuilt allocates nothing for them. The rebuild leaves the refit's tables of the new topology
+ * ready on the device (what every node's box is computed from, the nodes bucketed by height, where the heights start: device passes
+ * of the rebuild, read back with its second record): the first mi_scene_update* after a rebuild costs what any other does. Only a
+ * scene's very first update derives its tables on the host, from the nodes the scene was created with; a scene whose first call is
+ * a rebuild never does (mi_get_live_stats counts the derivations). */
 int mi_scene_rebuild(mi_scene* scene, void* hip_stream, uint32_t* max_leaf_depth /* may be NULL */);
 /* Measurement only (tools/bench_rebuild.py): the last rebuild's pass times in milliseconds from HIP events on its stream, out =
  * {primitive boxes + scene box + keys, key sort, hierarchy + depths + depth sort (with the first read-back), level boxes,
- * preorder indices, scatter + copies}; zeros unless scene option "rebuild_timing" is 1. */
+ * preorder indices, refit tables (height sort, height starts, with the second read-back) + scatter + copies}; zeros unless scene
+ * option "rebuild_timing" is 1. */
 int mi_get_rebuild_timing(mi_scene* scene, double out[6]);
+
+/* The surface-area cost of the scene's CURRENT BVH - the nodes mi_scene_get_bvh would return -, summed on the device: the figure a
+ * caller (and option "auto_rebuild") decides between refit and rebuild by. out = {sum_all, sum_leaf, a_root}: a node's term is
+ * a = (ex * ey + ey * ez) + ez * ex in binary64 from its three binary16 extents; sum_all sums it over all nodes (every visited node
+ * costs a box test, leaves included), sum_leaf over the leaves (a primitive test each), a_root is the root's term. sum_all / a_root
+ * is the expected number of box tests of a random line through the root box, sum_leaf / a_root that of primitive tests. The raw
+ * sums come back and the caller divides: an empty scene gives zeros, and a_root == 0 (a root box without area) is legal.
+ * Bit-reproducible: the sums are formed in a fixed shape (blocks of 256 consecutive nodes through a fixed binary tree, then the
+ * partial sums the same way, level by level; no atomics), so the result is the same run to run and on every replica of a group, and
+ * equals the host twin mi_bvh_cost_compact (mi_scene_host.h) of the same nodes bit for bit.
+ * Its kernels run on hip_stream (a hipStream_t as void*; NULL = the null stream) and it waits for that stream only; one read-back of
+ * 32 bytes. It changes nothing of the scene, the counters included. A scene that was never updated or rebuilt still has its nodes on
+ * the host only: the twin then runs there (the same bits) and nothing is allocated. MI_ERR_INVALID_ARG: a null scene or out. */
+int mi_scene_bvh_cost(mi_scene* scene, void* hip_stream, double out[3]);
+
+/* What updates and rebuilds have done to this scene so far: out = {updates applied, updates refused for their geometry (a node box
+ * not finite or too large; argument errors are not counted), explicit rebuilds (mi_scene_rebuild calls that succeeded), automatic
+ * rebuilds (option "auto_rebuild"), host derivations of the refit's tables (1 after the first update of a scene that was not rebuilt
+ * before, else 0: never more), cost evaluations (mi_scene_bvh_cost calls and the policy's own), the current max_leaf_depth (the
+ * scene's at create, the rebuilt tree's afterwards), 0}. Touches no device. */
+int mi_get_live_stats(mi_scene* scene, uint64_t out[8]);
 
 /* Replaces: IpuScene::getTraceTimeSecs (IpuScene.hpp:55). Wall time of the last mi_render. */
 double mi_trace_time_secs(const mi_scene* scene);
@@ -356,7 +380,20 @@ int mi_scene_set_ray_batch(mi_scene* scene, size_t rays_per_batch);
  *   "query_kernel"  0 | 1           ray queries (mi_query*): one thread per ray (0, the default: measured faster) or K4, the
  *                                   persistent phase-scheduled query kernel (1)
  *   "query_tune"    "leafAt,dbl,maxExtra,burst,keep8"   scheduling weights of K4 (csrc/query_kernels.hpp QueryTune)
- * None of them changes a result bit. Two further keys select ARITHMETIC:
+ *   "auto_rebuild"  0 | R > 1       0 (default) = off. A decimal ratio R above 1: mi_scene_update* runs the rebuild itself, before it returns, when
+ *                                   the refitted tree has degraded. Set through this call only (no environment variable, as for the arithmetic
+ *                                   options). The figure compared is est = (26 * sum_all + 224 * sum_leaf) / a_root of mi_scene_bvh_cost - 26
+ *                                   and 224 are the static instruction counts of the box-test and the triangle-test step.
+ *                                   Baseline: est of the tree right after the scene's last rebuild made with the option on; before that, est of
+ *                                   the tree as it stood before the first update that found the option on and had no baseline (evaluated once).
+ *                                   Decision: after an update has been APPLIED (a refused one never triggers it), est of the refitted tree is
+ *                                   computed on the update's stream; if a_root > 0 and est > R * baseline (binary64), mi_scene_rebuild's work
+ *                                   runs on the same stream under the same ordering rules, and the baseline becomes the rebuilt tree's est.
+ *                                   An LBVH is a dearer tree than the host builder's (28.87 against 19.75 box tests per cast on the box scene,
+ *                                   DESIGN.md §17), so a small R can fire once on a healthy tree; the scene then settles on the LBVH's
+ *                                   baseline. mi_get_live_stats tells whether a rebuild happened. Renders and queries equal those of a fresh
+ *                                   scene made from the current arrays and mi_scene_get_bvh's nodes either way.
+ * None of them changes a result bit (auto_rebuild changes the tree, not what a cast returns beyond what mi_scene_rebuild itself documents). Two further keys select ARITHMETIC:
  *   "double_fallback" 0 | 1         the reference built with -DALLOW_DOUBLE_FALLBACK=1 (CMakeLists.txt:13,34-41; src/Mesh.cpp:38-51):
  *                                   edge functions that are exactly zero in binary32 are recomputed in binary64. Results are those
  *                                   of the reference's CPU path built the same way, bit for bit (default 0 = the reference default)
@@ -391,7 +428,9 @@ int mi_nif_infer_device(mi_scene* scene, const float* d_u, const float* d_v, flo
  * mi_group_scene hands out a replica's scene for the per-scene setters (mi_scene_set_nif, mi_scene_set_option, ...),
  * which must be applied to every replica alike. The same holds for geometry updates: mi_scene_update / mi_scene_update_device on
  * every replica's scene, with the same arrays (there is no group-level update entry), and for mi_scene_rebuild: call it on every
- * replica's scene (the result is a function of the geometry alone, so the replicas stay alike). */
+ * replica's scene (the result is a function of the geometry alone, so the replicas stay alike). Option "auto_rebuild" likewise: set it
+ * on every replica's scene, with the same ratio. The decision is a function of the geometry alone - the cost pass is bit-reproducible
+ * and the compare is binary64 -, so replicas fed the same arrays rebuild in the same update and stay alike. */
 typedef struct mi_group mi_group;
 int mi_group_create(const mi_scene_desc* desc, const int32_t* devices, uint32_t num_replicas, int32_t transport, mi_group** out);
 void mi_group_destroy(mi_group* group);

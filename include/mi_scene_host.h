@@ -73,6 +73,20 @@ int mi_refit_compact_bvh(const mi_scene_desc* desc, mi_bvh_node* out);
  * scene a rebuilt one must equal. */
 int mi_build_lbvh_compact(const mi_scene_desc* desc, mi_bvh_node* out, uint32_t* num_nodes, uint32_t* max_leaf_depth);
 
+/* The surface-area cost of a tree of n compact nodes, out = {sum_all, sum_leaf, a_root}: a node's term is
+ * a = (ex * ey + ey * ez) + ez * ex in binary64 from its three binary16 extents (decoded exactly, every operation rounded once in
+ * that order); sum_all sums it over all nodes (every visited node costs a box test), sum_leaf over the leaves (a primitive test
+ * each), a_root is node 0's term. sum_all / a_root is the expected number of box tests of a random line through the root box,
+ * sum_leaf / a_root that of primitive tests; the entry returns the raw sums (zeros for n == 0, and a_root == 0 is legal) and the
+ * caller divides. The sums are formed in a fixed shape - blocks of 256 consecutive entries through a fixed binary tree, level by
+ * level (ipu_ray_lib_amd/csrc/ray_math.h, cost_block_reduce) - which the device pass mi_scene_bvh_cost (mi_raylib.h) runs too:
+ * the twin returns the same three doubles as the device, bit for bit. mi_bvh_cost_compact_block is the same with another block
+ * width (a power of two, at least 2: tests reach three levels with 65 nodes and a width of 4). mi_bvh_cost_estimate is the
+ * figure the auto-rebuild policy compares (mi_raylib.h, option "auto_rebuild"): (26 * sum_all + 224 * sum_leaf) / a_root. */
+int mi_bvh_cost_compact(const mi_bvh_node* nodes, uint32_t n, double out[3]);
+int mi_bvh_cost_compact_block(const mi_bvh_node* nodes, uint32_t n, uint32_t block, double out[3]);
+double mi_bvh_cost_estimate(const double cost[3]);
+
 /* initPerspectiveRayStream(rayStream, image, data, nullptr) + zeroRgb: window_w*window_h rays in
  * row-major window order, origin 0, un-jittered pinhole directions, u=row, v=col. */
 int mi_init_ray_stream(const mi_scene_desc* desc, mi_trace_result* rays, size_t capacity);

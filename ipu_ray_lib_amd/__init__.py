@@ -140,6 +140,10 @@ def host_lib() -> C.CDLL:
                                              C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.mi_refit_compact_bvh.argtypes = [C.POINTER(SceneDesc), C.c_void_p]
         lib.mi_build_lbvh_compact.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.mi_bvh_cost_compact.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
+        lib.mi_bvh_cost_compact_block.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
+        lib.mi_bvh_cost_estimate.argtypes = [C.POINTER(C.c_double)]
+        lib.mi_bvh_cost_estimate.restype = C.c_double
         lib.mi_init_ray_stream.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_size_t]
         lib.mi_scale_rgb.argtypes = [C.c_void_p, C.c_size_t, C.c_float]
         lib.mi_scale_rgb.restype = None
@@ -208,6 +212,8 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_scene_rebuild.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
         lib.mi_get_rebuild_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.mi_scene_get_bvh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.mi_scene_bvh_cost.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        lib.mi_get_live_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.mi_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
         lib.mi_group_destroy.argtypes = [C.c_void_p]
@@ -369,6 +375,29 @@ def build_lbvh(desc: SceneDesc):
     n, depth = C.c_uint32(), C.c_uint32()
     _check_host(host_lib().mi_build_lbvh_compact(C.byref(desc), out.ctypes.data, C.byref(n), C.byref(depth)))
     return out[:n.value].copy(), depth.value
+
+
+def _cost_dict(out) -> dict:
+    """{sum_all, sum_leaf, a_root} and, where a_root > 0, the figures normalised by it: the expected box tests and primitive tests
+    of a random line through the root box, and the estimate the auto-rebuild policy compares (mi_bvh_cost_estimate)."""
+    d = {"sum_all": out[0], "sum_leaf": out[1], "a_root": out[2]}
+    if out[2] > 0:
+        d["box_tests"] = out[0] / out[2]
+        d["prim_tests"] = out[1] / out[2]
+        d["estimate"] = host_lib().mi_bvh_cost_estimate(out)
+    return d
+
+
+def bvh_cost(nodes: np.ndarray, block: int | None = None) -> dict:
+    """mi_bvh_cost_compact: the surface-area cost of a tree of compact nodes (a BVH_NODE array), the host twin of
+    IpuScene.bvh_cost - the same three doubles bit for bit. `block`: another block width of the reduction (a power of two)."""
+    nodes = np.ascontiguousarray(nodes, dtype=BVH_NODE)
+    out = (C.c_double * 3)()
+    if block is None:
+        _check_host(host_lib().mi_bvh_cost_compact(nodes.ctypes.data, nodes.size, out))
+    else:
+        _check_host(host_lib().mi_bvh_cost_compact_block(nodes.ctypes.data, nodes.size, block, out))
+    return _cost_dict(out)
 
 
 def _geometry_array(a, dtype, width):
@@ -608,12 +637,8 @@ class IpuScene:
         """mi_scene_rebuild: a new BVH topology from the scene's current geometry, built on the device (an LBVH; build_lbvh is its
         host twin). `stream`: a raw hipStream_t as an int, default torch.cuda.current_stream() when torch is loaded, else the
         null stream. Synchronous. Returns the maximal leaf depth (root = 1)."""
-        if stream is None:
-            import sys
-            torch = sys.modules.get("torch")
-            stream = torch.cuda.current_stream().cuda_stream if torch is not None and torch.cuda.is_available() else 0
         depth = C.c_uint32()
-        self._check(self._lib.mi_scene_rebuild(self._h, C.c_void_p(stream), C.byref(depth)))
+        self._check(self._lib.mi_scene_rebuild(self._h, C.c_void_p(self._stream(stream)), C.byref(depth)))
         return depth.value
 
     def rebuild_timing(self) -> list:
@@ -621,6 +646,27 @@ class IpuScene:
         out = (C.c_double * 6)()
         self._check(self._lib.mi_get_rebuild_timing(self._h, out))
         return list(out)
+
+    def _stream(self, stream):
+        if stream is None:
+            import sys
+            torch = sys.modules.get("torch")
+            stream = torch.cuda.current_stream().cuda_stream if torch is not None and torch.cuda.is_available() else 0
+        return stream
+
+    def bvh_cost(self, stream=None) -> dict:
+        """mi_scene_bvh_cost: the surface-area cost of the scene's current BVH, summed on the device (bvh_cost is its host twin,
+        bit for bit). `stream` as for rebuild_bvh. Keys as bvh_cost's."""
+        out = (C.c_double * 3)()
+        self._check(self._lib.mi_scene_bvh_cost(self._h, C.c_void_p(self._stream(stream)), out))
+        return _cost_dict(out)
+
+    def live_stats(self) -> dict:
+        """mi_get_live_stats: what updates and rebuilds have done to this scene so far."""
+        out = (C.c_uint64 * 8)()
+        self._check(self._lib.mi_get_live_stats(self._h, out))
+        return dict(zip(("updates_applied", "updates_refused", "rebuilds", "auto_rebuilds", "host_derivations", "cost_evaluations",
+                         "max_leaf_depth"), (int(x) for x in out)))
 
     def bvh_nodes(self) -> np.ndarray:
         """The scene's current compact BVH nodes (mi_scene_get_bvh): a BVH_NODE array."""

@@ -10,6 +10,7 @@
 #include "scene_types.hpp"
 #include "../scene_blob.hpp"
 #include "../ray_shard.hpp"
+#include "../bvh_cost_host.hpp"
 
 using namespace mi;
 using namespace mi::host;
@@ -156,6 +157,15 @@ int mi_build_lbvh_compact(const mi_scene_desc* desc, mi_bvh_node* out, uint32_t*
     *max_leaf_depth = depth;
   });
 }
+
+// The surface-area cost of a tree of compact nodes: the host twin of mi_scene_bvh_cost (bvh_cost_host.hpp)
+int mi_bvh_cost_compact_block(const mi_bvh_node* nodes, uint32_t n, uint32_t block, double out[3]) {
+  if (!out || (!nodes && n)) { g_err = "mi_bvh_cost_compact: null argument"; return MI_ERR_INVALID_ARG; }
+  if (block < 2 || (block & (block - 1))) { g_err = "mi_bvh_cost_compact_block: the block width is a power of two, at least 2"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { bvh_cost_host(nodes, n, block, out); });
+}
+int mi_bvh_cost_compact(const mi_bvh_node* nodes, uint32_t n, double out[3]) { return mi_bvh_cost_compact_block(nodes, n, kCostBlock, out); }
+double mi_bvh_cost_estimate(const double cost[3]) { return cost ? bvh_cost_estimate(cost) : 0.0; }
 
 // initPerspectiveRayStream with gen == nullptr, then zeroRgb (src/app_utils.cpp:19-53)
 int mi_init_ray_stream(const mi_scene_desc* d, mi_trace_result* rays, size_t capacity) {

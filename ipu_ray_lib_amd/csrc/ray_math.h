@@ -231,6 +231,40 @@ MI_HD double box_centre_dist2(const Box3& b) {
   return (double)c.x * c.x + (double)c.y * c.y + (double)c.z * c.z;
 }
 
+// ---- BVH cost: the surface-area cost of a tree of compact nodes ---------------------------------------------------------------
+// One definition for the host twin (mi_bvh_cost_compact, host/scene_api.cpp) and the device pass (cost_kernels.hpp,
+// mi_scene_bvh_cost): both must return the same three doubles bit for bit, run to run.
+// A node's term is half its box's surface area from its three binary16 extents, decoded exactly, in binary64, every operation
+// rounded once in the order written.
+MI_HD double bvh_cost_term(uint16_t dx, uint16_t dy, uint16_t dz) {
+  const double ex = (double)half_bits_to_float(dx), ey = (double)half_bits_to_float(dy), ez = (double)half_bits_to_float(dz);
+  return (ex * ey + ey * ez) + ez * ex;
+}
+// The two sums carried through the reduction: over all nodes (a box test each), over the leaves (a primitive test each).
+struct Cost2 { double all, leaf; };
+MI_HD Cost2 cost_add(Cost2 a, Cost2 b) { Cost2 r; r.all = a.all + b.all; r.leaf = a.leaf + b.leaf; return r; }
+// The reduction's shape. Level 0 holds one Cost2 per node, in node order. A level of n entries becomes one of cost_blocks(n, W)
+// entries: entry b is the sum of entries b W .. b W + W - 1 (entries past the end count as +0) through the fixed binary tree
+// below - strides W / 2, W / 4, .. 1, entry i taking entry i + stride - and the levels repeat until one entry is left (at least
+// once: a single node is reduced as a block of its own). Floating-point addition is not associative: this shape, not the order in
+// which threads happen to run, decides every bit of the result.
+// v[0 .. W) -> v[0]; W a power of two. `lane` of `lanes` workers share the work of one stride, sync() separates the strides
+// (the device: the workgroup's threads and __syncthreads(); the host: one worker, nothing to wait for).
+constexpr uint32_t kCostBlock = 256;
+template <class Sync>
+MI_HD void cost_block_reduce(Cost2* v, uint32_t W, uint32_t lane, uint32_t lanes, Sync&& sync) {
+  for (uint32_t s = W >> 1; s > 0; s >>= 1) {
+    for (uint32_t i = lane; i < s; i += lanes) v[i] = cost_add(v[i], v[i + s]);
+    sync();
+  }
+}
+MI_HD uint32_t cost_blocks(uint32_t n, uint32_t W) { return n / W + (n % W ? 1u : 0u); }
+// The traversal-cost estimate the auto-rebuild policy compares: expected box tests and primitive tests of a random line through
+// the root box, weighted by the static instruction counts of the box-test step and the triangle-test step (DESIGN.md §6,
+// tools/bvh_eval.py). cost = {sum_all, sum_leaf, a_root}; a_root == 0 gives inf or NaN, which the policy never acts on.
+constexpr double kCostBoxTest = 26.0, kCostPrimTest = 224.0;
+MI_HD double bvh_cost_estimate(const double cost[3]) { return (kCostBoxTest * cost[0] + kCostPrimTest * cost[1]) / cost[2]; }
+
 // ---- sincos: ext/math/sincos.cpp:236-355 (ACC5, ABSERR, MOD360, flg=0) ---------------------------
 // `tbl` = 92 floats, sin(i degrees); lives in LDS on the device, static storage on the host.
 MI_HD void sincos_deg_table(float x, const float* tbl, float& s, float& c) {

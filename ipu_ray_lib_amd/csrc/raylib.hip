@@ -19,7 +19,9 @@
 #include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
-#include <rocprim/device/device_radix_sort.hpp>   // the rebuild's two sorts (header-only, compiled for gfx950 with the rest of this file)
+#include "cost_kernels.hpp"          // the surface-area cost of the current tree (mi_scene_bvh_cost, option auto_rebuild)
+#include "bvh_cost_host.hpp"         // its host twin: a scene whose nodes are still only on the host
+#include <rocprim/device/device_radix_sort.hpp>   // the rebuild's three sorts (header-only, compiled for gfx950 with the rest of this file)
 // MI_RAYLIB_VARIANTS=1 (libmi_raylib_variants.so, the test build): the kernel families that were built, measured and not
 // made the default - LDS-staged nodes (kernel 2), the path pool (kernel 3), the speculative walk (spec), the 4-wave and
 // the runtime-weights instantiations (waves, tune), the register-resident MLP kernel K3r (nif_shape r8 / r8s) - stay
@@ -150,6 +152,8 @@ struct SceneOptions {
   bool fast = false;               // "fast": the tolerance tier (FMA box / triangle tests; plain path-trace renders of the default kernel only)
   int queryKernel = 0;             // "query_kernel": ray queries (mi_query*) run the one-thread-per-ray kernel (0, the default: measured faster, DESIGN.md §6 "K4") or K4 (1, query_kernels.hpp)
   QueryTune queryTune = kDefaultQueryTune;   // "query_tune": K4's scheduling weights leafAt,dbl,maxExtra,burst,keep8
+  double autoRebuild = 0.0;        // "auto_rebuild": 0 = off; a ratio R > 1: an applied update whose tree's cost estimate is above R x the baseline's runs
+                                   // the rebuild before it returns (refitScene). No environment variable, as for the arithmetic options: replicas must decide alike
 
   // Every key takes values from a stated domain; anything else leaves the option as it was and returns false
   // (mi_scene_set_option then reports MI_ERR_INVALID_ARG, as include/mi_raylib.h promises).
@@ -164,6 +168,17 @@ struct SceneOptions {
     const unsigned long long q = strtoull(v, &end, 10);
     if (!end || *end != '\0' || v[0] == '-' || q < lo || q > hi) return false;
     out = q;
+    return true;
+  }
+  // "0", or a decimal ratio above 1 (finite; digits, a point, an exponent - nothing strtod would read as hex, inf or nan)
+  static bool autoRebuildValue(const char* v, double& out) {
+    if (!v || !*v) return false;
+    if (!strcmp(v, "0")) { out = 0.0; return true; }
+    for (const char* c = v; *c; ++c) if (!((*c >= '0' && *c <= '9') || *c == '.' || *c == 'e' || *c == 'E' || *c == '+' || *c == '-')) return false;
+    char* end = nullptr;
+    const double r = strtod(v, &end);
+    if (!end || end == v || *end != '\0' || !(r > 1.0) || !std::isfinite(r)) return false;
+    out = r;
     return true;
   }
   bool set(const std::string& key, const char* v) {
@@ -237,6 +252,7 @@ struct SceneOptions {
       return true;
     }
     if (key == "lean_hit") return flag01(v, leanHit);
+    if (key == "auto_rebuild") { if (!autoRebuildValue(v, autoRebuild)) { why = "auto_rebuild takes 0 (off) or a decimal ratio above 1"; return false; } return true; }
     if (key == "leaf_rot") return flag01(v, leafRot);
     if (key == "double_fallback") {
       bool b = doubleFallback;
@@ -368,9 +384,10 @@ struct mi_scene {
   // mi_scene_update: what a refit needs, kept on the HOST at create (the device holds only records derived from it), and the
   // device tables the first update builds (refitTables; a scene that is never updated allocates nothing for them)
   struct Refit {
-    std::vector<mi_bvh_node> nodes;                           // the compact nodes the tables below were built from: those at create (mi_scene_get_bvh before an update), or
-                                                              // the rebuilt ones, read back by the first update after a rebuild (stale: not read back yet)
-    bool stale = false; uint32_t levelCap = 0;                // levelCap: entries d_levelStart holds
+    std::vector<mi_bvh_node> nodes;                           // the compact nodes at create: the scene's current ones until the first update or rebuild (live < 0),
+                                                              // what the first update derives the tables below from; afterwards only their count is used
+    bool tables = false; uint32_t levelCap = 0;               // tables: d_prims, d_order and the level starts describe the current topology (derived on the host by
+                                                              // the first update, written by the device passes of every rebuild); levelCap: entries d_levelStart holds
     std::vector<uint32_t> matIds;                             // per geometry (a rebuild writes leaf records)
     std::vector<mi_geom_ref> geometry; std::vector<mi_mesh_info> meshInfo; std::vector<uint16_t> tris;
     std::vector<mi_vec3> verts; std::vector<mi_sphere> spheres; std::vector<mi_disc> discs;   // the geometry at create (-> d_verts ... at the first update)
@@ -398,10 +415,20 @@ struct mi_scene {
     uint32_t* d_depth[2] = {nullptr, nullptr}; uint32_t* d_ids[2] = {nullptr, nullptr};        // the depth sort's
     uint2* d_child = nullptr; uint2* d_range = nullptr; uint32_t* d_parent = nullptr; uint8_t* d_swapped = nullptr; uint32_t* d_index = nullptr;
     uint32_t* d_levelStart = nullptr;                         // [kRebuildMaxDepth + 2]
+    uint32_t* d_height = nullptr;                             // [2 P - 1] node heights, Karras numbering
+    uint32_t* d_hvals[2] = {nullptr, nullptr};                // the height sort's values (the keys reuse d_keys: 8 P bytes hold 2 P - 1 words)
+    uint32_t* d_heightStart = nullptr;                        // [kRebuildHeightSlots]
     void* d_sortTmp = nullptr; size_t sortTmpBytes = 0;
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // option "rebuild_timing"
-    double ms[6] = {0, 0, 0, 0, 0, 0};                        // the last rebuild's {boxes + keys, sort, hierarchy + depths, level boxes, preorder, scatter}
+    double ms[6] = {0, 0, 0, 0, 0, 0};                        // the last rebuild's {boxes + keys, sort, hierarchy + depths, level boxes, preorder, tables + scatter}
   } rebuild;
+  // the live loop (refit every frame, rebuild when the tree has degraded): the cost pass's scratch, the policy's baseline, what happened
+  struct Live {
+    Cost2* d_cost = nullptr;                                  // slot 0 = {a_root, -}, slot 1 = the last level's one entry, then the levels before it, the first last
+    double baseline = 0.0; bool baselineValid = false;        // the estimate the policy compares against (option auto_rebuild)
+    uint64_t applied = 0, refused = 0, rebuilds = 0, autoRebuilds = 0, hostDerivations = 0, costEvals = 0;
+    uint32_t maxLeafDepth = 0;
+  } live;
 
   ~mi_scene() {
     (void)hipSetDevice(device);
@@ -636,12 +663,56 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
 // The refit's device tables, built on the first update from what buildDeviceScene kept: per node what its box is computed from,
 // the nodes bucketed by height (leaf 0, interior 1 + the higher child), scratch for the float boxes, two compact arrays (the
 // current one and the one a refit writes), and the current geometry.
+// The allocations: the two compact arrays, the tables' arrays, the scratch, the current geometry (about 100 bytes per node).
+void refitAlloc(mi_scene& S) {
+  mi_scene::Refit& R = S.refit;
+  if (R.ready) return;
+  const uint32_t N = (uint32_t)R.nodes.size();
+  if (N) {
+    HIP_CHECK(hipMalloc(&R.d_prims, (size_t)N * sizeof(RefitPrim)));
+    S.keep(R.d_prims);
+    HIP_CHECK(hipMalloc(&R.d_order, (size_t)N * sizeof(uint32_t)));
+    S.keep(R.d_order);
+    HIP_CHECK(hipMalloc(&R.d_boxes, (size_t)N * sizeof(RefitBox)));
+    S.keep(R.d_boxes);
+  }
+  R.d_cnodes[0] = S.keep(upload(R.nodes));
+  R.d_cnodes[1] = S.keep(upload(R.nodes));
+  HIP_CHECK(hipMalloc(&R.d_err, sizeof(uint32_t)));
+  S.keep(R.d_err);
+  R.d_verts = S.keep(upload(R.verts));
+  R.d_spheres = S.keep(upload(R.spheres));
+  R.d_discs = S.keep(upload(R.discs));
+  // (the device copies are the current geometry from now on)
+  R.verts = {}; R.spheres = {}; R.discs = {};
+  R.ready = true;
+}
+
+// Room for `entries` level starts on the device (a rebuilt tree may be higher than the one before: room to spare, the old array
+// goes with the scene).
+void refitLevelRoom(mi_scene& S, uint32_t entries) {
+  mi_scene::Refit& R = S.refit;
+  if (entries <= R.levelCap) return;
+  R.levelCap = 2 * entries;
+  HIP_CHECK(hipMalloc(&R.d_levelStart, R.levelCap * sizeof(uint32_t)));
+  S.keep(R.d_levelStart);
+}
+
+// The top levels that fit one workgroup's threads go to refit_top_kernel: one launch for them, not one per level.
+void refitTopFirst(mi_scene::Refit& R) {
+  const uint32_t H = (uint32_t)R.levelStart.size() - 2;
+  R.topFirst = H + 1;
+  while (R.topFirst > 1 && R.levelStart[R.topFirst] - R.levelStart[R.topFirst - 1] <= kRefitTopThreads) --R.topFirst;
+}
+
+// The tables of a scene's FIRST update, derived on the host from the nodes it was created with. A rebuild writes the tables of its
+// topology on the device (rebuildScene), so nothing is ever derived - or read back - after one.
 void refitTables(mi_scene& S) {
   mi_scene::Refit& R = S.refit;
-  if (R.ready && !R.stale) return;
+  refitAlloc(S);
+  if (R.tables) return;
+  ++S.live.hostDerivations;
   const uint32_t N = (uint32_t)R.nodes.size();
-  // after a rebuild (rebuildScene): the new topology is on the device only - read it back once, and derive the tables again
-  if (R.stale && N) HIP_CHECK(hipMemcpy(R.nodes.data(), R.d_cnodes[R.live], (size_t)N * sizeof(mi_bvh_node), hipMemcpyDeviceToHost));
   std::vector<RefitPrim> prims(N);
   std::vector<uint32_t> height(N, 0);
   for (uint32_t i = N; i-- > 0;) {
@@ -668,37 +739,42 @@ void refitTables(mi_scene& S) {
   for (uint32_t h = 0; h <= H; ++h) R.levelStart[h + 1] += R.levelStart[h];
   std::vector<uint32_t> order(N), at(R.levelStart.begin(), R.levelStart.end() - 1);
   for (uint32_t i = 0; i < N; ++i) order[at[height[i]]++] = i;
-  // the top levels that fit one workgroup's threads go to refit_top_kernel: one launch for them, not one per level
-  R.topFirst = H + 1;
-  while (R.topFirst > 1 && R.levelStart[R.topFirst] - R.levelStart[R.topFirst - 1] <= kRefitTopThreads) --R.topFirst;
-  if (R.levelStart.size() > R.levelCap) {      // (a rebuilt tree may be higher than the one before: room to spare, the old array goes with the scene)
-    R.levelCap = 2 * (uint32_t)R.levelStart.size();
-    HIP_CHECK(hipMalloc(&R.d_levelStart, R.levelCap * sizeof(uint32_t)));
-    S.keep(R.d_levelStart);
-  }
+  refitTopFirst(R);
+  refitLevelRoom(S, (uint32_t)R.levelStart.size());
   HIP_CHECK(hipMemcpy(R.d_levelStart, R.levelStart.data(), R.levelStart.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  if (R.ready) {                               // the same node count: the tables' arrays are reused
-    if (N) {
-      HIP_CHECK(hipMemcpy(R.d_prims, prims.data(), (size_t)N * sizeof(RefitPrim), hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(R.d_order, order.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice));
-    }
-    R.stale = false;
-    return;
+  if (N) {
+    HIP_CHECK(hipMemcpy(R.d_prims, prims.data(), (size_t)N * sizeof(RefitPrim), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(R.d_order, order.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
-  R.d_prims = S.keep(upload(prims));
-  R.d_order = S.keep(upload(order));
-  R.d_cnodes[0] = S.keep(upload(R.nodes));
-  R.d_cnodes[1] = S.keep(upload(R.nodes));
-  if (N) HIP_CHECK(hipMalloc(&R.d_boxes, (size_t)N * sizeof(RefitBox)));
-  S.keep(R.d_boxes);
-  HIP_CHECK(hipMalloc(&R.d_err, sizeof(uint32_t)));
-  S.keep(R.d_err);
-  R.d_verts = S.keep(upload(R.verts));
-  R.d_spheres = S.keep(upload(R.spheres));
-  R.d_discs = S.keep(upload(R.discs));
-  // (the device copies are the current geometry from now on)
-  R.verts = {}; R.spheres = {}; R.discs = {};
-  R.ready = true;
+  R.tables = true;
+}
+
+// ---- tree cost (mi_scene_bvh_cost, cost_kernels.hpp) --------------------------------------------------------------------------------
+// {sum_all, sum_leaf, a_root} of the scene's current compact nodes, on `stream`, which it waits for. A scene that was never updated
+// or rebuilt has its nodes on the host only: the twin runs there, on the same shape, and nothing is allocated.
+void sceneCost(mi_scene& S, hipStream_t stream, double out[3]) {
+  const uint32_t N = S.ds.numNodes;
+  mi_scene::Live& L = S.live;
+  const mi_scene::Refit& R = S.refit;
+  ++L.costEvals;
+  out[0] = out[1] = out[2] = 0.0;
+  if (!N) return;
+  if (R.live < 0) { bvh_cost_host(R.nodes.data(), N, kCostBlock, out); return; }
+  // the levels' sizes, the first level first
+  uint32_t sizes[8]; int levels = 0;
+  uint32_t total = 0;
+  for (uint32_t n = N;;) { n = cost_blocks(n, kCostBlock); sizes[levels++] = n; total += n; if (n == 1) break; }
+  if (!L.d_cost) { HIP_CHECK(hipMalloc(&L.d_cost, ((size_t)total + 1) * sizeof(Cost2))); S.keep(L.d_cost); }
+  // level k lies behind the levels after it: the last one (one entry) in slot 1
+  auto levelAt = [&](int k) { uint32_t at = 1; for (int j = levels - 1; j > k; --j) at += sizes[j]; return L.d_cost + at; };
+  hipLaunchKernelGGL(cost_term_kernel, dim3(sizes[0]), dim3(kCostBlock), 0, stream, R.d_cnodes[R.live], N, levelAt(0), &L.d_cost[0].all);
+  for (int k = 1; k < levels; ++k)
+    hipLaunchKernelGGL(cost_partials_kernel, dim3(sizes[k]), dim3(kCostBlock), 0, stream, levelAt(k - 1), sizes[k - 1], levelAt(k));
+  HIP_CHECK(hipGetLastError());
+  Cost2 back[2];
+  HIP_CHECK(hipMemcpyAsync(back, L.d_cost, sizeof back, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  out[0] = back[1].all; out[1] = back[1].leaf; out[2] = back[0].all;
 }
 
 // Argument rules of the two update entries: the first three touch neither the scene nor a device.
@@ -719,6 +795,7 @@ void updateArgs(const char* fn, const mi_scene* S, const mi_geometry_update* u) 
 // The update proper, on DEVICE arrays (NULL = keep), on `stream`: passes 1 - 3 (scratch only, then the read-back that decides),
 // then - behind everything already enqueued on the scene - pass 4 and the copies into the current geometry. Returns when it is
 // all in place; on a refused box nothing of the scene has changed.
+uint32_t rebuildScene(mi_scene& S, hipStream_t stream);
 void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
   refitTables(S);
   mi_scene::Refit& R = S.refit;
@@ -759,8 +836,17 @@ void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
       R.ms[0] = a; R.ms[1] = b;
     }
     // (an empty leaf box - every point NaN on an axis - also makes its parent's extent infinite: the leaf is named first)
+    if (err) ++S.live.refused;
     if (err & (1u << kBoxNotFinite)) throw ArgError("mi_scene_update: a node box is not finite; the scene is unchanged");
     if (err) throw ArgError("mi_scene_update: a node extent is above 65504 (Cannot compress BVH bounds into fp16 (half)); the scene is unchanged");
+  }
+  // option auto_rebuild: the baseline where there is none yet - the estimate of the tree as it stands before this update, which
+  // is now certain to be applied (R.live still names it)
+  const double ratio = S.opt.autoRebuild;
+  if (ratio > 0.0 && N && !S.live.baselineValid) {
+    double c[3];
+    sceneCost(S, stream, c);
+    S.live.baseline = bvh_cost_estimate(c); S.live.baselineValid = true;
   }
   // from here on the scene changes: after everything already enqueued on it, on any stream
   for (LaunchSlot& l : S.slots) if (l.stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, l.lastWork, 0));
@@ -778,12 +864,23 @@ void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
   if (timing) HIP_CHECK(hipEventRecord(R.ev[1], stream));
   HIP_CHECK(hipStreamSynchronize(stream));
   if (timing) { float w = 0.f; HIP_CHECK(hipEventElapsedTime(&w, R.ev[3], R.ev[1])); R.ms[2] = w; }
+  ++S.live.applied;
   if (!N) return;
   R.live = scratch;
   if (N > 1) {      // the root's box as buildDeviceScene sets it (root_start)
     ds.rootLoX = root.min_x; ds.rootHiX = root.min_x + half_bits_to_float(root.dx);
     ds.rootLoY = root.min_y; ds.rootHiY = root.min_y + half_bits_to_float(root.dy);
     ds.rootLoZ = root.min_z; ds.rootHiZ = root.min_z + half_bits_to_float(root.dz);
+  }
+  // option auto_rebuild: the refitted tree's estimate against the baseline, a binary64 compare of figures that are functions of the
+  // geometry alone (the cost pass is bit-reproducible), so every replica fed the same arrays decides alike
+  if (ratio > 0.0) {
+    double c[3];
+    sceneCost(S, stream, c);
+    if (c[2] > 0.0 && bvh_cost_estimate(c) > ratio * S.live.baseline) {
+      rebuildScene(S, stream);        // (the baseline becomes the rebuilt tree's estimate there)
+      ++S.live.autoRebuilds;
+    }
   }
 }
 
@@ -834,22 +931,24 @@ void rebuildTables(mi_scene& S) {
     for (int k = 0; k < 2; ++k) { alloc(B.d_keys[k], P); alloc(B.d_vals[k], P); alloc(B.d_depth[k], I); alloc(B.d_ids[k], I); }
     alloc(B.d_child, I); alloc(B.d_range, I); alloc(B.d_parent, N); alloc(B.d_swapped, I); alloc(B.d_index, N);
     alloc(B.d_levelStart, kRebuildMaxDepth + 2);
-    B.sortTmpBytes = std::max(rebuildSortBytes<uint64_t>((uint32_t)P, 3 * kMortonBits), rebuildSortBytes<uint32_t>(std::max(I, 1u), 8));
+    alloc(B.d_height, N); alloc(B.d_hvals[0], N); alloc(B.d_hvals[1], N); alloc(B.d_heightStart, kRebuildHeightSlots);
+    B.sortTmpBytes = std::max({rebuildSortBytes<uint64_t>((uint32_t)P, 3 * kMortonBits), rebuildSortBytes<uint32_t>(std::max(I, 1u), 8),
+                               rebuildSortBytes<uint32_t>((uint32_t)N, 8)});
     HIP_CHECK(hipMalloc(&B.d_sortTmp, std::max<size_t>(B.sortTmpBytes, 16)));
     S.keep(B.d_sortTmp);
   }
   B.ready = true;
 }
 
-// The rebuild proper on `stream`: passes 1 - 8 (scratch only, then the read-back that decides), then - behind everything already
-// enqueued on the scene - the scatter over the live records. Returns when it is all in place; on a refused box nothing of the
-// scene has changed. Returns the maximal leaf depth (root = 1).
+// The rebuild proper on `stream`: passes 1 - 9 (scratch only, then the read-back that decides), then - behind everything already
+// enqueued on the scene - the scatter over the live records and the refit's tables. Returns when it is all in place, the refit's
+// tables of the new topology included; on a refused box nothing of the scene has changed. Returns the maximal leaf depth (root = 1).
 uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
   const uint32_t N = S.ds.numNodes;
   if (!N) return 0;
-  // the current geometry and the two compact arrays on the device, the float-box scratch, the error word: the update's tables, built
-  // once (tables an earlier rebuild left stale stay stale: only an update needs them, and a rebuild reads nothing of them)
-  if (!S.refit.ready) refitTables(S);
+  // the current geometry and the two compact arrays on the device, the float-box scratch, the error word, room for the refit's
+  // tables: the update's allocations, made once (a rebuild reads nothing of the tables, and writes them below)
+  refitAlloc(S);
   rebuildTables(S);
   mi_scene::Refit& R = S.refit;
   mi_scene::Rebuild& B = S.rebuild;
@@ -865,6 +964,7 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
   auto blocks = [](uint32_t n) { return dim3((n + 255) / 256); };
   RebuildTree t;
   t.numPrims = P; t.child = B.d_child; t.range = B.d_range; t.parent = B.d_parent; t.swapped = B.d_swapped; t.boxes = R.d_boxes; t.index = B.d_index;
+  t.height = B.d_height;
 
   HIP_CHECK(hipMemsetAsync(R.d_err, 0, sizeof(uint32_t), stream));
   mark(0);
@@ -911,26 +1011,47 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
   hipLaunchKernelGGL(rebuild_preorder_kernel, blocks(N), dim3(256), 0, stream, t);
   HIP_CHECK(hipGetLastError());
   mark(5);
+  // the refit's order of the new topology: the nodes by height (scratch: the Morton sort's key buffers are free by now and hold
+  // 2 P words each), and where the heights start - read back with the decision below, no wait of its own
+  uint32_t* hkeys[2] = {(uint32_t*)B.d_keys[0], (uint32_t*)B.d_keys[1]};
+  hipLaunchKernelGGL(rebuild_heightkey_kernel, blocks(N), dim3(256), 0, stream, t, hkeys[0], B.d_hvals[0]);
+  HIP_CHECK(hipGetLastError());
+  uint32_t* heights = nullptr; uint32_t* byHeight = nullptr;
+  rebuildSort<uint32_t>(B, hkeys, B.d_hvals, N, 8, stream, heights, byHeight);
+  uint32_t heightStart[kRebuildHeightSlots] = {0};
+  HIP_CHECK(hipMemsetAsync(B.d_heightStart, 0, sizeof heightStart, stream));
+  hipLaunchKernelGGL(rebuild_heights_kernel, blocks(N), dim3(256), 0, stream, N, heights, B.d_heightStart);
+  HIP_CHECK(hipGetLastError());
   uint32_t err = 0;
   RefitBox rootBox{};
   HIP_CHECK(hipMemcpyAsync(&err, R.d_err, sizeof err, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipMemcpyAsync(&rootBox, R.d_boxes, sizeof rootBox, hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(heightStart, B.d_heightStart, sizeof heightStart, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream));
   if (err & (1u << kBoxNotFinite)) throw ArgError("mi_scene_rebuild: a node box is not finite; the scene is unchanged");
   if (err) throw ArgError("mi_scene_rebuild: a node extent is above 65504 (Cannot compress BVH bounds into fp16 (half)); the scene is unchanged");
+  const uint32_t H = heightStart[kRebuildHeightSlots - 1];
+  if (H > kRebuildMaxDepth || heightStart[H + 1] != N) throw DeviceError("mi_scene_rebuild: node heights out of range");
+  refitLevelRoom(S, H + 2);
   // from here on the scene changes: after everything already enqueued on it, on any stream
   for (LaunchSlot& l : S.slots) if (l.stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, l.lastWork, 0));
   hipLaunchKernelGGL(rebuild_scatter_kernel, blocks(N), dim3(256), 0, stream, t, B.d_canon, g, R.d_cnodes[scratch], const_cast<GNode*>(ds.nodes),
-                     const_cast<GLeaf*>(ds.leaves), const_cast<GLeafRot*>(ds.leavesRot), const_cast<float*>(ds.leafNormals));
+                     const_cast<GLeaf*>(ds.leaves), const_cast<GLeafRot*>(ds.leavesRot), const_cast<float*>(ds.leafNormals), R.d_prims);
   HIP_CHECK(hipGetLastError());
   // both compact arrays carry the topology (a refit keeps the links and geomIDs of the array it writes)
   HIP_CHECK(hipMemcpyAsync(R.d_cnodes[1 - scratch], R.d_cnodes[scratch], (size_t)N * sizeof(mi_bvh_node), hipMemcpyDeviceToDevice, stream));
+  // the refit's tables of the new topology: the scatter wrote d_prims; the order and the level starts out of the scratch
+  HIP_CHECK(hipMemcpyAsync(R.d_order, byHeight, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+  HIP_CHECK(hipMemcpyAsync(R.d_levelStart, B.d_heightStart, (H + 2) * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
   mark(6);
   HIP_CHECK(hipStreamSynchronize(stream));
   if (timing)
     for (int k = 0; k < 6; ++k) { float w = 0.f; HIP_CHECK(hipEventElapsedTime(&w, B.ev[k], B.ev[k + 1])); B.ms[k] = w; }
   R.live = scratch;
-  R.stale = true;                  // the refit's tables follow at the next update (refitTables)
+  R.levelStart.assign(heightStart, heightStart + H + 2);
+  refitTopFirst(R);
+  R.tables = true;
+  S.live.maxLeafDepth = I ? D + 2 : 1u;
   ds.rootInterior = 0;
   if (N > 1) {                     // the root's box as buildDeviceScene sets it (root_start)
     Box3 rb; rb.lo = mk(rootBox.lx, rootBox.ly, rootBox.lz); rb.hi = mk(rootBox.hx, rootBox.hy, rootBox.hz);
@@ -941,7 +1062,15 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
     ds.rootLoZ = root.min_z; ds.rootHiZ = root.min_z + half_bits_to_float(root.dz);
     ds.rootInterior = 1u;
   }
-  return I ? D + 2 : 1u;
+  // option auto_rebuild: the baseline is the estimate of the tree right after its last rebuild (with the option off, an update
+  // that finds it on takes the tree as it then stands)
+  S.live.baselineValid = false;
+  if (S.opt.autoRebuild > 0.0) {
+    double c[3];
+    sceneCost(S, stream, c);
+    S.live.baseline = bvh_cost_estimate(c); S.live.baselineValid = true;
+  }
+  return S.live.maxLeafDepth;
 }
 
 // Slots per pixel per launch in NIF renders: 48 B each (u, v, bgr, colour, throughput, list entry), and TWO sets of them when
@@ -1426,6 +1555,7 @@ int mi_scene_create(const mi_scene_desc* desc, mi_scene** out) {
     S->params.mesh_normals = nullptr; S->params.mat_ids = nullptr; S->params.materials = nullptr; S->params.bvh_nodes = nullptr;
     S->params.spheres = nullptr; S->params.discs = nullptr;
     S->opt.fromEnvironment();      // read once, into this scene (SceneOptions)
+    S->live.maxLeafDepth = desc->max_leaf_depth;
   });
   if (rc != MI_OK) { delete S; return rc; }
   *out = S;
@@ -1492,8 +1622,26 @@ int mi_scene_rebuild(mi_scene* scene, void* hip_stream, uint32_t* max_leaf_depth
     if (!scene) throw ArgError("mi_scene_rebuild: null scene");
     HIP_CHECK(hipSetDevice(scene->device));
     const uint32_t depth = rebuildScene(*scene, (hipStream_t)hip_stream);
+    ++scene->live.rebuilds;
     if (max_leaf_depth) *max_leaf_depth = depth;
   });
+}
+
+int mi_scene_bvh_cost(mi_scene* scene, void* hip_stream, double out[3]) {
+  if (!scene || !out) { g_err = "mi_scene_bvh_cost: null argument"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    if (scene->refit.live >= 0) HIP_CHECK(hipSetDevice(scene->device));
+    sceneCost(*scene, (hipStream_t)hip_stream, out);
+  });
+}
+
+int mi_get_live_stats(mi_scene* scene, uint64_t out[8]) {
+  if (!scene || !out) { g_err = "mi_get_live_stats: null argument"; return MI_ERR_INVALID_ARG; }
+  const mi_scene::Live& L = scene->live;
+  const uint64_t v[8] = {L.applied, L.refused, L.rebuilds, L.autoRebuilds, L.hostDerivations, L.costEvals, L.maxLeafDepth, 0};
+  for (int i = 0; i < 8; ++i) out[i] = v[i];
+  g_err.clear();
+  return MI_OK;
 }
 
 int mi_get_rebuild_timing(mi_scene* scene, double out[6]) {
@@ -1646,6 +1794,8 @@ int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n)
 
 int mi_scene_set_option(mi_scene* scene, const char* key, const char* value) {
   if (!scene || !key || !value) { g_err = "mi_scene_set_option: null argument"; return MI_ERR_INVALID_ARG; }
+  // (a value auto_rebuild does not take is refused before the scene is touched)
+  if (!strcmp(key, "auto_rebuild")) { double r; if (!SceneOptions::autoRebuildValue(value, r)) { g_err = std::string("mi_scene_set_option: auto_rebuild takes 0 (off) or a decimal ratio above 1: ") + key + "=" + value; return MI_ERR_INVALID_ARG; } }
   if (!scene->opt.set(key, value)) { g_err = std::string("mi_scene_set_option: ") + scene->opt.why + ": " + key + "=" + value; return MI_ERR_INVALID_ARG; }
   return MI_OK;
 }

@@ -22,8 +22,13 @@
 //   6 rebuild_level_kernel      one launch per depth, deepest first: the child order and the union of the children's boxes;
 //     rebuild_top_kernel        the small top levels in ONE workgroup, __syncthreads() between levels
 //   7 rebuild_preorder_kernel   one thread per node: its preorder index, walking up once more
-//   8 (host) read back the error word and the root box; on an error the scene is untouched (all of the above wrote scratch)
-//   9 rebuild_scatter_kernel    one thread per node: the compact node, GNode, GLeaf, GLeafRot and vertex normals at its new index
+//   8 rebuild_heightkey_kernel one thread per node: (height, preorder index) at its preorder index - the heights come from pass 6
+//     (rocPRIM radix sort)      nodes by height, stable: leaves first, inside a height by preorder index;
+//     rebuild_heights_kernel    where each height starts - the refit's d_order / levelStart of the new topology (refit_kernels.hpp)
+//   9 (host) read back the error word, the root box and the height starts; on an error the scene is untouched (all of the above
+//     wrote scratch)
+//  10 rebuild_scatter_kernel    one thread per node: the compact node, GNode, GLeaf, GLeafRot, vertex normals and the refit's
+//                               RefitPrim at its new index
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -51,10 +56,14 @@ struct RebuildTree {
   uint8_t* swapped;             // [P - 1] 1 = the higher-key child goes first
   RefitBox* boxes;              // [2 P - 1] float boxes
   uint32_t* index;              // [2 P - 1] preorder index
+  uint32_t* height;             // [2 P - 1] leaf 0, interior 1 + the higher child (what the refit buckets its passes by)
 };
 
 constexpr uint32_t kRebuildParts = 1024;       // workgroups of pass 1 = parts of the scene box, reduced by one workgroup of as many threads
 constexpr uint32_t kRebuildMaxDepth = 128;     // interior depths are below 63 key bits + 32 index bits
+// heights 0 .. H with H <= kRebuildMaxDepth (the root's height is the deepest interior depth + 1): heightStart[0 .. H + 1], and H
+// itself in the last slot
+constexpr uint32_t kRebuildHeightSlots = kRebuildMaxDepth + 3;
 
 __device__ __forceinline__ void rebuild_store_box(RefitBox* boxes, uint32_t i, const Box3& b) {
   RefitBox r; r.lx = b.lo.x; r.ly = b.lo.y; r.lz = b.lo.z; r.hx = b.hi.x; r.hy = b.hi.y; r.hz = b.hi.z;
@@ -113,6 +122,7 @@ __global__ void __launch_bounds__(256) rebuild_hierarchy_kernel(const uint64_t* 
   const uint32_t P = t.numPrims, I = P - 1;
   if (j >= P) return;
   t.boxes[I + j] = primBoxes[t.sorted[j]];
+  t.height[I + j] = 0u;
   if (j >= I) return;
   uint32_t first, last, split;
   lbvh_node(keys, P, j, first, last, split);
@@ -150,6 +160,8 @@ __device__ __forceinline__ void rebuild_interior(uint32_t i, const RebuildTree& 
   const bool sw = box_centre_dist2(r) < box_centre_dist2(l);
   const Box3 u = sw ? box_union(r, l) : box_union(l, r);
   t.swapped[i] = sw ? 1 : 0;
+  const uint32_t hl = t.height[c.x], hr = t.height[c.y];
+  t.height[i] = 1u + (hl > hr ? hl : hr);
   rebuild_store_box(t.boxes, i, u);
   rebuild_check_box(u, err);
 }
@@ -189,10 +201,30 @@ __global__ void __launch_bounds__(256) rebuild_preorder_kernel(RebuildTree t) {
   t.index[n] = at;
 }
 
-// pass 9: node n's records at its preorder index, as buildDeviceScene (raylib.hip) derives them at create from the compact nodes
-// and the geometry; interior nodes leave zero records behind, as at create.
+// pass 8: the refit's order of the new topology. Slot i (a preorder index) gets (height, i), so that the stable sort by height
+// leaves every height's nodes in preorder - the order the host derivation of a scene's first update gives them.
+__global__ void __launch_bounds__(256) rebuild_heightkey_kernel(RebuildTree t, uint32_t* keys, uint32_t* vals) {
+  const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= 2 * t.numPrims - 1) return;
+  const uint32_t i = t.index[n];
+  keys[i] = t.height[n];
+  vals[i] = i;
+}
+// height[] sorted, N entries: heightStart[h] = the first position of height h, heightStart[H + 1] = N for the largest height H,
+// which goes to the last slot (every height 0 .. H has a node; the array was cleared before)
+__global__ void __launch_bounds__(256) rebuild_heights_kernel(uint32_t N, const uint32_t* height, uint32_t* heightStart) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= N) return;
+  const uint32_t h = height[k];
+  if (h > kRebuildMaxDepth) { if (k == N - 1) heightStart[kRebuildHeightSlots - 1] = h; return; }   // (cannot happen; the driver refuses it)
+  if (k == 0 || height[k - 1] != h) heightStart[h] = k;
+  if (k == N - 1) { heightStart[h + 1] = N; heightStart[kRebuildHeightSlots - 1] = h; }
+}
+
+// pass 10: node n's records at its preorder index, as buildDeviceScene (raylib.hip) derives them at create from the compact nodes
+// and the geometry; interior nodes leave zero records behind, as at create. prims[i]: what a later refit computes node i's box from.
 __global__ void __launch_bounds__(256) rebuild_scatter_kernel(RebuildTree t, const RebuildPrim* canon, RefitGeom g, mi_bvh_node* cnodes,
-                                                              GNode* nodes, GLeaf* leaves, GLeafRot* rot, float* leafNormals) {
+                                                              GNode* nodes, GLeaf* leaves, GLeafRot* rot, float* leafNormals, RefitPrim* prims) {
   const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t P = t.numPrims, I = P - 1;
   if (n >= 2 * P - 1) return;
@@ -210,13 +242,16 @@ __global__ void __launch_bounds__(256) rebuild_scatter_kernel(RebuildTree t, con
   __builtin_memset(&L, 0, sizeof L);
   __builtin_memset(&R, 0, sizeof R);
   float vn[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  RefitPrim rp;
   if (n < I) {
     const uint2 ch = t.child[n];
     c.geom_id = MI_INVALID_GEOM;
     c.prim_or_second_child = i + 1u + rebuild_size(t, t.swapped[n] ? ch.y : ch.x);
     nd.hit = (i + 1u) << 5;
+    rp.a = c.prim_or_second_child; rp.b = 0u; rp.c = 0u; rp.kind = REFIT_INTERIOR;
   } else {
     const RebuildPrim p = canon[t.sorted[n - I]];
+    rp.a = p.a; rp.b = p.b; rp.c = p.c; rp.kind = p.kind;
     c.geom_id = (uint16_t)p.geomID;
     c.prim_or_second_child = p.primID;
     nd.hit = (end << 5) | kLeafFlag;
@@ -252,6 +287,7 @@ __global__ void __launch_bounds__(256) rebuild_scatter_kernel(RebuildTree t, con
     }
   }
   cnodes[i] = c;
+  prims[i] = rp;
   nodes[i] = nd;
   leaves[i] = L;
   rot[i] = R;
