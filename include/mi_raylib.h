@@ -250,6 +250,55 @@ int mi_scene_rebuild(mi_scene* scene, void* hip_stream, uint32_t* max_leaf_depth
  * option "rebuild_timing" is 1. */
 int mi_get_rebuild_timing(mi_scene* scene, double out[6]);
 
+/* Replace the CONTENTS of a live scene: new geometry list, meshes, triangle lists, vertices, normals, spheres, discs, material ids
+ * and materials - every count may differ from the scene's, vertex normals may appear or disappear - and its BVH built on the device
+ * (Embree's rtcCommitScene after attaching or detaching geometry, an OptiX BUILD into a live pipeline). The scene stays: the render
+ * parameters of its desc (image, fov, spp, seed, window, path length), the NIF environment, every option, the counters (they go
+ * on counting), the launch slots and their scratch, its place in a group. An empty scene (mi_scene_create with no geometry and no
+ * nodes) that takes this call is a scene made without a host-built BVH.
+ * Arrays. The control plane - geometry, mesh_info, mat_ids, materials - is always HOST memory. The data plane - mesh_tris,
+ * mesh_verts, mesh_normals, spheres, discs - is HOST memory for mi_scene_set_geometry and DEVICE memory for
+ * mi_scene_set_geometry_device. All of them are copied: they may be freed when the call returns.
+ * Result. The scene's contents are exactly the given arrays and its BVH is their LBVH: mi_scene_get_bvh returns what
+ * mi_build_lbvh_compact (mi_scene_host.h) computes from the same arrays, byte for byte; *max_leaf_depth (may be NULL) is the twin's
+ * depth; every render and query afterwards equals that of a scene freshly created from the arrays and the twin's nodes, bit for
+ * bit. No primitives: an empty scene (0 nodes, depth 0). One primitive: a single leaf root (depth 1).
+ * How. The new contents are built aside and swapped in: new geometry buffers, device records and refit tables are allocated, the
+ * canonical primitive table is written by a kernel (one thread per primitive, a binary search over the geometries' prefix sums),
+ * the passes of mi_scene_rebuild run into the new buffers, the decision is read back, and only then the scene's pointers are
+ * swapped and the old buffers freed. The rebuild's scratch is reused where it is large enough. Peak device memory is the old scene
+ * plus the new one plus the scratch (about 135 bytes per primitive).
+ * Ordering and return. Work enqueued on the scene before the call, on any stream, sees the old contents. The call returns once
+ * the new contents are in place. Its kernels and copies run on hip_stream (a hipStream_t as void*; NULL = the null stream;
+ * mi_scene_set_geometry uses the null stream) and it waits for that stream only - and, before it frees anything old, for the
+ * work the scene had enqueued before (the launch slots' events).
+ * Refusal. MI_ERR_INVALID_ARG leaves the scene unchanged - every record, node and later result. Refused is exactly what
+ * mi_scene_create from the same arrays and the twin's nodes would refuse, with its words where the check is the same one: a null
+ * array that comes with a count, a geometry type, geometry index, material index or mesh range out of bounds, normals neither
+ * absent nor one per vertex, more than 65535 geometries, more than 2^25 primitives, a triangle's vertex index not below its mesh's
+ * num_vertices, a node box that is not finite, an extent above 65504. The last three are found on the device (the error word
+ * the passes share); the others on the host before any device work. A null scene or struct is refused before a device is touched.
+ * Afterwards the scene is in the state of one just rebuilt: the refit's tables are device-made and ready (no host derivation, the
+ * first mi_scene_update* costs what any other does, and its count checks use the new counts), mi_scene_rebuild is the identity,
+ * mi_get_live_stats counts the call and carries the new depth, and option "auto_rebuild" takes the new tree's estimate as its
+ * baseline (off: the baseline is dropped, a later enable measures the new tree). */
+typedef struct {
+  /* control plane: always HOST memory (at most 65535 geometries) */
+  const mi_geom_ref*  geometry;   uint32_t num_geometry;
+  const mi_mesh_info* mesh_info;  uint32_t num_meshes;
+  const uint32_t*     mat_ids;    uint32_t num_mat_ids;
+  const mi_material*  materials;  uint32_t num_materials;
+  /* data plane: HOST memory for mi_scene_set_geometry, DEVICE memory for mi_scene_set_geometry_device */
+  const uint16_t*  mesh_tris;    uint32_t num_tris;
+  const mi_vec3*   mesh_verts;   uint32_t num_verts;
+  const mi_vec3*   mesh_normals; uint32_t num_normals;   /* 0, or == num_verts */
+  const mi_sphere* spheres;      uint32_t num_spheres;
+  const mi_disc*   discs;        uint32_t num_discs;
+} mi_scene_geometry;
+
+int mi_scene_set_geometry(mi_scene* scene, const mi_scene_geometry* host_arrays, uint32_t* max_leaf_depth /* may be NULL */);
+int mi_scene_set_geometry_device(mi_scene* scene, const mi_scene_geometry* arrays, void* hip_stream, uint32_t* max_leaf_depth /* may be NULL */);
+
 /* The surface-area cost of the scene's CURRENT BVH - the nodes mi_scene_get_bvh would return -, summed on the device: the figure a
  * caller (and option "auto_rebuild") decides between refit and rebuild by. out = {sum_all, sum_leaf, a_root}: a node's term is
  * a = (ex * ey + ey * ez) + ez * ex in binary64 from its three binary16 extents; sum_all sums it over all nodes (every visited node
@@ -267,8 +316,9 @@ int mi_scene_bvh_cost(mi_scene* scene, void* hip_stream, double out[3]);
 /* What updates and rebuilds have done to this scene so far: out = {updates applied, updates refused for their geometry (a node box
  * not finite or too large; argument errors are not counted), explicit rebuilds (mi_scene_rebuild calls that succeeded), automatic
  * rebuilds (option "auto_rebuild"), host derivations of the refit's tables (1 after the first update of a scene that was not rebuilt
- * before, else 0: never more), cost evaluations (mi_scene_bvh_cost calls and the policy's own), the current max_leaf_depth (the
- * scene's at create, the rebuilt tree's afterwards), 0}. Touches no device. */
+ * before or given new contents, else 0: never more), cost evaluations (mi_scene_bvh_cost calls and the policy's own), the current
+ * max_leaf_depth (the scene's at create, the rebuilt or newly built tree's afterwards), mi_scene_set_geometry* calls that
+ * succeeded}. Touches no device. */
 int mi_get_live_stats(mi_scene* scene, uint64_t out[8]);
 
 /* Replaces: IpuScene::getTraceTimeSecs (IpuScene.hpp:55). Wall time of the last mi_render. */
@@ -430,7 +480,9 @@ int mi_nif_infer_device(mi_scene* scene, const float* d_u, const float* d_v, flo
  * every replica's scene, with the same arrays (there is no group-level update entry), and for mi_scene_rebuild: call it on every
  * replica's scene (the result is a function of the geometry alone, so the replicas stay alike). Option "auto_rebuild" likewise: set it
  * on every replica's scene, with the same ratio. The decision is a function of the geometry alone - the cost pass is bit-reproducible
- * and the compare is binary64 -, so replicas fed the same arrays rebuild in the same update and stay alike. */
+ * and the compare is binary64 -, so replicas fed the same arrays rebuild in the same update and stay alike. New contents go the
+ * same way: mi_scene_set_geometry / mi_scene_set_geometry_device on every replica's scene, with the same arrays (there is no
+ * group-level entry; the result is a function of the arrays alone, and the replica keeps its place in the group). */
 typedef struct mi_group mi_group;
 int mi_group_create(const mi_scene_desc* desc, const int32_t* devices, uint32_t num_replicas, int32_t transport, mi_group** out);
 void mi_group_destroy(mi_group* group);

@@ -73,6 +73,18 @@ int mi_refit_compact_bvh(const mi_scene_desc* desc, mi_bvh_node* out);
  * scene a rebuilt one must equal. */
 int mi_build_lbvh_compact(const mi_scene_desc* desc, mi_bvh_node* out, uint32_t* num_nodes, uint32_t* max_leaf_depth);
 
+/* The canonical primitive table of desc's geometry arrays: its primitives in canonical order (geometry 0 .. num_geometry - 1, inside
+ * a mesh triangle 0 .. T - 1), 32 bytes each - eight uint32: {a, b, c, kind, geomID, primID, triBase, matIndex}; kind 0 = a triangle
+ * (a, b, c = its absolute vertex indices, triBase = the index of its first uint16 in mesh_tris), 1 = a sphere, 2 = a disc (a = its
+ * index in spheres / discs). It is what the LBVH builds sort, so it fixes the tree. The twin of the kernel that writes the table
+ * for mi_scene_set_geometry* (mi_raylib.h), through the same code: the exclusive prefix of the geometries' primitive counts, then
+ * per canonical index a binary search for its geometry (geometries without triangles are stepped over) and the record. desc's
+ * nodes and render parameters are ignored. *count = the primitive count; `out` must hold it (out == NULL with capacity 0: only
+ * the count). MI_ERR_INVALID_ARG with mi_scene_create's words for what it refuses of these arrays: null arrays that come with
+ * counts, a geometry type, geometry index, material index or mesh range out of bounds, normals neither absent nor one per vertex,
+ * more than 65535 geometries, too many primitives, a triangle's vertex index not below its mesh's num_vertices. */
+int mi_canonical_prims(const mi_scene_desc* desc, void* out /* 32 B each */, uint32_t capacity, uint32_t* count);
+
 /* The surface-area cost of a tree of n compact nodes, out = {sum_all, sum_leaf, a_root}: a node's term is
  * a = (ex * ey + ey * ez) + ez * ex in binary64 from its three binary16 extents (decoded exactly, every operation rounded once in
  * that order); sum_all sums it over all nodes (every visited node costs a box test), sum_leaf over the leaves (a primitive test

@@ -99,6 +99,35 @@ class GeometryUpdate(C.Structure):
                 ("discs", C.c_void_p), ("num_discs", C.c_uint32)]
 
 
+class SceneGeometry(C.Structure):
+    """mi_scene_geometry (include/mi_raylib.h): new contents for a live scene. Control plane (geometry, mesh_info, mat_ids,
+    materials) in host memory; data plane in host memory for mi_scene_set_geometry, device memory for ..._device."""
+    _fields_ = [("geometry", C.c_void_p), ("num_geometry", C.c_uint32),
+                ("mesh_info", C.c_void_p), ("num_meshes", C.c_uint32),
+                ("mat_ids", C.c_void_p), ("num_mat_ids", C.c_uint32),
+                ("materials", C.c_void_p), ("num_materials", C.c_uint32),
+                ("mesh_tris", C.c_void_p), ("num_tris", C.c_uint32),
+                ("mesh_verts", C.c_void_p), ("num_verts", C.c_uint32),
+                ("mesh_normals", C.c_void_p), ("num_normals", C.c_uint32),
+                ("spheres", C.c_void_p), ("num_spheres", C.c_uint32),
+                ("discs", C.c_void_p), ("num_discs", C.c_uint32)]
+
+    @classmethod
+    def from_desc(cls, desc: "SceneDesc") -> "SceneGeometry":
+        """The nine arrays of a SceneDesc (its nodes and render parameters are not part of a scene's contents)."""
+        g = cls()
+        for name, _ in cls._fields_:
+            setattr(g, name, getattr(desc, name))
+        return g
+
+
+# a canonical primitive (mi_canonical_prims, include/mi_scene_host.h): kind 0 = triangle (a, b, c = absolute vertex indices), 1 = sphere,
+# 2 = disc (a = its index)
+CANON_PRIM = np.dtype([("a", "<u4"), ("b", "<u4"), ("c", "<u4"), ("kind", "<u4"), ("geomID", "<u4"), ("primID", "<u4"),
+                       ("triBase", "<u4"), ("matIndex", "<u4")])
+assert CANON_PRIM.itemsize == 32
+
+
 class NifDesc(C.Structure):
     """mi_nif_desc (include/mi_scene_host.h)."""
     _fields_ = [("num_layers", C.c_uint32), ("kernels", C.POINTER(C.POINTER(C.c_float))),
@@ -140,6 +169,7 @@ def host_lib() -> C.CDLL:
                                              C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.mi_refit_compact_bvh.argtypes = [C.POINTER(SceneDesc), C.c_void_p]
         lib.mi_build_lbvh_compact.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        lib.mi_canonical_prims.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.mi_bvh_cost_compact.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_compact_block.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_estimate.argtypes = [C.POINTER(C.c_double)]
@@ -210,6 +240,8 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_scene_update.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate)]
         lib.mi_scene_update_device.argtypes = [C.c_void_p, C.POINTER(GeometryUpdate), C.c_void_p]
         lib.mi_scene_rebuild.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.mi_scene_set_geometry.argtypes = [C.c_void_p, C.POINTER(SceneGeometry), C.POINTER(C.c_uint32)]
+        lib.mi_scene_set_geometry_device.argtypes = [C.c_void_p, C.POINTER(SceneGeometry), C.c_void_p, C.POINTER(C.c_uint32)]
         lib.mi_get_rebuild_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.mi_scene_get_bvh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.mi_scene_bvh_cost.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
@@ -287,6 +319,7 @@ class HostScene:
         if not ptr or not count:
             return np.zeros(0, dtype=dtype)
         buf = (C.c_char * (count * dtype.itemsize)).from_address(ptr)
+        buf._scene = self          # a view keeps its scene alive: `HostScene.builtin(...).nodes` must not read freed memory
         return np.frombuffer(buf, dtype=dtype, count=count)
 
     @property
@@ -375,6 +408,17 @@ def build_lbvh(desc: SceneDesc):
     n, depth = C.c_uint32(), C.c_uint32()
     _check_host(host_lib().mi_build_lbvh_compact(C.byref(desc), out.ctypes.data, C.byref(n), C.byref(depth)))
     return out[:n.value].copy(), depth.value
+
+
+def canonical_prims(desc: SceneDesc) -> np.ndarray:
+    """mi_canonical_prims: desc's primitives in canonical order (geometry 0 .. G - 1, inside a mesh triangle 0 .. T - 1), a
+    CANON_PRIM array - the table the LBVH builds sort, from the code the device kernel of IpuScene.set_geometry runs. Raises
+    RaylibError, with mi_scene_create's words, where the arrays are not a scene."""
+    n = C.c_uint32()
+    _check_host(host_lib().mi_canonical_prims(C.byref(desc), None, 0, C.byref(n)))
+    out = np.zeros(n.value, dtype=CANON_PRIM)
+    _check_host(host_lib().mi_canonical_prims(C.byref(desc), out.ctypes.data if n.value else None, n.value, C.byref(n)))
+    return out
 
 
 def _cost_dict(out) -> dict:
@@ -489,6 +533,19 @@ class IpuScene:
         self.desc = extras
         b = np.ascontiguousarray(blob, dtype=np.uint8)
         self._check(self._lib.mi_scene_create_from_blob(b.ctypes.data, b.size, C.byref(extras), C.byref(self._h)))
+        return self
+
+    @classmethod
+    def from_geometry(cls, desc: SceneDesc, variants: bool = False) -> "IpuScene":
+        """A scene without a host-built BVH: an empty scene with desc's render parameters, then set_geometry(desc) - the BVH is
+        the LBVH of desc's arrays, built on the device (desc's own nodes are ignored)."""
+        empty = SceneDesc.from_buffer_copy(desc)
+        for name, _ in SceneGeometry._fields_:
+            setattr(empty, name, 0)
+        empty.bvh_nodes, empty.num_nodes, empty.max_leaf_depth = None, 0, 0
+        self = cls(empty, variants)
+        self.desc = desc
+        self.set_geometry(desc)
         return self
 
     def setHdriRotation(self, degrees: float):
@@ -633,6 +690,45 @@ class IpuScene:
         self._check(self._lib.mi_scene_update_device(self._h, C.byref(u), C.c_void_p(stream)))
         return self
 
+    # -- new contents (mi_scene_set_geometry*): another geometry list, other meshes, other counts; the BVH built on the device ------------
+    def set_geometry(self, desc: SceneDesc) -> int:
+        """Replace the scene's contents by desc's nine arrays (HOST memory; desc's nodes and render parameters are ignored) and
+        build their LBVH on the device (build_lbvh is its host twin). Options, counters, the NIF environment and the render
+        parameters stay. Synchronous; work enqueued before sees the old contents. Returns the maximal leaf depth (root = 1)."""
+        g = SceneGeometry.from_desc(desc)
+        depth = C.c_uint32()
+        self._check(self._lib.mi_scene_set_geometry(self._h, C.byref(g), C.byref(depth)))
+        return depth.value
+
+    def set_geometry_device(self, desc: SceneDesc, tris=None, vertices=None, normals=None, spheres=None, discs=None, stream=None) -> int:
+        """The same with the data plane in contiguous CUDA tensors: tris int16 / uint16 [T, 3], vertices and normals float32 [n, 3],
+        spheres float32 [n, 4], discs float32 [n, 7] (None = none of that kind). The control plane - geometry, mesh_info, mat_ids,
+        materials - is taken from desc (host memory). On `stream` (a raw hipStream_t as an int), default torch.cuda.current_stream()."""
+        import torch
+        g = SceneGeometry.from_desc(desc)
+        keep = []
+        dev = None
+        for ptr, cnt, width, t in (("mesh_tris", "num_tris", 3, tris), ("mesh_verts", "num_verts", 3, vertices), ("mesh_normals", "num_normals", 3, normals),
+                                   ("spheres", "num_spheres", 4, spheres), ("discs", "num_discs", 7, discs)):
+            setattr(g, ptr, None)
+            setattr(g, cnt, 0)
+            if t is None:
+                continue
+            dtypes = tuple(d for d in (torch.int16, getattr(torch, "uint16", None)) if d is not None) if ptr == "mesh_tris" else (torch.float32,)
+            if not t.is_cuda or t.dtype not in dtypes or t.ndim != 2 or t.shape[1] != width or not t.is_contiguous():
+                kind = "16-bit integer" if ptr == "mesh_tris" else "float32"
+                raise ValueError(f"set_geometry_device: {ptr} must be a contiguous {kind} CUDA tensor of shape [n, {width}]")
+            dev = t.device
+            keep.append(t)
+            if t.shape[0]:
+                setattr(g, ptr, t.data_ptr())
+            setattr(g, cnt, t.shape[0])
+        if stream is None:
+            stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None else 0
+        depth = C.c_uint32()
+        self._check(self._lib.mi_scene_set_geometry_device(self._h, C.byref(g), C.c_void_p(stream), C.byref(depth)))
+        return depth.value
+
     def rebuild_bvh(self, stream=None) -> int:
         """mi_scene_rebuild: a new BVH topology from the scene's current geometry, built on the device (an LBVH; build_lbvh is its
         host twin). `stream`: a raw hipStream_t as an int, default torch.cuda.current_stream() when torch is loaded, else the
@@ -666,7 +762,7 @@ class IpuScene:
         out = (C.c_uint64 * 8)()
         self._check(self._lib.mi_get_live_stats(self._h, out))
         return dict(zip(("updates_applied", "updates_refused", "rebuilds", "auto_rebuilds", "host_derivations", "cost_evaluations",
-                         "max_leaf_depth"), (int(x) for x in out)))
+                         "max_leaf_depth", "geometry_sets"), (int(x) for x in out)))
 
     def bvh_nodes(self) -> np.ndarray:
         """The scene's current compact BVH nodes (mi_scene_get_bvh): a BVH_NODE array."""

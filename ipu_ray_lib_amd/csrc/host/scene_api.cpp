@@ -11,6 +11,7 @@
 #include "../scene_blob.hpp"
 #include "../ray_shard.hpp"
 #include "../bvh_cost_host.hpp"
+#include "../canon_prims.hpp"
 
 using namespace mi;
 using namespace mi::host;
@@ -155,6 +156,28 @@ int mi_build_lbvh_compact(const mi_scene_desc* desc, mi_bvh_node* out, uint32_t*
     if (!nodes.empty()) memcpy(out, nodes.data(), nodes.size() * sizeof(mi_bvh_node));
     *num_nodes = (uint32_t)nodes.size();
     *max_leaf_depth = depth;
+  });
+}
+
+// The canonical primitive table of desc's arrays: the host twin of canon_prim_kernel (canon_kernels.hpp, mi_scene_set_geometry*) -
+// the same prefix, the same search and record per canonical index (canon_prims.hpp), the same checks with mi_scene_create's words
+int mi_canonical_prims(const mi_scene_desc* desc, void* out, uint32_t capacity, uint32_t* count) {
+  if (!desc || !count) { g_err = "mi_canonical_prims: null argument"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    auto need = [](bool ok, const char* what) { if (!ok) throw std::invalid_argument(std::string("mi_canonical_prims: ") + what); };
+    const mi_scene_geometry g = canon_geometry_of(*desc);
+    canon_check_control(g, 1u << 26, need);
+    std::vector<uint32_t> primStart((size_t)g.num_geometry + 1);
+    const uint32_t P = canon_prim_starts(g, primStart.data());
+    *count = P;
+    if (!out && !capacity) return;                       // only the count
+    need(out && capacity >= P, "capacity is smaller than the scene's primitive count");
+    RebuildPrim* prims = (RebuildPrim*)out;
+    for (uint32_t p = 0; p < P; ++p) {
+      RebuildPrim q;
+      need(canon_prim(p, primStart.data(), g.num_geometry, g.geometry, g.mesh_info, g.mat_ids, g.mesh_tris, q), "triangle vertex index out of range");
+      memcpy(&prims[p], &q, sizeof q);                   // (the caller's buffer need not be 16-byte aligned)
+    }
   });
 }
 

@@ -19,6 +19,7 @@
 #include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
+#include "canon_kernels.hpp"         // new contents for a live scene: the canonical primitive table on the device (mi_scene_set_geometry*)
 #include "cost_kernels.hpp"          // the surface-area cost of the current tree (mi_scene_bvh_cost, option auto_rebuild)
 #include "bvh_cost_host.hpp"         // its host twin: a scene whose nodes are still only on the host
 #include <rocprim/device/device_radix_sort.hpp>   // the rebuild's three sorts (header-only, compiled for gfx950 with the rest of this file)
@@ -385,7 +386,8 @@ struct mi_scene {
   // device tables the first update builds (refitTables; a scene that is never updated allocates nothing for them)
   struct Refit {
     std::vector<mi_bvh_node> nodes;                           // the compact nodes at create: the scene's current ones until the first update or rebuild (live < 0),
-                                                              // what the first update derives the tables below from; afterwards only their count is used
+                                                              // what the first update derives the tables below from; not read afterwards (the count is ds.numNodes).
+                                                              // New contents (setGeometry) leave every host vector here empty: only the counts below are read then
     bool tables = false; uint32_t levelCap = 0;               // tables: d_prims, d_order and the level starts describe the current topology (derived on the host by
                                                               // the first update, written by the device passes of every rebuild); levelCap: entries d_levelStart holds
     std::vector<uint32_t> matIds;                             // per geometry (a rebuild writes leaf records)
@@ -409,7 +411,8 @@ struct mi_scene {
   struct Rebuild {
     bool ready = false;
     uint32_t numPrims = 0;
-    RebuildPrim* d_canon = nullptr;
+    RebuildPrim* d_canon = nullptr;                           // [numPrims] the canonical table of the scene's contents
+    uint32_t capPrims = 0;                                    // primitives the scratch below has room for (rebuildScratch: new contents reuse it while it fits)
     RefitBox* d_primBoxes = nullptr; RefitBox* d_parts = nullptr; RefitBox* d_sceneBox = nullptr;
     uint64_t* d_keys[2] = {nullptr, nullptr}; uint32_t* d_vals[2] = {nullptr, nullptr};        // the Morton sort's double buffers
     uint32_t* d_depth[2] = {nullptr, nullptr}; uint32_t* d_ids[2] = {nullptr, nullptr};        // the depth sort's
@@ -426,7 +429,7 @@ struct mi_scene {
   struct Live {
     Cost2* d_cost = nullptr;                                  // slot 0 = {a_root, -}, slot 1 = the last level's one entry, then the levels before it, the first last
     double baseline = 0.0; bool baselineValid = false;        // the estimate the policy compares against (option auto_rebuild)
-    uint64_t applied = 0, refused = 0, rebuilds = 0, autoRebuilds = 0, hostDerivations = 0, costEvals = 0;
+    uint64_t applied = 0, refused = 0, rebuilds = 0, autoRebuilds = 0, hostDerivations = 0, costEvals = 0, geometrySets = 0;
     uint32_t maxLeafDepth = 0;
   } live;
 
@@ -465,6 +468,14 @@ struct mi_scene {
     }
   }
   template <class T> T* keep(T* p) { if (p) allocations.push_back((void*)p); return p; }
+  // gives a kept buffer up before the scene goes (new contents replace the old ones': setGeometry)
+  void release(const void* p) {
+    if (!p) return;
+    auto it = std::find(allocations.begin(), allocations.end(), (void*)p);
+    if (it == allocations.end()) return;
+    allocations.erase(it);
+    (void)hipFree((void*)p);
+  }
   // the launch slot of a stream (created on first use; a scene is thread-compatible, not thread-safe)
   LaunchSlot& slotFor(hipStream_t stream);
 };
@@ -690,8 +701,7 @@ void refitAlloc(mi_scene& S) {
 
 // Room for `entries` level starts on the device (a rebuilt tree may be higher than the one before: room to spare, the old array
 // goes with the scene).
-void refitLevelRoom(mi_scene& S, uint32_t entries) {
-  mi_scene::Refit& R = S.refit;
+void refitLevelRoom(mi_scene& S, mi_scene::Refit& R, uint32_t entries) {
   if (entries <= R.levelCap) return;
   R.levelCap = 2 * entries;
   HIP_CHECK(hipMalloc(&R.d_levelStart, R.levelCap * sizeof(uint32_t)));
@@ -740,7 +750,7 @@ void refitTables(mi_scene& S) {
   std::vector<uint32_t> order(N), at(R.levelStart.begin(), R.levelStart.end() - 1);
   for (uint32_t i = 0; i < N; ++i) order[at[height[i]]++] = i;
   refitTopFirst(R);
-  refitLevelRoom(S, (uint32_t)R.levelStart.size());
+  refitLevelRoom(S, R, (uint32_t)R.levelStart.size());
   HIP_CHECK(hipMemcpy(R.d_levelStart, R.levelStart.data(), R.levelStart.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   if (N) {
     HIP_CHECK(hipMemcpy(R.d_prims, prims.data(), (size_t)N * sizeof(RefitPrim), hipMemcpyHostToDevice));
@@ -902,57 +912,64 @@ size_t rebuildSortBytes(uint32_t n, unsigned endBit) {
   return bytes;
 }
 
-// The canonical primitive table (geometry 0 .. G - 1, inside a mesh triangle 0 .. T - 1) and the passes' scratch, at the first rebuild.
+// The passes' scratch for P primitives: every array here is written from its start by every build before it is read, so it belongs
+// to no contents. Kept while it is large enough: new contents of a scene (setGeometry) reuse it, and take new arrays - the old ones
+// are given up by the caller - only when they have grown. (The canonical table is not scratch: it is the contents'.)
+void rebuildScratch(mi_scene& S, mi_scene::Rebuild& B, uint32_t P) {
+  const size_t N = 2 * (size_t)P - 1;
+  const uint32_t I = P - 1;
+  const size_t sortBytes = std::max({rebuildSortBytes<uint64_t>(P, 3 * kMortonBits), rebuildSortBytes<uint32_t>(std::max(I, 1u), 8),
+                                     rebuildSortBytes<uint32_t>((uint32_t)N, 8)});
+  if (B.capPrims >= P && B.sortTmpBytes >= sortBytes) return;
+  auto alloc = [&](auto*& p, size_t count) { HIP_CHECK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(*p))); S.keep(p); };
+  alloc(B.d_primBoxes, P); alloc(B.d_parts, kRebuildParts); alloc(B.d_sceneBox, 1);
+  for (int k = 0; k < 2; ++k) { alloc(B.d_keys[k], P); alloc(B.d_vals[k], P); alloc(B.d_depth[k], I); alloc(B.d_ids[k], I); }
+  alloc(B.d_child, I); alloc(B.d_range, I); alloc(B.d_parent, N); alloc(B.d_swapped, I); alloc(B.d_index, N);
+  alloc(B.d_levelStart, kRebuildMaxDepth + 2);
+  alloc(B.d_height, N); alloc(B.d_hvals[0], N); alloc(B.d_hvals[1], N); alloc(B.d_heightStart, kRebuildHeightSlots);
+  B.sortTmpBytes = sortBytes;
+  HIP_CHECK(hipMalloc(&B.d_sortTmp, std::max<size_t>(B.sortTmpBytes, 16)));
+  S.keep(B.d_sortTmp);
+  B.capPrims = P;
+}
+// every buffer rebuildScratch allocates
+std::vector<void*> rebuildScratchBuffers(const mi_scene::Rebuild& B) {
+  return {B.d_primBoxes, B.d_parts, B.d_sceneBox, B.d_keys[0], B.d_keys[1], B.d_vals[0], B.d_vals[1], B.d_depth[0], B.d_depth[1],
+          B.d_ids[0], B.d_ids[1], B.d_child, B.d_range, B.d_parent, B.d_swapped, B.d_index, B.d_levelStart, B.d_height, B.d_hvals[0],
+          B.d_hvals[1], B.d_heightStart, B.d_sortTmp};
+}
+
+// The canonical primitive table (geometry 0 .. G - 1, inside a mesh triangle 0 .. T - 1) and the passes' scratch, at the first rebuild
+// of a scene that still has the contents it was created with: from the host copies create kept. (New contents write the table
+// on the device and leave it ready: setGeometry.)
 void rebuildTables(mi_scene& S) {
   mi_scene::Rebuild& B = S.rebuild;
   if (B.ready) return;
   const mi_scene::Refit& R = S.refit;
-  std::vector<RebuildPrim> canon;
-  for (uint32_t g = 0; g < (uint32_t)R.geometry.size(); ++g) {
-    const mi_geom_ref& r = R.geometry[g];
-    if (r.type == 0) {
-      const mi_mesh_info& m = R.meshInfo[r.index];
-      for (uint32_t t = 0; t < m.num_triangles; ++t) {
-        const size_t base = 3 * ((size_t)m.first_index + t);
-        canon.push_back({m.first_vertex + R.tris[base], m.first_vertex + R.tris[base + 1], m.first_vertex + R.tris[base + 2], REFIT_TRI, g, t, (uint32_t)base, R.matIds[g]});
-      }
-    } else {
-      canon.push_back({r.index, 0u, 0u, r.type == 1 ? (uint32_t)REFIT_SPHERE : (uint32_t)REFIT_DISC, g, 0u, 0u, R.matIds[g]});
-    }
-  }
-  const size_t P = canon.size(), N = R.nodes.size();
+  mi_scene_geometry d{};
+  d.geometry = R.geometry.data(); d.num_geometry = (uint32_t)R.geometry.size(); d.mesh_info = R.meshInfo.data(); d.num_meshes = (uint32_t)R.meshInfo.size();
+  std::vector<uint32_t> primStart(d.num_geometry + 1);
+  const size_t P = canon_prim_starts(d, primStart.data()), N = R.nodes.size();
+  std::vector<RebuildPrim> canon(P);
+  for (uint32_t p = 0; p < (uint32_t)P; ++p)      // (the indices were checked at create)
+    (void)canon_prim(p, primStart.data(), d.num_geometry, d.geometry, d.mesh_info, R.matIds.data(), R.tris.data(), canon[p]);
   if (N != (P ? 2 * P - 1 : 0)) throw ArgError("mi_scene_rebuild: the scene's BVH does not hold every primitive exactly once (one leaf per primitive is what a rebuild keeps)");
   B.numPrims = (uint32_t)P;
   if (P) {
-    const uint32_t I = (uint32_t)P - 1;
-    auto alloc = [&](auto*& p, size_t count) { HIP_CHECK(hipMalloc(&p, std::max<size_t>(count, 1) * sizeof(*p))); S.keep(p); };
+    rebuildScratch(S, B, (uint32_t)P);
     B.d_canon = S.keep(upload(canon));
-    alloc(B.d_primBoxes, P); alloc(B.d_parts, kRebuildParts); alloc(B.d_sceneBox, 1);
-    for (int k = 0; k < 2; ++k) { alloc(B.d_keys[k], P); alloc(B.d_vals[k], P); alloc(B.d_depth[k], I); alloc(B.d_ids[k], I); }
-    alloc(B.d_child, I); alloc(B.d_range, I); alloc(B.d_parent, N); alloc(B.d_swapped, I); alloc(B.d_index, N);
-    alloc(B.d_levelStart, kRebuildMaxDepth + 2);
-    alloc(B.d_height, N); alloc(B.d_hvals[0], N); alloc(B.d_hvals[1], N); alloc(B.d_heightStart, kRebuildHeightSlots);
-    B.sortTmpBytes = std::max({rebuildSortBytes<uint64_t>((uint32_t)P, 3 * kMortonBits), rebuildSortBytes<uint32_t>(std::max(I, 1u), 8),
-                               rebuildSortBytes<uint32_t>((uint32_t)N, 8)});
-    HIP_CHECK(hipMalloc(&B.d_sortTmp, std::max<size_t>(B.sortTmpBytes, 16)));
-    S.keep(B.d_sortTmp);
   }
   B.ready = true;
 }
 
-// The rebuild proper on `stream`: passes 1 - 9 (scratch only, then the read-back that decides), then - behind everything already
-// enqueued on the scene - the scatter over the live records and the refit's tables. Returns when it is all in place, the refit's
-// tables of the new topology included; on a refused box nothing of the scene has changed. Returns the maximal leaf depth (root = 1).
-uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
-  const uint32_t N = S.ds.numNodes;
-  if (!N) return 0;
-  // the current geometry and the two compact arrays on the device, the float-box scratch, the error word, room for the refit's
-  // tables: the update's allocations, made once (a rebuild reads nothing of the tables, and writes them below)
-  refitAlloc(S);
-  rebuildTables(S);
-  mi_scene::Refit& R = S.refit;
-  mi_scene::Rebuild& B = S.rebuild;
-  DeviceScene& ds = S.ds;
+// The build proper on `stream`, shared by mi_scene_rebuild (R, B, ds = the scene's own: its live records are rewritten in place) and
+// mi_scene_set_geometry* (R, B, ds = a set built aside for the new contents, which becomes the scene's afterwards): passes 1 - 9
+// (scratch only, then the read-back that decides), then the scatter over ds's records and R's tables - in place, behind everything
+// already enqueued on the scene. B.d_canon holds the P = B.numPrims > 0 canonical primitives, R the geometry, ds.numNodes = 2 P - 1.
+// Returns when it is all in place, the refit's tables of the new topology included; on a refusal (an ArgError that starts with
+// `fn`) nothing of ds's records or R's tables has been written. Returns the maximal leaf depth (root = 1).
+uint32_t rebuildPasses(mi_scene& S, mi_scene::Refit& R, mi_scene::Rebuild& B, DeviceScene& ds, hipStream_t stream, const char* fn, bool inPlace) {
+  const uint32_t N = ds.numNodes;
   const uint32_t P = B.numPrims, I = P - 1;
   RefitGeom g;
   g.verts = R.d_verts; g.spheres = R.d_spheres; g.discs = R.d_discs;
@@ -966,7 +983,7 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
   t.numPrims = P; t.child = B.d_child; t.range = B.d_range; t.parent = B.d_parent; t.swapped = B.d_swapped; t.boxes = R.d_boxes; t.index = B.d_index;
   t.height = B.d_height;
 
-  HIP_CHECK(hipMemsetAsync(R.d_err, 0, sizeof(uint32_t), stream));
+  if (inPlace) HIP_CHECK(hipMemsetAsync(R.d_err, 0, sizeof(uint32_t), stream));      // (aside: cleared in front of the table's kernel, which raises a bit of it)
   mark(0);
   const uint32_t parts = std::min((P + 255) / 256, kRebuildParts);
   hipLaunchKernelGGL(rebuild_prim_kernel, dim3(parts), dim3(256), 0, stream, P, B.d_canon, g, B.d_primBoxes, B.d_parts, R.d_err);
@@ -996,7 +1013,7 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
   mark(3);
   const uint32_t D = levelStart[kRebuildMaxDepth + 1];           // the deepest interior node
   if (I) {
-    if (D >= kRebuildMaxDepth) throw DeviceError("mi_scene_rebuild: interior depth out of range");
+    if (D >= kRebuildMaxDepth) throw DeviceError(std::string(fn) + ": interior depth out of range");
     // depths 0 .. top go to the one-workgroup kernel: from the root down, every level of at most kRefitTopThreads nodes
     uint32_t top = 0;
     while (top < D && levelStart[top + 2] - levelStart[top + 1] <= kRefitTopThreads) ++top;
@@ -1028,13 +1045,15 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
   HIP_CHECK(hipMemcpyAsync(&rootBox, R.d_boxes, sizeof rootBox, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipMemcpyAsync(heightStart, B.d_heightStart, sizeof heightStart, hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream));
-  if (err & (1u << kBoxNotFinite)) throw ArgError("mi_scene_rebuild: a node box is not finite; the scene is unchanged");
-  if (err) throw ArgError("mi_scene_rebuild: a node extent is above 65504 (Cannot compress BVH bounds into fp16 (half)); the scene is unchanged");
+  // (an index out of range comes first, as at create: its record named another vertex, the boxes are not the arrays')
+  if (err & (1u << kTriIndexOutOfRange)) throw ArgError(std::string(fn) + ": triangle vertex index out of range; the scene is unchanged");
+  if (err & (1u << kBoxNotFinite)) throw ArgError(std::string(fn) + ": a node box is not finite; the scene is unchanged");
+  if (err) throw ArgError(std::string(fn) + ": a node extent is above 65504 (Cannot compress BVH bounds into fp16 (half)); the scene is unchanged");
   const uint32_t H = heightStart[kRebuildHeightSlots - 1];
-  if (H > kRebuildMaxDepth || heightStart[H + 1] != N) throw DeviceError("mi_scene_rebuild: node heights out of range");
-  refitLevelRoom(S, H + 2);
-  // from here on the scene changes: after everything already enqueued on it, on any stream
-  for (LaunchSlot& l : S.slots) if (l.stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, l.lastWork, 0));
+  if (H > kRebuildMaxDepth || heightStart[H + 1] != N) throw DeviceError(std::string(fn) + ": node heights out of range");
+  refitLevelRoom(S, R, H + 2);
+  // from here on the scene changes: after everything already enqueued on it, on any stream (records built aside are nobody's yet)
+  if (inPlace) for (LaunchSlot& l : S.slots) if (l.stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, l.lastWork, 0));
   hipLaunchKernelGGL(rebuild_scatter_kernel, blocks(N), dim3(256), 0, stream, t, B.d_canon, g, R.d_cnodes[scratch], const_cast<GNode*>(ds.nodes),
                      const_cast<GLeaf*>(ds.leaves), const_cast<GLeafRot*>(ds.leavesRot), const_cast<float*>(ds.leafNormals), R.d_prims);
   HIP_CHECK(hipGetLastError());
@@ -1051,7 +1070,6 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
   R.levelStart.assign(heightStart, heightStart + H + 2);
   refitTopFirst(R);
   R.tables = true;
-  S.live.maxLeafDepth = I ? D + 2 : 1u;
   ds.rootInterior = 0;
   if (N > 1) {                     // the root's box as buildDeviceScene sets it (root_start)
     Box3 rb; rb.lo = mk(rootBox.lx, rootBox.ly, rootBox.lz); rb.hi = mk(rootBox.hx, rootBox.hy, rootBox.hz);
@@ -1062,15 +1080,139 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
     ds.rootLoZ = root.min_z; ds.rootHiZ = root.min_z + half_bits_to_float(root.dz);
     ds.rootInterior = 1u;
   }
-  // option auto_rebuild: the baseline is the estimate of the tree right after its last rebuild (with the option off, an update
-  // that finds it on takes the tree as it then stands)
+  return I ? D + 2 : 1u;
+}
+
+// option auto_rebuild: the baseline is the estimate of the tree right after its last rebuild or its last new contents (with the
+// option off, an update that finds it on takes the tree as it then stands)
+void rebuildBaseline(mi_scene& S, hipStream_t stream) {
   S.live.baselineValid = false;
-  if (S.opt.autoRebuild > 0.0) {
+  if (S.opt.autoRebuild > 0.0 && S.ds.numNodes) {
     double c[3];
     sceneCost(S, stream, c);
     S.live.baseline = bvh_cost_estimate(c); S.live.baselineValid = true;
   }
+}
+
+// mi_scene_rebuild's work (and option auto_rebuild's): the scene's own records rebuilt in place
+uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
+  if (!S.ds.numNodes) return 0;
+  // the current geometry and the two compact arrays on the device, the float-box scratch, the error word, room for the refit's
+  // tables: the update's allocations, made once (a rebuild reads nothing of the tables, and writes them below)
+  refitAlloc(S);
+  rebuildTables(S);
+  S.live.maxLeafDepth = rebuildPasses(S, S.refit, S.rebuild, S.ds, stream, "mi_scene_rebuild", true);
+  rebuildBaseline(S, stream);
   return S.live.maxLeafDepth;
+}
+
+// ---- new contents (mi_scene_set_geometry*, canon_kernels.hpp) ---------------------------------------------------------------------
+// The scene's contents replaced by the arrays of `g` (control plane on the host, data plane where `kind` says) and its BVH built from
+// them: everything the contents own - geometry, records, the refit's tables - is allocated aside, the canonical table is written by
+// canon_prim_kernel, rebuildPasses runs into the new set, and only after its decision the scene's pointers are swapped and the old
+// set is freed, once the work the scene had enqueued before has finished. The rebuild's scratch is reused while it is large enough.
+// On any failure the new set is freed and the scene is as it was. Returns the maximal leaf depth.
+uint32_t setGeometry(mi_scene& S, const mi_scene_geometry& g, hipStream_t stream, hipMemcpyKind kind, const char* fn) {
+  canon_check_control(g, kLeafFlag >> 5, [&](bool ok, const char* what) { if (!ok) throw ArgError(std::string(fn) + ": " + what); });
+  const uint32_t G = g.num_geometry, M = g.num_meshes;
+  std::vector<uint32_t> primStart(G + 1);
+  const uint32_t P = canon_prim_starts(g, primStart.data());
+  const uint32_t N = P ? 2 * P - 1 : 0;
+  const uint32_t numVerts = M ? g.num_verts : 0, numTris = M ? g.num_tris : 0;      // (as create keeps them)
+  if (!S.refit.d_err) { HIP_CHECK(hipMalloc(&S.refit.d_err, sizeof(uint32_t))); S.keep(S.refit.d_err); }
+  if (S.opt.rebuildTiming && !S.rebuild.ev[0]) for (hipEvent_t& e : S.rebuild.ev) HIP_CHECK(hipEventCreate(&e));
+
+  const size_t mark = S.allocations.size();      // what is kept from here on is the new set's: freed again on any failure
+  std::vector<void*> staged;                     // the control plane's device copies: freed on every way out
+  DeviceScene ds = S.ds;
+  mi_scene::Refit R;
+  mi_scene::Rebuild B = S.rebuild;
+  uint32_t depth = 0;
+  try {
+    auto alloc = [&](auto*& p, size_t count) { p = nullptr; if (count) { HIP_CHECK(hipMalloc(&p, count * sizeof(*p))); S.keep(p); } };
+    auto put = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind k) { if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, k, stream)); };
+    auto stage = [&](auto*& p, const void* src, size_t count) {
+      p = nullptr;
+      if (!count) return;
+      HIP_CHECK(hipMalloc(&p, count * sizeof(*p)));
+      staged.push_back(p);
+      put(p, src, count * sizeof(*p), hipMemcpyHostToDevice);
+    };
+    // the contents: materials, the geometry as the refit and the rebuild read it, what vertex-normal scenes look up
+    uint32_t* matIDs; mi_material* materials; uint16_t* tris; mi_vec3* normals; uint32_t* firstVertex;
+    alloc(matIDs, g.num_mat_ids); put(matIDs, g.mat_ids, (size_t)g.num_mat_ids * sizeof(uint32_t), hipMemcpyHostToDevice);
+    alloc(materials, g.num_materials); put(materials, g.materials, (size_t)g.num_materials * sizeof(mi_material), hipMemcpyHostToDevice);
+    alloc(R.d_verts, numVerts); put(R.d_verts, g.mesh_verts, (size_t)numVerts * sizeof(mi_vec3), kind);
+    alloc(R.d_spheres, g.num_spheres); put(R.d_spheres, g.spheres, (size_t)g.num_spheres * sizeof(mi_sphere), kind);
+    alloc(R.d_discs, g.num_discs); put(R.d_discs, g.discs, (size_t)g.num_discs * sizeof(mi_disc), kind);
+    alloc(tris, 3 * (size_t)numTris); put(tris, g.mesh_tris, 3 * (size_t)numTris * sizeof(uint16_t), kind);
+    alloc(normals, g.num_normals); put(normals, g.mesh_normals, (size_t)g.num_normals * sizeof(mi_vec3), kind);
+    alloc(firstVertex, G);
+    R.numVerts = numVerts; R.numNormals = g.num_normals; R.numSpheres = g.num_spheres; R.numDiscs = g.num_discs;
+    R.d_err = S.refit.d_err;
+    for (int k = 0; k < 4; ++k) R.ev[k] = S.refit.ev[k];
+    for (int k = 0; k < 3; ++k) R.ms[k] = S.refit.ms[k];
+    R.ready = true;
+    // the records and the refit's tables, one entry per node
+    GNode* nodes; GLeaf* leaves; GLeafRot* rot; float* leafNormals;
+    alloc(nodes, N); alloc(leaves, N); alloc(rot, N); alloc(leafNormals, g.num_normals ? 9 * (size_t)N : 0);
+    alloc(R.d_prims, N); alloc(R.d_order, N); alloc(R.d_boxes, N); alloc(R.d_cnodes[0], N); alloc(R.d_cnodes[1], N);
+    ds.nodes = nodes; ds.numNodes = N; ds.leaves = leaves; ds.numLeaves = N; ds.leavesRot = rot;
+    ds.matIDs = matIDs; ds.materials = materials; ds.numMaterials = g.num_materials;
+    ds.hasNormals = g.num_normals ? 1u : 0u; ds.leafNormals = leafNormals;
+    ds.meshTris = tris; ds.meshNormals = normals; ds.geomFirstVertex = firstVertex;
+    ds.rootInterior = 0;
+    ds.rootLoX = ds.rootHiX = ds.rootLoY = ds.rootHiY = ds.rootLoZ = ds.rootHiZ = 0.f;
+    B.numPrims = P; B.ready = true;
+    alloc(B.d_canon, P);                         // (the table is the new contents': a refusal must leave the scene's own as it is)
+    if (P) {
+      rebuildScratch(S, B, P);
+      uint32_t* d_primStart; mi_geom_ref* d_geometry; mi_mesh_info* d_meshInfo;
+      stage(d_primStart, primStart.data(), (size_t)G + 1); stage(d_geometry, g.geometry, G); stage(d_meshInfo, g.mesh_info, M);
+      HIP_CHECK(hipMemsetAsync(R.d_err, 0, sizeof(uint32_t), stream));
+      hipLaunchKernelGGL(canon_prim_kernel, dim3((P + 255) / 256), dim3(256), 0, stream, P, d_primStart, G, d_geometry, d_meshInfo, matIDs, tris, B.d_canon, R.d_err);
+      hipLaunchKernelGGL(canon_first_vertex_kernel, dim3((G + 255) / 256), dim3(256), 0, stream, G, d_geometry, d_meshInfo, firstVertex);
+      HIP_CHECK(hipGetLastError());
+      depth = rebuildPasses(S, R, B, ds, stream, fn, false);
+    } else {
+      // an empty scene: no node, no record; the tables of no height
+      if (G) {
+        mi_geom_ref* d_geometry; mi_mesh_info* d_meshInfo;
+        stage(d_geometry, g.geometry, G); stage(d_meshInfo, g.mesh_info, M);
+        hipLaunchKernelGGL(canon_first_vertex_kernel, dim3((G + 255) / 256), dim3(256), 0, stream, G, d_geometry, d_meshInfo, firstVertex);
+        HIP_CHECK(hipGetLastError());
+      }
+      HIP_CHECK(hipStreamSynchronize(stream));
+      R.levelStart.assign(2, 0u);
+      refitTopFirst(R);
+      R.tables = true; R.live = 0;
+    }
+    // nothing old goes before the work the scene had enqueued on it, on any stream, has finished
+    for (LaunchSlot& l : S.slots) HIP_CHECK(hipEventSynchronize(l.lastWork));
+  } catch (...) {
+    (void)hipStreamSynchronize(stream);
+    for (void* p : staged) (void)hipFree(p);
+    for (size_t k = mark; k < S.allocations.size(); ++k) (void)hipFree(S.allocations[k]);
+    S.allocations.resize(mark);
+    throw;
+  }
+  for (void* p : staged) (void)hipFree(p);
+  // the swap: the old set's buffers, then the scene's pointers
+  const DeviceScene& o = S.ds;
+  const mi_scene::Refit& oR = S.refit;
+  std::vector<const void*> old = {o.nodes, o.leaves, o.leavesRot, o.matIDs, o.materials, o.leafNormals, o.meshTris, o.meshNormals, o.geomFirstVertex,
+                                  oR.d_prims, oR.d_order, oR.d_boxes, oR.d_cnodes[0], oR.d_cnodes[1], oR.d_levelStart, oR.d_verts, oR.d_spheres, oR.d_discs,
+                                  S.rebuild.d_canon, S.live.d_cost};
+  if (B.d_primBoxes != S.rebuild.d_primBoxes) for (void* p : rebuildScratchBuffers(S.rebuild)) old.push_back(p);
+  for (const void* p : old) S.release(p);
+  S.ds = ds;
+  S.refit = std::move(R);
+  S.rebuild = B;
+  S.live.d_cost = nullptr;                       // (sized for the old node count: sceneCost allocates it again)
+  S.live.maxLeafDepth = depth;
+  ++S.live.geometrySets;
+  rebuildBaseline(S, stream);
+  return depth;
 }
 
 // Slots per pixel per launch in NIF renders: 48 B each (u, v, bgr, colour, throughput, list entry), and TWO sets of them when
@@ -1627,6 +1769,27 @@ int mi_scene_rebuild(mi_scene* scene, void* hip_stream, uint32_t* max_leaf_depth
   });
 }
 
+int mi_scene_set_geometry_device(mi_scene* scene, const mi_scene_geometry* arrays, void* hip_stream, uint32_t* max_leaf_depth) {
+  return guarded([&] {
+    if (!scene) throw ArgError("mi_scene_set_geometry_device: null scene");
+    if (!arrays) throw ArgError("mi_scene_set_geometry_device: null geometry");
+    HIP_CHECK(hipSetDevice(scene->device));
+    const uint32_t depth = setGeometry(*scene, *arrays, (hipStream_t)hip_stream, hipMemcpyDeviceToDevice, "mi_scene_set_geometry_device");
+    if (max_leaf_depth) *max_leaf_depth = depth;
+  });
+}
+
+int mi_scene_set_geometry(mi_scene* scene, const mi_scene_geometry* host_arrays, uint32_t* max_leaf_depth) {
+  return guarded([&] {
+    if (!scene) throw ArgError("mi_scene_set_geometry: null scene");
+    if (!host_arrays) throw ArgError("mi_scene_set_geometry: null geometry");
+    HIP_CHECK(hipSetDevice(scene->device));
+    // the device entry's work on the null stream, the data plane uploaded straight into the buffers the scene will own
+    const uint32_t depth = setGeometry(*scene, *host_arrays, nullptr, hipMemcpyHostToDevice, "mi_scene_set_geometry");
+    if (max_leaf_depth) *max_leaf_depth = depth;
+  });
+}
+
 int mi_scene_bvh_cost(mi_scene* scene, void* hip_stream, double out[3]) {
   if (!scene || !out) { g_err = "mi_scene_bvh_cost: null argument"; return MI_ERR_INVALID_ARG; }
   return guarded([&] {
@@ -1638,7 +1801,7 @@ int mi_scene_bvh_cost(mi_scene* scene, void* hip_stream, double out[3]) {
 int mi_get_live_stats(mi_scene* scene, uint64_t out[8]) {
   if (!scene || !out) { g_err = "mi_get_live_stats: null argument"; return MI_ERR_INVALID_ARG; }
   const mi_scene::Live& L = scene->live;
-  const uint64_t v[8] = {L.applied, L.refused, L.rebuilds, L.autoRebuilds, L.hostDerivations, L.costEvals, L.maxLeafDepth, 0};
+  const uint64_t v[8] = {L.applied, L.refused, L.rebuilds, L.autoRebuilds, L.hostDerivations, L.costEvals, L.maxLeafDepth, L.geometrySets};
   for (int i = 0; i < 8; ++i) out[i] = v[i];
   g_err.clear();
   return MI_OK;
@@ -1662,9 +1825,9 @@ int mi_scene_get_bvh(mi_scene* scene, mi_bvh_node* out, uint32_t capacity, uint3
   if (!scene || !num_nodes) { g_err = "mi_scene_get_bvh: null argument"; return MI_ERR_INVALID_ARG; }
   return guarded([&] {
     const mi_scene::Refit& R = scene->refit;
-    const uint32_t N = (uint32_t)R.nodes.size();
+    const uint32_t N = scene->ds.numNodes;
     *num_nodes = N;
-    if (!out) return;
+    if (!out || !N) return;
     if (capacity < N) throw ArgError("mi_scene_get_bvh: capacity is smaller than the scene's node count");
     if (R.live >= 0) {
       HIP_CHECK(hipSetDevice(scene->device));

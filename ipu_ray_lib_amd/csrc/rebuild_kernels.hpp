@@ -36,14 +36,15 @@
 #include "ray_math.h"
 #include "trace_kernels.hpp"
 #include "refit_kernels.hpp"
+#include "canon_prims.hpp"
 #include "../../include/mi_raylib.h"
 
 namespace mi {
 
-// A canonical primitive (32 B, built on the host at the first rebuild and kept): what its box is computed from, as RefitPrim
-// (kind REFIT_TRI: a, b, c = absolute vertex indices; REFIT_SPHERE / REFIT_DISC: a = the index), and what its leaf record carries.
-struct __attribute__((aligned(16))) RebuildPrim { uint32_t a, b, c, kind, geomID, primID, triBase, matIndex; };
-static_assert(sizeof(RebuildPrim) == 32, "RebuildPrim: 32 B");
+// A canonical primitive is a RebuildPrim (canon_prims.hpp; 32 B, built on the host at the first rebuild and kept, or on the device
+// by mi_scene_set_geometry*): what its box is computed from, as RefitPrim (kind REFIT_TRI: a, b, c = absolute vertex indices;
+// REFIT_SPHERE / REFIT_DISC: a = the index), and what its leaf record carries.
+static_assert(REFIT_TRI == 0 && REFIT_SPHERE == 1 && REFIT_DISC == 2, "a RebuildPrim's kind is its geometry's type");
 
 // Node numbering until the scatter: interior nodes 0 .. P - 2 (Karras' indices, the root is 0), the leaf at sorted position j is
 // node P - 1 + j. One primitive: node 0 is its leaf.
