@@ -78,6 +78,20 @@ typedef struct {
 
 enum { MI_QUERY_CLOSEST = 0, MI_QUERY_ANY = 1 };
 
+/* A point query (mi_point_query / mi_point_query_device) and its MI_POINT_CLOSEST result. No reference POD: Embree's
+ * rtcPointQuery asks the same of its BVH. */
+typedef struct { float x, y, z, radius; } mi_point;            /* 16 B */
+typedef struct {
+  float    dist;       /* sqrtf of the winning squared distance; == radius as given when nothing was found              */
+  uint32_t prim_id;    /* as mi_query_hit; MI_INVALID_PRIM when nothing was found                                        */
+  uint16_t geom_id;    /* MI_INVALID_GEOM when nothing was found                                                         */
+  uint16_t flags;      /* MI_FLAG_ESCAPED when nothing was found, else 0                                                 */
+  mi_vec3  point;      /* the closest point on the primitive; 0 when nothing was found                                   */
+  float    b1, b2;     /* triangle: barycentrics v, w of `point` (point = a + ab v + ac w); 0 otherwise                  */
+} mi_point_hit;                                                  /* 32 B */
+
+enum { MI_POINT_CLOSEST = 0, MI_POINT_WITHIN = 1 };
+
 typedef struct {
   float min_x, min_y, min_z;
   uint32_t prim_or_second_child;   /* leaf: primID; interior: index of second child (first child = this+1) */
@@ -183,6 +197,44 @@ int mi_render_device(mi_scene* scene, int mode, void* d_rays, size_t n, void* hi
  * query_tune, and the arithmetic options double_fallback and fast, as for renders. */
 int mi_query_device(mi_scene* scene, int kind, const void* d_rays, void* d_out, size_t n, void* hip_stream);
 int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n);
+
+/* Point queries: for each of n caller-supplied points with its own radius, the primitive of the scene's CURRENT BVH nearest to the
+ * point and strictly within the radius, how far away it is and where on it (MI_POINT_CLOSEST, Embree's rtcPointQuery), or only
+ * whether there is one (MI_POINT_WITHIN). Distances are to the SURFACE, as rays hit surfaces: a point inside a sphere is its
+ * distance from the shell away.
+ * Device entry: d_points = n mi_point, d_out = n mi_point_hit (CLOSEST) or n uint8_t, 1 = a primitive lies strictly within the
+ * radius (WITHIN), DEVICE memory. Asynchronous on hip_stream (a hipStream_t as void*; NULL = the null stream); the scene waits for
+ * it when destroyed, and mi_scene_update*, mi_scene_rebuild and mi_scene_set_geometry* wait for it before they overwrite a record:
+ * a point query enqueued before one of them sees the old geometry.
+ * Host entry: the same on HOST buffers, synchronous (copies + the device entry), in batches of mi_scene_set_ray_batch points.
+ * n == 0 is a no-op. MI_ERR_INVALID_ARG, before any device work: a null scene or buffer, an unknown kind, a points buffer or a
+ * CLOSEST out buffer that is not 16-byte aligned (the bytes of WITHIN need no alignment), or more points in one launch
+ * (mi_point_query: in one batch) than the 32-bit work index allows (0xFFBFFFFF).
+ * Arithmetic: binary32, one rounding per operation in the order written below, no contraction, correctly rounded divide and sqrt;
+ * a dot product is (x x' + y y') + z z'. One definition (ipu_ray_lib_amd/csrc/point_math.hpp) serves the kernel and the host twin
+ * mi_point_query_host (mi_scene_host.h), which returns the same bytes.
+ * The walk is the stackless preorder walk of the ray kernels - first child first, whatever the point - with a distance test in place
+ * of the slab test. best = radius * radius. At node nd: ex = fmaxf(fmaxf(nd.min.x - p.x, p.x - nd.max.x), 0), ey and ez alike,
+ * db = (ex ex + ey ey) + ez ez; the node is entered when db < best, else passed. At a leaf so reached the primitive's closest
+ * point q is evaluated, d2 = dot(p - q, p - q), and the leaf is accepted when d2 < best: strictly, so of equal distances the first
+ * leaf in preorder wins and a NaN d2 is never accepted. CLOSEST sets best = d2 and walks on; WITHIN stops at the first accept.
+ * Written without a walk, as "nothing found": a point with a coordinate that is not finite, a radius that is NaN or negative, an
+ * empty scene. radius = +inf is legal (a box or primitive whose squared distance overflows to +inf is then never reached).
+ * Triangle (a, b, c): Ericson, Real-Time Collision Detection 5.1.5. ab = b - a, ac = c - a; d1 = ab.(p - a), d2 = ac.(p - a),
+ * d3 = ab.(p - b), d4 = ac.(p - b), d5 = ab.(p - c), d6 = ac.(p - c); vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4.
+ * Regions in this order, with the barycentrics (v, w): A: d1 <= 0 && d2 <= 0: (0, 0). B: d3 >= 0 && d4 <= d3: (1, 0).
+ * AB: vc <= 0 && d1 >= 0 && d3 <= 0: (d1 / (d1 - d3), 0). C: d6 >= 0 && d5 <= d6: (0, 1). AC: vb <= 0 && d2 >= 0 && d6 <= 0:
+ * (0, d2 / (d2 - d6)). BC: va <= 0 && d4 - d3 >= 0 && d5 - d6 >= 0: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), (1 - w, w).
+ * Face otherwise: den = 1 / ((va + vb) + vc), (vb den, vc den). q = (a + ab v) + ac w. A triangle collapsed to a point falls in
+ * region A; nothing is special-cased.
+ * Sphere (centre c): v = p - c, len = sqrtf(v.v); len > 0: q = c + v (radius / len), otherwise q = (c.x + radius, c.y, c.z).
+ * Disc (centre c, normal n as given, as the ray test takes it, r2 = r r, r' = sqrtf(r2)): v = p - c, h = v.n, q0 = p - n h,
+ * u = q0 - c, uu = u.u; uu <= r2: q = q0, otherwise q = c + u (r' / sqrtf(uu)).
+ * Counters (mi_get_counters): nothing is added to casts or paths; under option full_stats the box tests are added to "nodes
+ * visited" and the primitive evaluations to "leaf tests". Options: double_fallback, fast, query_kernel and query_tune do NOT apply
+ * (there is one kernel and one arithmetic). Groups: call it on a replica's scene (mi_group_scene), as for ray queries. */
+int mi_point_query_device(mi_scene* scene, int kind, const void* d_points, void* d_out, size_t n, void* hip_stream);
+int mi_point_query(mi_scene* scene, int kind, const mi_point* points, void* out, size_t n);
 
 /* Geometry updates: new positions for the primitives of a live scene, the topology kept - triangles, geometry list, materials and
  * the BVH's shape - and every BVH box recomputed on the device (a refit: Embree's RTC_BUILD_QUALITY_REFIT commit, OptiX's

@@ -99,6 +99,16 @@ int mi_bvh_cost_compact(const mi_bvh_node* nodes, uint32_t n, double out[3]);
 int mi_bvh_cost_compact_block(const mi_bvh_node* nodes, uint32_t n, uint32_t block, double out[3]);
 double mi_bvh_cost_estimate(const double cost[3]);
 
+/* Point queries on the host: the twin of mi_point_query / mi_point_query_device (mi_raylib.h, where the contract is written), for
+ * the same `kind`, points and out (n mi_point_hit for MI_POINT_CLOSEST, n uint8_t for MI_POINT_WITHIN; no alignment asked). It walks
+ * desc->bvh_nodes - compact nodes: max = min + (float)extent, one rounded add; first child first - in the device's order, resolves
+ * every leaf's primitive from desc's arrays as mi_scene_create resolves it, and evaluates boxes and primitives through the code the
+ * kernel runs (ipu_ray_lib_amd/csrc/point_math.hpp): it returns the bytes the device returns. visits (may be NULL) receives
+ * {box tests, primitive evaluations} summed over the n points: what the device adds to "nodes visited" and "leaf tests" under option
+ * full_stats. MI_ERR_INVALID_ARG: a null desc, an unknown kind, a null buffer with n > 0, nodes that are not a depth-first BVH2, a
+ * leaf whose geometry, primitive or vertex index is out of range. */
+int mi_point_query_host(const mi_scene_desc* desc, int kind, const mi_point* points, void* out, size_t n, uint64_t visits[2]);
+
 /* initPerspectiveRayStream(rayStream, image, data, nullptr) + zeroRgb: window_w*window_h rays in
  * row-major window order, origin 0, un-jittered pinhole directions, u=row, v=col. */
 int mi_init_ray_stream(const mi_scene_desc* desc, mi_trace_result* rays, size_t capacity);

@@ -43,13 +43,20 @@ DISC = np.dtype([("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("r", "<f4"), ("cx
 QUERY_HIT = np.dtype([("t", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("normal", VEC3),
                       ("b1", "<f4"), ("b2", "<f4")])
 
+# mi_point / mi_point_hit: a point query and its closest-primitive result (IpuScene.closest_points / point_query_device)
+POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("radius", "<f4")])
+POINT_HIT = np.dtype([("dist", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("point", VEC3),
+                      ("b1", "<f4"), ("b2", "<f4")])
+
 assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
+assert POINT.itemsize == 16 and POINT_HIT.itemsize == 32
 assert BVH_NODE.itemsize == 24 and MATERIAL.itemsize == 36 and MESH_INFO.itemsize == 16 and GEOM_REF.itemsize == 4
 
 FLAG_ERROR, FLAG_ESCAPED = 1, 2
 INVALID_GEOM, INVALID_PRIM = 0xFFFF, 0xFFFFFFFF
 MODE_SHADOW_TRACE, MODE_PATH_TRACE = 0, 1
 QUERY_CLOSEST, QUERY_ANY = 0, 1
+POINT_CLOSEST, POINT_WITHIN = 0, 1
 
 MI_OK = 0
 
@@ -170,6 +177,7 @@ def host_lib() -> C.CDLL:
         lib.mi_refit_compact_bvh.argtypes = [C.POINTER(SceneDesc), C.c_void_p]
         lib.mi_build_lbvh_compact.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.mi_canonical_prims.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.mi_point_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_bvh_cost_compact.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_compact_block.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_estimate.argtypes = [C.POINTER(C.c_double)]
@@ -247,6 +255,8 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_scene_bvh_cost.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         lib.mi_get_live_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.mi_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_point_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_point_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
         lib.mi_group_destroy.argtypes = [C.c_void_p]
         lib.mi_group_destroy.restype = None
@@ -442,6 +452,19 @@ def bvh_cost(nodes: np.ndarray, block: int | None = None) -> dict:
     else:
         _check_host(host_lib().mi_bvh_cost_compact_block(nodes.ctypes.data, nodes.size, block, out))
     return _cost_dict(out)
+
+
+def point_query_host(desc: SceneDesc, kind: int, points: np.ndarray):
+    """mi_point_query_host: the host twin of IpuScene.closest_points / .within on desc's arrays and nodes - the same bytes.
+    Returns (out, visits): a POINT_HIT array (POINT_CLOSEST) or a bool array (POINT_WITHIN), and {"box_tests", "prim_evals"}
+    summed over the points (what the device counts as nodes visited / leaf tests under option full_stats)."""
+    assert points.dtype == POINT and points.ndim == 1
+    src = np.ascontiguousarray(points)
+    out = np.zeros(src.size, np.uint8) if kind == POINT_WITHIN else np.zeros(src.size, POINT_HIT)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_point_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
+                                               out.ctypes.data if src.size else None, src.size, visits))
+    return (out.view(np.bool_) if kind == POINT_WITHIN else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
 
 
 def _geometry_array(a, dtype, width):
@@ -654,6 +677,49 @@ class IpuScene:
         halves = raw.view(torch.int16)
         return {"t": raw[:, 0], "prim_id": words[:, 1], "geom_id": halves[:, 4].to(torch.int32),
                 "normal": raw[:, 3:6], "bary": raw[:, 6:8]}
+
+    # -- point queries (mi_point_query / mi_point_query_device): the nearest primitive within each point's radius -----------------
+    def _point_query_host(self, kind: int, points: np.ndarray, out: np.ndarray) -> np.ndarray:
+        assert points.dtype == POINT and points.ndim == 1
+        src = points if (points.flags["C_CONTIGUOUS"] and points.ctypes.data % 16 == 0) else _aligned_copy(points)
+        self._check(self._lib.mi_point_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
+        return out
+
+    def closest_points(self, points: np.ndarray) -> np.ndarray:
+        """The nearest primitive strictly within each point's radius (a POINT array, host memory): a POINT_HIT array - distance,
+        ids, the closest point on the primitive, a triangle's barycentrics. Synchronous; batched by setRayBatch."""
+        return self._point_query_host(POINT_CLOSEST, points, aligned_bytes(points.size * POINT_HIT.itemsize).view(POINT_HIT))
+
+    def within(self, points: np.ndarray) -> np.ndarray:
+        """Whether some primitive lies strictly within each point's radius (a POINT array, host memory): a bool array."""
+        return self._point_query_host(POINT_WITHIN, points, aligned_bytes(points.size)).view(np.bool_)
+
+    def point_query_device(self, kind: int, d_points: int, d_out: int, n: int, stream: int = 0):
+        """mi_point_query_device on device pointers (n POINT records in, n POINT_HIT records or n bytes out), asynchronous on `stream`."""
+        self._check(self._lib.mi_point_query_device(self._h, int(kind), C.c_void_p(d_points), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
+
+    def nearest(self, points, radius=float("inf"), within: bool = False) -> dict:
+        """Torch convenience over mi_point_query_device: a float32 device tensor of shape [N, 3] (radius: a number or an [N]
+        tensor), enqueued on torch.cuda.current_stream(). Returns device tensors: {"dist" [N], "prim_id" [N] int32, "geom_id" [N]
+        int32 (-1 when nothing was found, for both), "point" [N, 3], "bary" [N, 2] (b1, b2)}; within=True: {"within" [N] bool}."""
+        import torch
+        p = points.to(torch.float32)
+        if p.ndim != 2 or p.shape[1] != 3 or not p.is_cuda:
+            raise ValueError("nearest: points must be an [N, 3] tensor on a GPU")
+        n = p.shape[0]
+        r = torch.as_tensor(radius, dtype=torch.float32, device=p.device).expand(n).reshape(n, 1)
+        pts = torch.cat([p, r], dim=1).contiguous()      # [N, 4] = n mi_point
+        stream = torch.cuda.current_stream(p.device).cuda_stream
+        if within:
+            out = torch.empty(n, dtype=torch.uint8, device=p.device)
+            self.point_query_device(POINT_WITHIN, pts.data_ptr(), out.data_ptr(), n, stream)
+            return {"within": out.bool()}
+        raw = torch.empty((n, 8), dtype=torch.float32, device=p.device)
+        self.point_query_device(POINT_CLOSEST, pts.data_ptr(), raw.data_ptr(), n, stream)
+        words = raw.view(torch.int32)
+        halves = raw.view(torch.int16)
+        return {"dist": raw[:, 0], "prim_id": words[:, 1], "geom_id": halves[:, 4].to(torch.int32),
+                "point": raw[:, 3:6], "bary": raw[:, 6:8]}
 
     # -- geometry updates (mi_scene_update*): new primitive positions, the BVH refit on the device ------------------------------------
     def update_geometry(self, vertices=None, normals=None, spheres=None, discs=None) -> "IpuScene":

@@ -159,6 +159,14 @@ int mi_build_lbvh_compact(const mi_scene_desc* desc, mi_bvh_node* out, uint32_t*
   });
 }
 
+// Point queries: the host twin of mi_point_query / mi_point_query_device (point_query_host.cpp)
+int mi_point_query_host(const mi_scene_desc* desc, int kind, const mi_point* points, void* out, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_point_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (kind != MI_POINT_CLOSEST && kind != MI_POINT_WITHIN) { g_err = "mi_point_query_host: unknown query kind"; return MI_ERR_INVALID_ARG; }
+  if (n && (!points || !out)) { g_err = "mi_point_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { pointQueryHost(*desc, kind, points, out, n, visits); });
+}
+
 // The canonical primitive table of desc's arrays: the host twin of canon_prim_kernel (canon_kernels.hpp, mi_scene_set_geometry*) -
 // the same prefix, the same search and record per canonical index (canon_prims.hpp), the same checks with mi_scene_create's words
 int mi_canonical_prims(const mi_scene_desc* desc, void* out, uint32_t capacity, uint32_t* count) {

@@ -99,6 +99,8 @@ void buildCompactBvh(const std::vector<BuildPrim>& prims, std::vector<mi_bvh_nod
 void refitCompactBvh(const mi_scene_desc& desc, mi_bvh_node* out);
 // lbvh.cpp: the host twin of mi_scene_rebuild
 void buildLbvhCompact(const mi_scene_desc& desc, std::vector<mi_bvh_node>& nodes, uint32_t& maxDepth);
+// point_query_host.cpp: the host twin of mi_point_query (visits: {box tests, primitive evaluations}, may be null)
+void pointQueryHost(const mi_scene_desc& desc, int kind, const mi_point* points, void* out, size_t n, uint64_t* visits);
 
 // glb_reader.cpp: meshes of a glTF-binary file with node transforms baked in, file order kept
 std::vector<TriMesh> loadGlbMeshes(const std::string& path, bool loadNormals);

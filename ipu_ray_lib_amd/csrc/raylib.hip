@@ -17,6 +17,7 @@
 #include "trace_kernels.hpp"
 #include "trace_wavefront.hpp"
 #include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
+#include "point_kernels.hpp"         // point queries: the nearest primitive of each given point (mi_point_query / mi_point_query_device)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
 #include "canon_kernels.hpp"         // new contents for a live scene: the canonical primitive table on the device (mi_scene_set_geometry*)
@@ -54,6 +55,10 @@ static_assert(offsetof(mi_hit_record, prim_id) == 32 && offsetof(mi_hit_record, 
 static_assert(sizeof(mi_query_hit) == 32 && offsetof(mi_query_hit, prim_id) == 4 && offsetof(mi_query_hit, geom_id) == 8 &&
               offsetof(mi_query_hit, flags) == 10 && offsetof(mi_query_hit, normal) == 12 && offsetof(mi_query_hit, b1) == 24 &&
               offsetof(mi_query_hit, b2) == 28, "mi_query_hit layout");
+static_assert(sizeof(mi_point) == 16 && offsetof(mi_point, radius) == 12, "mi_point layout");
+static_assert(sizeof(mi_point_hit) == 32 && offsetof(mi_point_hit, prim_id) == 4 && offsetof(mi_point_hit, geom_id) == 8 &&
+              offsetof(mi_point_hit, flags) == 10 && offsetof(mi_point_hit, point) == 12 && offsetof(mi_point_hit, b1) == 24 &&
+              offsetof(mi_point_hit, b2) == 28, "mi_point_hit layout");
 
 namespace {
 
@@ -1646,6 +1651,38 @@ bool queryArgsBad(const char* fn, const mi_scene* scene, int kind, const void* r
   return true;
 }
 
+// Point queries (mi_point_query_device): the nearest primitive within each point's radius (MI_POINT_CLOSEST, n mi_point_hit) or
+// whether there is one (MI_POINT_WITHIN, n bytes), one thread per point (point_kernels.hpp). full_stats picks the instrumented
+// build; the arithmetic options and the query-kernel options do not apply. Records the slot's lastWork event, as launchQuery does:
+// ~mi_scene waits for the launch, and so do update, rebuild and set-geometry before they overwrite a record.
+void launchPointQuery(mi_scene& S, int kind, const mi_point* d_points, void* d_out, size_t n, hipStream_t stream) {
+  if (n == 0) return;
+  if (n > kMaxWorkItems) throw ArgError("mi_point_query: more points than one launch indexes (kMaxWorkItems)");
+  const uint32_t cnt = (uint32_t)n;
+  LaunchSlot& slot = S.slotFor(stream);
+  const DeviceScene dsv = S.ds;
+  const dim3 block(256), grid((cnt + 255) / 256);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_points, d_out, cnt); };
+  if (kind == MI_POINT_WITHIN) { if (S.opt.fullStats) go(point_query_kernel<true, true>); else go(point_query_kernel<true, false>); }
+  else { if (S.opt.fullStats) go(point_query_kernel<false, true>); else go(point_query_kernel<false, false>); }
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
+}
+
+// Argument rules shared by the two point-query entries; touches neither the scene nor a device.
+bool pointArgsBad(const char* fn, const mi_scene* scene, int kind, const void* points, const void* out, size_t n, size_t limit) {
+  const char* why = nullptr;
+  if (!scene) why = "null scene";
+  else if (kind != MI_POINT_CLOSEST && kind != MI_POINT_WITHIN) why = "unknown query kind";
+  else if (n == 0) return false;
+  else if (!points || !out) why = "null buffer";
+  else if ((uintptr_t)points % 16 || (kind == MI_POINT_CLOSEST && (uintptr_t)out % 16)) why = "buffers must be 16-byte aligned";
+  else if (n > limit) why = "more points than one launch indexes (kMaxWorkItems)";
+  if (!why) return false;
+  g_err = std::string(fn) + ": " + why;
+  return true;
+}
+
 // One wave that samples the work counter of `hip_stream`'s persistent launches `n` times, `period_ticks` (100-MHz ticks) apart, into
 // d_samples as pairs {s_memrealtime, counter}: how fast a launch hands its work units out over its life - the ramp at its start, the
 // moment the queue runs empty, the drain behind it (tools/launch_progress.py). It runs on a stream of the scene's own beside the launch it
@@ -1948,6 +1985,52 @@ int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n)
         const size_t first = b * batch, cnt = std::min(batch, n - first);
         HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], rays + first, cnt * sizeof(mi_ray), hipMemcpyHostToDevice, st));
         launchQuery(*scene, kind, static_cast<const mi_ray*>(scene->d_qRays[i]), scene->d_qOut[i], cnt, st);
+        HIP_CHECK(hipMemcpyAsync(static_cast<char*>(out) + first * outSize, scene->d_qOut[i], cnt * outSize, hipMemcpyDeviceToHost, st));
+      }
+      for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
+    } catch (...) { (void)hipDeviceSynchronize(); throw; }
+  });
+}
+
+int mi_point_query_device(mi_scene* scene, int kind, const void* d_points, void* d_out, size_t n, void* hip_stream) {
+  if (pointArgsBad("mi_point_query_device", scene, kind, d_points, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    launchPointQuery(*scene, kind, static_cast<const mi_point*>(d_points), d_out, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_point_query(mi_scene* scene, int kind, const mi_point* points, void* out, size_t n) {
+  if (pointArgsBad("mi_point_query", scene, kind, points, out, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  // (the host stream is cut into batches of mi_scene_set_ray_batch points: the work-index limit applies per batch)
+  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
+  if (batch > kMaxWorkItems) { g_err = "mi_point_query: more points per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    // mi_query's pipeline and its buffers (a slot holds `batch` 32-byte records in and out: room for 16-byte points and either result)
+    const size_t outSize = kind == MI_POINT_WITHIN ? 1 : sizeof(mi_point_hit);
+    const size_t numBatches = (n + batch - 1) / batch;
+    const int slots = numBatches > 1 ? 2 : 1;
+    try {
+      for (int i = 0; i < slots; ++i) {
+        if (scene->qCap[i] < batch) {
+          if (scene->d_qRays[i] || scene->d_qOut[i]) HIP_CHECK(hipDeviceSynchronize());
+          for (void** p : {&scene->d_qRays[i], &scene->d_qOut[i]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+          scene->qCap[i] = 0;
+          HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * sizeof(mi_ray)));
+          HIP_CHECK(hipMalloc(&scene->d_qOut[i], batch * sizeof(mi_query_hit)));
+          scene->qCap[i] = batch;
+        }
+        if (!scene->pipeStream[i]) HIP_CHECK(hipStreamCreateWithFlags(&scene->pipeStream[i], hipStreamNonBlocking));
+      }
+      for (size_t b = 0; b < numBatches; ++b) {
+        const int i = (int)(b % slots);
+        hipStream_t st = scene->pipeStream[i];
+        const size_t first = b * batch, cnt = std::min(batch, n - first);
+        HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], points + first, cnt * sizeof(mi_point), hipMemcpyHostToDevice, st));
+        launchPointQuery(*scene, kind, static_cast<const mi_point*>(scene->d_qRays[i]), scene->d_qOut[i], cnt, st);
         HIP_CHECK(hipMemcpyAsync(static_cast<char*>(out) + first * outSize, scene->d_qOut[i], cnt * outSize, hipMemcpyDeviceToHost, st));
       }
       for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));

@@ -1,11 +1,11 @@
 """Ray batches for ray queries, built on the host with numpy alone (no oracle): a scene's primary camera rays, cosine-distributed
 diffuse bounce rays from their first hits, and shadow rays from those hits to a point light. tools/bench_query.py measures the
-query kernels on them; tests/test_query_gpu.py checks them at scale."""
+query kernels on them; tests/test_query_gpu.py checks them at scale. And point batches for point queries (make_points: tools/bench_point_query.py)."""
 from __future__ import annotations
 
 import numpy as np
 
-from . import RAY, INVALID_PRIM
+from . import RAY, POINT, POINT_HIT, INVALID_PRIM      # noqa: F401  (the record dtypes of ray and point queries, side by side)
 
 RAY_EPSILON = np.float32(5.9604644775390625e-08 * 1500.0)       # ray_math.h kRayEpsilon (precision_utils.hpp)
 LIGHT = np.array([18.0, 257.0, -1060.0], np.float32)            # the reference's shadow-trace light (trace.cpp:247)
@@ -25,6 +25,15 @@ def make_rays(origins: np.ndarray, directions: np.ndarray, t_min=0.0, t_max=np.i
     r["tMin"] = t_min
     r["tMax"] = t_max
     return r
+
+
+def make_points(positions: np.ndarray, radius=np.inf) -> np.ndarray:
+    """A POINT array from [N, 3] positions and a radius (a number or [N])."""
+    p = np.zeros(len(positions), POINT)
+    for k, c in enumerate("xyz"):
+        p[c] = positions[:, k]
+    p["radius"] = radius
+    return p
 
 
 def primary_rays(host_scene) -> np.ndarray:
