@@ -236,6 +236,68 @@ int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n)
 int mi_point_query_device(mi_scene* scene, int kind, const void* d_points, void* d_out, size_t n, void* hip_stream);
 int mi_point_query(mi_scene* scene, int kind, const mi_point* points, void* out, size_t n);
 
+/* Crossing counts: for each of n caller-supplied rays, how many surfaces of the scene's CURRENT BVH it crosses with t_min < t < t_max
+ * (Open3D's count_intersections). A closest-hit cast prunes what lies behind its hit and cannot say this; callers of mi_query would
+ * need one round trip per surface layer.
+ * Device entry: d_rays = n mi_ray, d_counts = n uint32_t, DEVICE memory. Asynchronous on hip_stream (a hipStream_t as void*; NULL =
+ * the null stream); ordering, destruction, groups and batches are those of mi_query_device / mi_query: the scene waits for it when
+ * destroyed, updates, rebuilds and set-geometry wait for it before they overwrite a record, and on a group it is called on a
+ * replica's scene (mi_group_scene).
+ * Host entry: the same on HOST buffers, synchronous (copies + the device entry), in batches of mi_scene_set_ray_batch rays.
+ * n == 0 is a no-op; an empty scene gives zeros. MI_ERR_INVALID_ARG, before any device work and without reading the scene: a null
+ * scene or buffer, rays that are not 16-byte aligned, counts that are not 4-byte aligned, or more rays in one launch
+ * (mi_count_query: in one batch) than the 32-bit work index allows (0xFFBFFFFF).
+ * The walk is the stackless preorder walk of the ray queries with their box test (CompactBVH2Node.cpp:5-22, the literal per-axis
+ * sequence) over the FIXED interval [t_min, t_max]: it never shrinks, so the leaves visited are a function of the ray and the nodes
+ * alone, and the count - a sum over them - does not depend on the visit order. A visited leaf adds
+ *   triangle, disc: 1 when the ray query's primitive test accepts it against t_max: t > t_min && t < t_max (and t > 0 && t < inf for
+ *     a triangle, Mesh.hpp:93);
+ *   sphere (centre c, radius2 = radius radius): 0, 1 or 2, both roots - the reference's sphere test returns one t per sphere and
+ *     misses when the centre lies behind the origin, even for an origin inside the sphere. In binary32, one rounding per operation,
+ *     a dot product (x x' + y y') + z z' (ipu_ray_lib_amd/csrc/cross_math.hpp; mi_sphere_crossings_host in mi_scene_host.h runs it
+ *     on the host): f = c - o; dd = d.d; tca = (f.d) / dd; l = f - d tca; l2 = l.l; !(l2 <= radius2): 0; otherwise
+ *     td = sqrtf((radius2 - l2) / dd), t0 = tca - td, t1 = tca + td, and the count is (t0 > t_min && t0 < t_max) + (t1 > t_min &&
+ *     t1 < t_max). No tca < 0 early-out; right for any length of d; a tangent ray (td == 0) adds 0 or 2, so a parity survives it; a
+ *     NaN never counts.
+ * On a scene without spheres count > 0 holds exactly when MI_QUERY_ANY answers 1 for the same ray (same boxes visited until the
+ * first accept, same acceptance).
+ * Options: double_fallback applies, with its triangle test (it matters most exactly here, where an edge function is zero); fast,
+ * query_kernel and query_tune do NOT apply (one kernel, the exact arithmetic). Counters (mi_get_counters): casts += n; under
+ * full_stats the box tests and primitive tests are added as for ray queries (double_fallback has no instrumented build and takes
+ * precedence, as for ray queries). */
+int mi_count_query_device(mi_scene* scene, const void* d_rays, uint32_t* d_counts, size_t n, void* hip_stream);
+int mi_count_query(mi_scene* scene, const mi_ray* rays, uint32_t* counts, size_t n);
+
+/* Inside tests and signed distance: whether each of n caller-supplied points lies inside the scene's surfaces (MI_SIGN_INSIDE,
+ * Open3D's compute_occupancy, trimesh's contains) and its distance from them with that sign (MI_SIGN_DISTANCE, Open3D's
+ * compute_signed_distance).
+ * A point is inside when the crossing count (above) of the ray origin = the point, direction = dir, t_min = 0, t_max = +inf is odd:
+ * the walk and the arithmetic of mi_count_query, option double_fallback likewise.
+ * dir: a HOST pointer to three floats, read before the call returns; NULL = {1.0f, 0.70710678f, 0.57735027f}. A component that is
+ * zero, NaN or infinite is refused: the reference's triangle test shears by the SMALLEST signed direction component
+ * (Primitives.cpp:5-22), so an axis direction such as (1, 0, 0) divides by zero there and misses every triangle. The default's
+ * components are 1, 1/sqrt 2 and 1/sqrt 3: rays from grid points do not run through the edges and face diagonals of axis-aligned boxes,
+ * as those of a direction such as (1, 0.618034, 0.381966), whose components sum to 1, do. A caller who wants a majority vote calls three times with three directions.
+ * MI_SIGN_INSIDE: d_out = n uint8_t, 1 = inside. The radius is ignored. A point with a coordinate that is not finite is not walked
+ * and gets 0.
+ * MI_SIGN_DISTANCE: d_out = n mi_point_hit, 16-byte aligned: byte for byte what MI_POINT_CLOSEST writes for the same point and
+ * radius, except where the point is inside: there the sign bit of dist is set and flags |= MI_FLAG_INSIDE. When nothing lies within
+ * the radius dist is the radius as given with MI_FLAG_ESCAPED, and still negative with MI_FLAG_INSIDE for a point inside: a
+ * narrow-band caller gets -radius. A query a point query does not walk (a coordinate that is not finite, a NaN or negative radius)
+ * is not walked for crossings either: its record is MI_POINT_CLOSEST's "nothing found", unchanged.
+ * Meaning: only closed surfaces have an inside. A disc or an open mesh counts as one crossing and means what the caller makes of
+ * it; a point closer to a surface than the triangle test's own error bound (t <= deltaT, Mesh.cpp) can fall on either side.
+ * Form: MI_SIGN_DISTANCE is two launches on hip_stream - the point query, then the crossing walk, which changes the records in
+ * place -; MI_SIGN_INSIDE is the walk alone. Ordering, destruction, groups, batches and the argument rules are those of
+ * mi_point_query_device / mi_point_query (an unknown kind: "unknown sign kind"; the bytes of MI_SIGN_INSIDE need no alignment); a
+ * refused dir is MI_ERR_INVALID_ARG before any device work, too.
+ * Counters: the point query counts as mi_point_query does; the walk adds the points it walked to casts and, under full_stats, its
+ * box tests and primitive tests to "nodes visited" and "leaf tests". */
+#define MI_FLAG_INSIDE ((uint16_t)4)
+enum { MI_SIGN_INSIDE = 0, MI_SIGN_DISTANCE = 1 };
+int mi_point_sign_device(mi_scene* scene, int kind, const void* d_points, void* d_out, const float dir[3], size_t n, void* hip_stream);
+int mi_point_sign(mi_scene* scene, int kind, const mi_point* points, void* out, const float dir[3], size_t n);
+
 /* Geometry updates: new positions for the primitives of a live scene, the topology kept - triangles, geometry list, materials and
  * the BVH's shape - and every BVH box recomputed on the device (a refit: Embree's RTC_BUILD_QUALITY_REFIT commit, OptiX's
  * OPTIX_BUILD_OPERATION_UPDATE). Any pointer may be NULL = keep; a non-NULL array must have exactly the scene's count (a NULL array

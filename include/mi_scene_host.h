@@ -109,6 +109,13 @@ double mi_bvh_cost_estimate(const double cost[3]);
  * leaf whose geometry, primitive or vertex index is out of range. */
 int mi_point_query_host(const mi_scene_desc* desc, int kind, const mi_point* points, void* out, size_t n, uint64_t visits[2]);
 
+/* Sphere crossings on the host: how often the ray origin + t direction, t_min < t < t_max, crosses the shell of the sphere (centre,
+ * radius2 = the squared radius) - 0, 1 or 2 -, from the definition the crossing-count kernels run (mi_count_query / mi_point_sign,
+ * mi_raylib.h, where the formula is written; ipu_ray_lib_amd/csrc/cross_math.hpp). The triangle and disc tests of a crossing count
+ * are the reference's and are checked against the CPU oracle; this is the part with no reference counterpart. A null pointer gives 0. */
+uint32_t mi_sphere_crossings_host(const float centre[3], float radius2, const float origin[3], const float direction[3],
+                                  float t_min, float t_max);
+
 /* initPerspectiveRayStream(rayStream, image, data, nullptr) + zeroRgb: window_w*window_h rays in
  * row-major window order, origin 0, un-jittered pinhole directions, u=row, v=col. */
 int mi_init_ray_stream(const mi_scene_desc* desc, mi_trace_result* rays, size_t capacity);

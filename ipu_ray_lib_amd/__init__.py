@@ -52,11 +52,14 @@ assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32
 assert POINT.itemsize == 16 and POINT_HIT.itemsize == 32
 assert BVH_NODE.itemsize == 24 and MATERIAL.itemsize == 36 and MESH_INFO.itemsize == 16 and GEOM_REF.itemsize == 4
 
-FLAG_ERROR, FLAG_ESCAPED = 1, 2
+FLAG_ERROR, FLAG_ESCAPED, FLAG_INSIDE = 1, 2, 4
 INVALID_GEOM, INVALID_PRIM = 0xFFFF, 0xFFFFFFFF
 MODE_SHADOW_TRACE, MODE_PATH_TRACE = 0, 1
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 POINT_CLOSEST, POINT_WITHIN = 0, 1
+SIGN_INSIDE, SIGN_DISTANCE = 0, 1
+# the ray direction of an inside test when none is given (mi_point_sign: no zero component, off the diagonals of axis-aligned boxes)
+DEFAULT_INSIDE_DIR = (1.0, 0.70710678, 0.57735027)
 
 MI_OK = 0
 
@@ -178,6 +181,8 @@ def host_lib() -> C.CDLL:
         lib.mi_build_lbvh_compact.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.mi_canonical_prims.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.mi_point_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
+        lib.mi_sphere_crossings_host.restype = C.c_uint32
         lib.mi_bvh_cost_compact.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_compact_block.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_estimate.argtypes = [C.POINTER(C.c_double)]
@@ -257,6 +262,10 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_point_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
         lib.mi_point_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_count_query.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_count_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_point_sign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t]
+        lib.mi_point_sign_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
         lib.mi_group_destroy.argtypes = [C.c_void_p]
         lib.mi_group_destroy.restype = None
@@ -465,6 +474,15 @@ def point_query_host(desc: SceneDesc, kind: int, points: np.ndarray):
     _check_host(host_lib().mi_point_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
                                                out.ctypes.data if src.size else None, src.size, visits))
     return (out.view(np.bool_) if kind == POINT_WITHIN else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def sphere_crossings_host(centre, radius2, origin, direction, t_min=0.0, t_max=float("inf")) -> int:
+    """mi_sphere_crossings_host: how often the ray crosses the sphere's shell with t_min < t < t_max (0, 1 or 2), from the
+    definition the crossing-count kernels run (csrc/cross_math.hpp) - the part of IpuScene.count_crossings with no reference
+    counterpart. centre, origin, direction: three numbers each, taken as binary32; radius2: the squared radius."""
+    c, o, d = ((C.c_float * 3)(*[float(np.float32(x)) for x in v]) for v in (centre, origin, direction))
+    return int(host_lib().mi_sphere_crossings_host(c, C.c_float(float(np.float32(radius2))), o, d, C.c_float(float(np.float32(t_min))),
+                                                   C.c_float(float(np.float32(t_max)))))
 
 
 def _geometry_array(a, dtype, width):
@@ -720,6 +738,67 @@ class IpuScene:
         halves = raw.view(torch.int16)
         return {"dist": raw[:, 0], "prim_id": words[:, 1], "geom_id": halves[:, 4].to(torch.int32),
                 "point": raw[:, 3:6], "bary": raw[:, 6:8]}
+
+    # -- crossing counts, inside tests, signed distance (mi_count_query*, mi_point_sign*) -----------------------------------------------
+    def count_crossings(self, rays: np.ndarray) -> np.ndarray:
+        """How many surfaces each ray crosses with tMin < t < tMax (a RAY array, host memory): a uint32 array. A sphere counts
+        both of its roots. Synchronous; batched by setRayBatch."""
+        assert rays.dtype == RAY and rays.ndim == 1
+        src = rays if (rays.flags["C_CONTIGUOUS"] and rays.ctypes.data % 16 == 0) else _aligned_copy(rays)
+        out = np.zeros(src.size, np.uint32)
+        self._check(self._lib.mi_count_query(self._h, src.ctypes.data, out.ctypes.data, src.size))
+        return out
+
+    def count_query_device(self, d_rays: int, d_counts: int, n: int, stream: int = 0):
+        """mi_count_query_device on device pointers (n RAY records in, n uint32 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_count_query_device(self._h, C.c_void_p(d_rays), C.c_void_p(d_counts), int(n), C.c_void_p(stream)))
+
+    @staticmethod
+    def _direction(direction):
+        """The `dir` argument of mi_point_sign*: None (the library's default) or three floats."""
+        return None if direction is None else (C.c_float * 3)(*[float(x) for x in direction])
+
+    def _point_sign_host(self, kind: int, points: np.ndarray, out: np.ndarray, direction) -> np.ndarray:
+        assert points.dtype == POINT and points.ndim == 1
+        src = points if (points.flags["C_CONTIGUOUS"] and points.ctypes.data % 16 == 0) else _aligned_copy(points)
+        self._check(self._lib.mi_point_sign(self._h, kind, src.ctypes.data, out.ctypes.data, self._direction(direction), src.size))
+        return out
+
+    def inside(self, points: np.ndarray, direction=None) -> np.ndarray:
+        """Whether each point (a POINT array, host memory; the radius is ignored) lies inside the scene's closed surfaces: a uint8
+        array, 1 = the ray from the point along `direction` (None: DEFAULT_INSIDE_DIR; no component may be zero) crosses an odd
+        number of surfaces. Synchronous; batched by setRayBatch."""
+        return self._point_sign_host(SIGN_INSIDE, points, aligned_bytes(points.size), direction)
+
+    def signed_distance(self, points: np.ndarray, direction=None) -> np.ndarray:
+        """closest_points with a sign: the POINT_HIT array of closest_points(points), and for every point inside (see inside) dist
+        negative and FLAG_INSIDE set - also where nothing lies within the radius (dist = -radius)."""
+        return self._point_sign_host(SIGN_DISTANCE, points, aligned_bytes(points.size * POINT_HIT.itemsize).view(POINT_HIT), direction)
+
+    def point_sign_device(self, kind: int, d_points: int, d_out: int, n: int, direction=None, stream: int = 0):
+        """mi_point_sign_device on device pointers (n POINT records in, n bytes or n POINT_HIT records out), asynchronous on `stream`."""
+        self._check(self._lib.mi_point_sign_device(self._h, int(kind), C.c_void_p(d_points), C.c_void_p(d_out), self._direction(direction),
+                                                   int(n), C.c_void_p(stream)))
+
+    def sdf(self, points, radius=float("inf"), direction=None) -> dict:
+        """Torch convenience over mi_point_sign_device (SIGN_DISTANCE), like nearest: a float32 device tensor of shape [N, 3]
+        (radius: a number or an [N] tensor), enqueued on torch.cuda.current_stream(). Returns device tensors: {"dist" [N], signed:
+        negative inside, "inside" [N] bool, "prim_id" [N] int32, "geom_id" [N] int32 (-1 when nothing was found, for both),
+        "point" [N, 3]}."""
+        import torch
+        p = points.to(torch.float32)
+        if p.ndim != 2 or p.shape[1] != 3 or not p.is_cuda:
+            raise ValueError("sdf: points must be an [N, 3] tensor on a GPU")
+        n = p.shape[0]
+        r = torch.as_tensor(radius, dtype=torch.float32, device=p.device).expand(n).reshape(n, 1)
+        pts = torch.cat([p, r], dim=1).contiguous()      # [N, 4] = n mi_point
+        stream = torch.cuda.current_stream(p.device).cuda_stream
+        raw = torch.empty((n, 8), dtype=torch.float32, device=p.device)
+        self.point_sign_device(SIGN_DISTANCE, pts.data_ptr(), raw.data_ptr(), n, direction, stream)
+        words = raw.view(torch.int32)
+        halves = raw.view(torch.int16)
+        return {"dist": raw[:, 0], "inside": (halves[:, 5] & FLAG_INSIDE) != 0, "prim_id": words[:, 1],
+                "geom_id": halves[:, 4].to(torch.int32), "point": raw[:, 3:6]}
 
     # -- geometry updates (mi_scene_update*): new primitive positions, the BVH refit on the device ------------------------------------
     def update_geometry(self, vertices=None, normals=None, spheres=None, discs=None) -> "IpuScene":

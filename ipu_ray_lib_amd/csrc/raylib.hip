@@ -18,6 +18,7 @@
 #include "trace_wavefront.hpp"
 #include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
 #include "point_kernels.hpp"         // point queries: the nearest primitive of each given point (mi_point_query / mi_point_query_device)
+#include "count_kernels.hpp"         // crossing counts, inside tests and signed distance (mi_count_query*, mi_point_sign*)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
 #include "canon_kernels.hpp"         // new contents for a live scene: the canonical primitive table on the device (mi_scene_set_geometry*)
@@ -1683,6 +1684,116 @@ bool pointArgsBad(const char* fn, const mi_scene* scene, int kind, const void* p
   return true;
 }
 
+// Crossing counts (mi_count_query_device): how many surfaces each of n caller-supplied rays crosses inside its interval, one thread
+// per ray (count_kernels.hpp). double_fallback and full_stats pick the build (double_fallback has no instrumented build: it takes
+// precedence, as in launchQuery); fast, query_kernel and query_tune do not apply. Records the slot's lastWork event, as launchQuery does.
+void launchCountQuery(mi_scene& S, const mi_ray* d_rays, uint32_t* d_counts, size_t n, hipStream_t stream) {
+  if (n == 0) return;
+  if (n > kMaxWorkItems) throw ArgError("mi_count_query: more rays than one launch indexes (kMaxWorkItems)");
+  const uint32_t cnt = (uint32_t)n;
+  LaunchSlot& slot = S.slotFor(stream);
+  const DeviceScene dsv = S.ds;
+  const dim3 block(256), grid((cnt + 255) / 256);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_rays, d_counts, cnt); };
+  if (S.opt.doubleFallback) go(count_query_kernel<false, true>);
+  else if (S.opt.fullStats) go(count_query_kernel<true, false>);
+  else go(count_query_kernel<false, false>);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
+}
+
+// Argument rules shared by the two count-query entries; touches neither the scene nor a device.
+bool countArgsBad(const char* fn, const mi_scene* scene, const void* rays, const void* counts, size_t n, size_t limit) {
+  const char* why = nullptr;
+  if (!scene) why = "null scene";
+  else if (n == 0) return false;
+  else if (!rays || !counts) why = "null buffer";
+  else if ((uintptr_t)rays % 16) why = "rays must be 16-byte aligned";
+  else if ((uintptr_t)counts % 4) why = "counts must be 4-byte aligned";
+  else if (n > limit) why = "more rays than one launch indexes (kMaxWorkItems)";
+  if (!why) return false;
+  g_err = std::string(fn) + ": " + why;
+  return true;
+}
+
+// Inside tests and signed distance (mi_point_sign_device). MI_SIGN_DISTANCE: the point query as mi_point_query_device launches it,
+// then point_sign_kernel, which walks the crossings of each point's ray along `dir` and marks the records of the points inside in
+// place; MI_SIGN_INSIDE: that walk alone, writing bytes. Both on `stream`, the slot's lastWork event behind the last launch.
+void launchPointSign(mi_scene& S, int kind, const mi_point* d_points, void* d_out, f3 dir, size_t n, hipStream_t stream) {
+  if (n == 0) return;
+  if (n > kMaxWorkItems) throw ArgError("mi_point_sign: more points than one launch indexes (kMaxWorkItems)");
+  const uint32_t cnt = (uint32_t)n;
+  LaunchSlot& slot = S.slotFor(stream);
+  const DeviceScene dsv = S.ds;
+  const dim3 block(256), grid((cnt + 255) / 256);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_points, d_out, dir, cnt); };
+#define MI_PS(D) do { if (S.opt.doubleFallback) go(point_sign_kernel<D, false, true>); \
+                      else if (S.opt.fullStats) go(point_sign_kernel<D, true, false>); \
+                      else go(point_sign_kernel<D, false, false>); } while (0)
+  if (kind == MI_SIGN_DISTANCE) {
+    auto first = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_points, d_out, cnt); };
+    if (S.opt.fullStats) first(point_query_kernel<false, true>); else first(point_query_kernel<false, false>);
+    HIP_CHECK(hipGetLastError());
+    MI_PS(true);
+  } else {
+    MI_PS(false);
+  }
+#undef MI_PS
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
+}
+
+// The direction of an inside test: the caller's three floats or the default; a zero, NaN or infinite component is refused (the
+// triangle test shears by the smallest signed component: an axis direction divides by zero there).
+constexpr float kDefaultInsideDir[3] = {1.0f, 0.70710678f, 0.57735027f};
+
+// Argument rules shared by the two point-sign entries; touches neither the scene nor a device.
+bool signArgsBad(const char* fn, const mi_scene* scene, int kind, const void* points, const void* out, const float* dir, size_t n, size_t limit) {
+  const char* why = nullptr;
+  if (!scene) why = "null scene";
+  else if (kind != MI_SIGN_INSIDE && kind != MI_SIGN_DISTANCE) why = "unknown sign kind";
+  else if (dir && !(dir[0] != 0.f && dir[1] != 0.f && dir[2] != 0.f && std::fabs(dir[0]) < kInf && std::fabs(dir[1]) < kInf && std::fabs(dir[2]) < kInf))
+    why = "a direction component is zero, NaN or infinite";
+  else if (n == 0) return false;
+  else if (!points || !out) why = "null buffer";
+  else if ((uintptr_t)points % 16 || (kind == MI_SIGN_DISTANCE && (uintptr_t)out % 16)) why = "buffers must be 16-byte aligned";
+  else if (n > limit) why = "more points than one launch indexes (kMaxWorkItems)";
+  if (!why) return false;
+  g_err = std::string(fn) + ": " + why;
+  return true;
+}
+
+// The host entries of the count and sign queries: mi_query's pipeline and its buffers (a slot holds `batch` 32-byte records in and
+// out: room for rays or points and any of the results). launch(in, out, cnt, stream) enqueues one batch.
+template <class Launch>
+void pipelinedQuery(mi_scene* scene, const void* in, size_t inSize, void* out, size_t outSize, size_t n, size_t batch, const Launch& launch) {
+  HIP_CHECK(hipSetDevice(scene->device));
+  const size_t numBatches = (n + batch - 1) / batch;
+  const int slots = numBatches > 1 ? 2 : 1;
+  try {
+    for (int i = 0; i < slots; ++i) {
+      if (scene->qCap[i] < batch) {
+        if (scene->d_qRays[i] || scene->d_qOut[i]) HIP_CHECK(hipDeviceSynchronize());
+        for (void** p : {&scene->d_qRays[i], &scene->d_qOut[i]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        scene->qCap[i] = 0;
+        HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * sizeof(mi_ray)));
+        HIP_CHECK(hipMalloc(&scene->d_qOut[i], batch * sizeof(mi_query_hit)));
+        scene->qCap[i] = batch;
+      }
+      if (!scene->pipeStream[i]) HIP_CHECK(hipStreamCreateWithFlags(&scene->pipeStream[i], hipStreamNonBlocking));
+    }
+    for (size_t b = 0; b < numBatches; ++b) {
+      const int i = (int)(b % slots);
+      hipStream_t st = scene->pipeStream[i];
+      const size_t first = b * batch, cnt = std::min(batch, n - first);
+      HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], static_cast<const char*>(in) + first * inSize, cnt * inSize, hipMemcpyHostToDevice, st));
+      launch(scene->d_qRays[i], scene->d_qOut[i], cnt, st);
+      HIP_CHECK(hipMemcpyAsync(static_cast<char*>(out) + first * outSize, scene->d_qOut[i], cnt * outSize, hipMemcpyDeviceToHost, st));
+    }
+    for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
+  } catch (...) { (void)hipDeviceSynchronize(); throw; }
+}
+
 // One wave that samples the work counter of `hip_stream`'s persistent launches `n` times, `period_ticks` (100-MHz ticks) apart, into
 // d_samples as pairs {s_memrealtime, counter}: how fast a launch hands its work units out over its life - the ramp at its start, the
 // moment the queue runs empty, the drain behind it (tools/launch_progress.py). It runs on a stream of the scene's own beside the launch it
@@ -2035,6 +2146,54 @@ int mi_point_query(mi_scene* scene, int kind, const mi_point* points, void* out,
       }
       for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
     } catch (...) { (void)hipDeviceSynchronize(); throw; }
+  });
+}
+
+int mi_count_query_device(mi_scene* scene, const void* d_rays, uint32_t* d_counts, size_t n, void* hip_stream) {
+  if (countArgsBad("mi_count_query_device", scene, d_rays, d_counts, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    launchCountQuery(*scene, static_cast<const mi_ray*>(d_rays), d_counts, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_count_query(mi_scene* scene, const mi_ray* rays, uint32_t* counts, size_t n) {
+  if (countArgsBad("mi_count_query", scene, rays, counts, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  // (the host stream is cut into batches of mi_scene_set_ray_batch rays: the work-index limit applies per batch)
+  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
+  if (batch > kMaxWorkItems) { g_err = "mi_count_query: more rays per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    pipelinedQuery(scene, rays, sizeof(mi_ray), counts, sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchCountQuery(*scene, static_cast<const mi_ray*>(d_in), static_cast<uint32_t*>(d_out), cnt, st);
+    });
+  });
+}
+
+int mi_point_sign_device(mi_scene* scene, int kind, const void* d_points, void* d_out, const float dir[3], size_t n, void* hip_stream) {
+  if (signArgsBad("mi_point_sign_device", scene, kind, d_points, d_out, dir, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const float* dv = dir ? dir : kDefaultInsideDir;
+  const f3 d = mk(dv[0], dv[1], dv[2]);
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    launchPointSign(*scene, kind, static_cast<const mi_point*>(d_points), d_out, d, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_point_sign(mi_scene* scene, int kind, const mi_point* points, void* out, const float dir[3], size_t n) {
+  if (signArgsBad("mi_point_sign", scene, kind, points, out, dir, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  // (the host stream is cut into batches of mi_scene_set_ray_batch points: the work-index limit applies per batch)
+  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
+  if (batch > kMaxWorkItems) { g_err = "mi_point_sign: more points per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
+  const float* dv = dir ? dir : kDefaultInsideDir;
+  const f3 d = mk(dv[0], dv[1], dv[2]);
+  return guarded([&] {
+    pipelinedQuery(scene, points, sizeof(mi_point), out, kind == MI_SIGN_INSIDE ? 1 : sizeof(mi_point_hit), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchPointSign(*scene, kind, static_cast<const mi_point*>(d_in), d_out, d, cnt, st);
+    });
   });
 }
 
