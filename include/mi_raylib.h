@@ -454,6 +454,10 @@ int mi_get_phase_stats(mi_scene* scene, uint64_t stats[12]);
 /* Scheduler bookkeeping of the path-pool kernel (kernel 3, instrumented build only): {loop iterations, refill turns,
  * lanes refilled, idle iterations, lost ring claims, traversal bursts, lanes walking at burst start, cycles in refill}. */
 int mi_get_pool_stats(mi_scene* scene, uint64_t stats[8]);
+/* What the instrumented build (option full_stats) counted of plain renders that walked the private, hot-first copy (option hot_nodes):
+ * {box-test steps that ran from LDS, the lanes in them, box-test steps of runs that ran from global memory, the lanes in them, box tests
+ * of nodes inside the staged prefix}. Zeros while no such render has run. */
+int mi_get_hot_stats(mi_scene* scene, uint64_t stats[5]);
 /* Measurement only: enqueues, on a stream of the scene's own, ONE wave that samples the work counter of `hip_stream`'s persistent
  * launches n times, period_ticks (100-MHz ticks) apart, into d_samples (device memory, 2 n words: {s_memrealtime, counter}). Call it
  * right before mi_render_device on `hip_stream`; read the samples after a device synchronise (tools/launch_progress.py: the rate at which
@@ -537,6 +541,14 @@ int mi_scene_set_ray_batch(mi_scene* scene, size_t rays_per_batch);
  *   "rebuild_timing" 0 | 1          bracket the passes of mi_scene_rebuild with HIP events (mi_get_rebuild_timing)
  *   "leaf_rot"      0 | 1           scenes without vertex normals: the default kernel reads primitive records pre-rotated for the cast's shear axis (default 1)
  *   "lean_hit"      0 | 1           scenes without vertex normals run the build of the default kernel that carries no barycentrics (default 1)
+ *   "hot_nodes"     auto | 0..65535 plain renders of the default kernel walk a private, hot-first copy of the BVH arrays and run the box-test runs whose lanes
+ *                                   all stand in its first nodes from LDS: that many nodes, clamped to the tree and to what fits beside the kernel's other LDS
+ *                                   (316 on an MI355X). 0 = off: the shared arrays and the launch of before. auto (the default): on, with as many as fit, where
+ *                                   those nodes take 0.9 of the tree's expected box tests (surface-area model, decided at create). Every result byte is the same
+ *                                   either way. NIF renders, renders under double_fallback or fast, and a scene whose geometry has been updated, rebuilt
+ *                                   or replaced (mi_scene_update*, mi_scene_rebuild, mi_scene_set_geometry*) run on the shared arrays whatever the option says.
+ *                                   The copy is made at create, whatever the option says then (it may be set later): about 260 bytes of device memory per
+ *                                   BVH node beside the shared arrays' own, given back by the first update, rebuild or replacement of the geometry
  *   "coords"        0 | 1           (pixel, segment) work units read the pixel's (u, v) from a compact copy of the stream gathered once
  *                                   per launch, not from the 84-byte record (default 1: a third of the HBM traffic)
  *   "cus"           0..4096         compute units the launch grids are sized for (0 = what the device reports; grids are

@@ -116,6 +116,28 @@ int mi_point_query_host(const mi_scene_desc* desc, int kind, const mi_point* poi
 uint32_t mi_sphere_crossings_host(const float centre[3], float radius2, const float origin[3], const float direction[3],
                                   float t_min, float t_max);
 
+/* The hot-first order of the private copy of the walk's arrays that plain renders may walk (scene option "hot_nodes", mi_raylib.h),
+ * from the functions the device library's upload runs (ipu_ray_lib_amd/csrc/hot_order.hpp). For num_nodes compact nodes (a depth-first
+ * BVH2) it writes, each num_nodes entries long: preorder - the 32-byte device nodes of the shared array (six floats min/max per axis,
+ * then the two successors as byte offsets: link, hit); order - order[k] = the preorder index of the node at place k of the private
+ * array (chains of first children by falling half-area of their first box, ties by preorder index, the root's chain first); hot - the
+ * private node array; leaf_link - per private node, the byte offset of the node that follows a leaf (its record carries it; 0 for
+ * interior nodes). MI_ERR_INVALID_ARG: a null pointer with num_nodes > 0, 2^26 nodes or more, nodes that are not a depth-first BVH2. */
+int mi_hot_nodes(const mi_bvh_node* compact, uint32_t num_nodes, void* preorder, uint32_t* order, void* hot, uint32_t* leaf_link);
+
+/* share[k - 1] = the share of a random line's box tests that falls on the first k nodes of `order`, under the surface-area model (a
+ * node is tested when its parent's box is hit; probability proportional to that box's half-area): what the default of option
+ * "hot_nodes" is decided from. preorder and order as mi_hot_nodes writes them. */
+int mi_hot_share(const void* preorder, uint32_t num_nodes, const uint32_t* order, double* share);
+
+/* The stackless walk of such a node array for the ray origin + t direction, t in [0, inf), with no primitive ever shortening it:
+ * visits[] receives, up to capacity entries, the index of every node whose box is tested, followed - for a leaf whose box is hit -
+ * by the same index with bit 31 set (the primitive test); the return value is the number of entries the walk makes. leaf_link = NULL
+ * walks the shared array's protocol (preorder), otherwise the layout-free one of the private array. *status (may be NULL) becomes
+ * MI_ERR_INVALID_ARG when a successor points outside the array or the walk does not end, else MI_OK. */
+uint32_t mi_hot_walk(const void* nodes, uint32_t num_nodes, const uint32_t* leaf_link, const float origin[3], const float direction[3],
+                     uint32_t* visits, uint32_t capacity, int* status);
+
 /* initPerspectiveRayStream(rayStream, image, data, nullptr) + zeroRgb: window_w*window_h rays in
  * row-major window order, origin 0, un-jittered pinhole directions, u=row, v=col. */
 int mi_init_ray_stream(const mi_scene_desc* desc, mi_trace_result* rays, size_t capacity);

@@ -183,6 +183,10 @@ def host_lib() -> C.CDLL:
         lib.mi_point_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
+        lib.mi_hot_nodes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mi_hot_walk.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]
+        lib.mi_hot_walk.restype = C.c_uint32
+        lib.mi_hot_share.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.mi_bvh_cost_compact.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_compact_block.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_estimate.argtypes = [C.POINTER(C.c_double)]
@@ -287,6 +291,7 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_group_gathered_device.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.c_uint32]
         lib.mi_group_reset_counters.argtypes = [C.c_void_p]
         lib.mi_get_pool_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.mi_get_hot_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
         lib.mi_debug_launch_progress.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
         lib.mi_scene_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p]
         lib.mi_get_nif_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
@@ -474,6 +479,36 @@ def point_query_host(desc: SceneDesc, kind: int, points: np.ndarray):
     _check_host(host_lib().mi_point_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
                                                out.ctypes.data if src.size else None, src.size, visits))
     return (out.view(np.bool_) if kind == POINT_WITHIN else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+DEVICE_NODE = np.dtype([("box", "<f4", (6,)), ("link", "<u4"), ("hit", "<u4")])     # the 32-byte device node: min/max per axis, two byte-offset successors
+
+
+def hot_nodes(nodes: np.ndarray) -> dict:
+    """mi_hot_nodes: for a BVH_NODE array, the device's preorder node array, the hot-first order of the private copy plain renders
+    may walk (option hot_nodes; order[k] = preorder index of the node at place k), that copy's node array and the successor each of
+    its leaves' records carries - {"preorder", "order", "hot", "leaf_link"}, from the functions the upload runs (csrc/hot_order.hpp)."""
+    nodes = np.ascontiguousarray(nodes, dtype=BVH_NODE)
+    n = nodes.size
+    out = {"preorder": np.zeros(n, DEVICE_NODE), "order": np.zeros(n, np.uint32), "hot": np.zeros(n, DEVICE_NODE), "leaf_link": np.zeros(n, np.uint32)}
+    _check_host(host_lib().mi_hot_nodes(nodes.ctypes.data if n else None, n, *[out[k].ctypes.data if n else None for k in ("preorder", "order", "hot", "leaf_link")]))
+    out["share"] = np.zeros(n, np.float64)      # share[k - 1]: what the first k places take of a random line's box tests (mi_hot_share)
+    _check_host(host_lib().mi_hot_share(out["preorder"].ctypes.data if n else None, n, out["order"].ctypes.data if n else None, out["share"].ctypes.data if n else None))
+    return out
+
+
+def hot_walk(device_nodes: np.ndarray, origin, direction, leaf_link: np.ndarray | None = None) -> np.ndarray:
+    """mi_hot_walk: the entries of the stackless, box-tests-only walk of a DEVICE_NODE array for one ray (node indices; bit 31 marks
+    the primitive test of a leaf whose box was hit). leaf_link = None: the shared array's protocol, else the private array's."""
+    assert device_nodes.dtype == DEVICE_NODE and device_nodes.flags.c_contiguous
+    o, d = ((C.c_float * 3)(*[float(np.float32(x)) for x in v]) for v in (origin, direction))
+    link = None if leaf_link is None else np.ascontiguousarray(leaf_link, np.uint32)
+    cap = 4 * device_nodes.size + 4
+    visits = np.zeros(cap, np.uint32)
+    status = C.c_int(0)
+    cnt = host_lib().mi_hot_walk(device_nodes.ctypes.data, device_nodes.size, None if link is None else link.ctypes.data, o, d, visits.ctypes.data, cap, C.byref(status))
+    _check_host(status.value)
+    return visits[:min(cnt, cap)].copy()
 
 
 def sphere_crossings_host(centre, radius2, origin, direction, t_min=0.0, t_max=float("inf")) -> int:
@@ -937,6 +972,14 @@ class IpuScene:
         c = (C.c_uint64 * 8)()
         self._check(self._lib.mi_get_pool_stats(self._h, c))
         return dict(zip(("loops", "refill_turns", "refill_lanes", "idle", "lost_claims", "bursts", "burst_lanes", "refill_cycles"), [int(x) for x in c]))
+
+    def hot_stats(self) -> dict:
+        """What the instrumented build (option full_stats) counted of plain renders that walked the private, hot-first copy (option
+        hot_nodes): box-test steps that ran from LDS and the lanes in them, the steps of runs that ran from global memory and their
+        lanes, and the box tests of nodes inside the staged prefix. All zero while such a render has not run."""
+        c = (C.c_uint64 * 5)()
+        self._check(self._lib.mi_get_hot_stats(self._h, c))
+        return dict(zip(("lds_steps", "lds_lanes", "global_steps", "global_lanes", "hot_visits"), [int(x) for x in c]))
 
     def launch_progress(self, d_samples: int, n: int, period_ticks: int, stream: int = 0) -> None:
         """mi_debug_launch_progress: one wave samples the work counter of `stream`'s persistent launches n times, period_ticks

@@ -16,6 +16,7 @@
 #include "ray_math.h"
 #include "trace_kernels.hpp"
 #include "trace_wavefront.hpp"
+#include "hot_order.hpp"
 #include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
 #include "point_kernels.hpp"         // point queries: the nearest primitive of each given point (mi_point_query / mi_point_query_device)
 #include "count_kernels.hpp"         // crossing counts, inside tests and signed distance (mi_count_query*, mi_point_sign*)
@@ -114,6 +115,10 @@ const float* hostSinTable() {
 // per launch, 11 with 512 and no less with 768 or 1 024 (profiles/r05_config5_launch_ab.txt); 512 samples are 48 B x 512 per pixel, 51 GB
 // of a 1440^2 frame's 288.
 constexpr uint32_t kNifSplDefault = 512, kNifSplMax = 1024;
+constexpr int kHotNodesAuto = -1;                 // option "hot_nodes" = auto: on, with as many nodes as fit, where the staged prefix takes kHotAutoShare of the tree's expected box tests
+constexpr double kHotAutoShare = 0.9;             // (hot_order.hpp hot_prefix_share; the box scene: 0.96 and -2.4 % frame time, test_scene.dae: 0.76 and +2 % - profiles/r06_k1w_hot_nodes_ab.txt)
+constexpr uint32_t kHotThreads = 768;             // the HOT builds' workgroup: two per compute unit, six waves per SIMD - the larger the workgroup, the larger the prefix its copies of the cold state leave room for (256 x 6: 68 nodes, 512 x 3: 172, 768 x 2: 316)
+constexpr uint32_t kLdsPerCU = 160 * 1024, kLdsGranule = 1280;      // gfx950 hands LDS out in 320-dword granules; the occupancy query does not round
 struct SceneOptions {
   bool fullStats = false;          // MI_RAYLIB_FULL_STATS / "full_stats": instrumented kernel variants (node/leaf counters, phase occupancy)
   WaveTune tune = kDefaultTune;
@@ -159,6 +164,8 @@ struct SceneOptions {
   bool fast = false;               // "fast": the tolerance tier (FMA box / triangle tests; plain path-trace renders of the default kernel only)
   int queryKernel = 0;             // "query_kernel": ray queries (mi_query*) run the one-thread-per-ray kernel (0, the default: measured faster, DESIGN.md §6 "K4") or K4 (1, query_kernels.hpp)
   QueryTune queryTune = kDefaultQueryTune;   // "query_tune": K4's scheduling weights leafAt,dbl,maxExtra,burst,keep8
+  int hotNodes = kHotNodesAuto;    // "hot_nodes": plain renders of the default kernel walk K1w's private, hot-first copy of the BVH and stage this many of its
+                                   // first nodes in LDS (clamped to what fits beside the cold state; trace_wavefront.hpp HOT). 0 = off: the shared arrays, today's launch; auto (the default): see kHotAutoShare
   double autoRebuild = 0.0;        // "auto_rebuild": 0 = off; a ratio R > 1: an applied update whose tree's cost estimate is above R x the baseline's runs
                                    // the rebuild before it returns (refitScene). No environment variable, as for the arithmetic options: replicas must decide alike
 
@@ -261,6 +268,7 @@ struct SceneOptions {
     if (key == "lean_hit") return flag01(v, leanHit);
     if (key == "auto_rebuild") { if (!autoRebuildValue(v, autoRebuild)) { why = "auto_rebuild takes 0 (off) or a decimal ratio above 1"; return false; } return true; }
     if (key == "leaf_rot") return flag01(v, leafRot);
+    if (key == "hot_nodes") { if (!strcmp(v, "auto")) { hotNodes = kHotNodesAuto; return true; } if (!number(v, 0, 65535, q)) return false; hotNodes = (int)q; return true; }
     if (key == "double_fallback") {
       bool b = doubleFallback;
       if (!flag01(v, b)) return false;
@@ -304,7 +312,8 @@ struct SceneOptions {
                                          {"MI_RAYLIB_NIF_SHAPE", "nif_shape"}, {"MI_RAYLIB_TUNE", "tune"},
                                          {"MI_RAYLIB_POOL_TUNE", "pool_tune"}, {"MI_RAYLIB_POOL_WAVES", "pool_waves"}, {"MI_RAYLIB_CUS", "cus"},
                                          {"MI_RAYLIB_NIF_OVERLAP", "nif_overlap"}, {"MI_RAYLIB_COORDS", "coords"},
-                                         {"MI_RAYLIB_NIF_TRACE_WGS", "nif_trace_wgs"}, {"MI_RAYLIB_NIF_SPLIT", "nif_split"}, {"MI_RAYLIB_NIF_GENERATIONS", "nif_generations"}};
+                                         {"MI_RAYLIB_NIF_TRACE_WGS", "nif_trace_wgs"}, {"MI_RAYLIB_NIF_SPLIT", "nif_split"}, {"MI_RAYLIB_NIF_GENERATIONS", "nif_generations"},
+                                         {"MI_RAYLIB_HOT_NODES", "hot_nodes"}};
     // (an unparsable environment value is ignored: the option keeps its default. The two options that select ARITHMETIC,
     // double_fallback and fast, are deliberately not in this list: a process that says "bit-exact" must not change tier
     // because of a variable somebody exported)
@@ -344,6 +353,46 @@ struct mi_scene {
   bool nifOverlapOn() const { return opt.nifOverlap < 0 ? (opt.nifSplit > 0 || !((opt.nifShape >= 6 && opt.nifShape <= 8) && nif_asm_covers(nif.regs))) : opt.nifOverlap != 0; }
   // the scene as one launch sees it: option "root_start" decides whether the walk may start below the root
   DeviceScene view() const { DeviceScene v = ds; if (!opt.rootStart) v.rootInterior = 0; return v; }
+  // K1w's private copies of the walk's arrays in hot-first order (option "hot_nodes"; hot_order.hpp), made at create from the
+  // arrays as uploaded. Everything that changes the shared arrays on the device - a refit, a rebuild, new contents - takes its
+  // mutable reference to them from touchArrays(), which retires the copies: from then on the scene launches today's kernel on
+  // the shared arrays (the copies are not regenerated on the device).
+  struct HotCopy { const GNode* nodes = nullptr; const GLeaf* leaves = nullptr; const GLeafRot* rot = nullptr; const float* leafNormals = nullptr; bool valid = false;
+                   std::vector<double> share; } hot;      // share[k - 1]: what the first k nodes take of the tree's expected box tests (hot_prefix_share)
+  DeviceScene hotView() const { DeviceScene v = view(); v.nodes = hot.nodes; v.leaves = hot.leaves; v.leavesRot = hot.rot; v.leafNormals = hot.leafNormals; return v; }
+  DeviceScene& touchArrays() { hot.valid = false; return ds; }
+  // gives a retired copy's buffers back (hipFree waits for the work that may still read them); called where an update has been applied
+  void freeRetiredHot() {
+    if (hot.valid) return;
+    for (const void* p : {(const void*)hot.nodes, (const void*)hot.leaves, (const void*)hot.rot, (const void*)hot.leafNormals}) release(p);
+    hot = HotCopy{};
+  }
+  bool hotRoomSaid = false;
+  // the dynamic LDS (bytes, a multiple of a node) a HOT build may take per workgroup without losing a resident workgroup per compute unit
+  std::map<const void*, uint32_t> hotRoomOf;
+  uint32_t hotRoom(const void* kern, int threads) {
+    auto it = hotRoomOf.find(kern);
+    if (it != hotRoomOf.end()) return it->second;
+    hipFuncAttributes fa{};
+    int nb0 = 0;
+    uint32_t room = 0;
+    if (hipFuncGetAttributes(&fa, kern) == hipSuccess && hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb0, kern, threads, 0) == hipSuccess && nb0 > 0) {
+      long bytes = ((long)(kLdsPerCU / (uint32_t)nb0 / kLdsGranule * kLdsGranule) - (long)fa.sharedSizeBytes) & ~31L;
+      for (; bytes >= 32; bytes -= 256) {
+        int nb = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, (size_t)bytes) == hipSuccess && nb >= nb0) break;
+      }
+      if (bytes >= 32) room = (uint32_t)bytes;
+    }
+    (void)hipGetLastError();
+    if (room && hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)room) != hipSuccess) { (void)hipGetLastError(); room = 0; }
+    if (!room && !hotRoomSaid) {      // (said once per scene: the renders are right either way, but not the ones the option asked for)
+      hotRoomSaid = true;
+      fprintf(stderr, "mi_raylib: option hot_nodes: the runtime leaves no LDS for hot nodes beside a %d-thread workgroup's own; rendering from the shared arrays\n", threads);
+    }
+    hotRoomOf.emplace(kern, room);
+    return room;
+  }
   uint32_t residentBlocks(const void* kern, int threads, size_t ldsBytes) {
     auto it = residentPerCU.find(kern);
     if (it == residentPerCU.end()) {
@@ -605,6 +654,24 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
   DeviceScene& ds = S.ds;
   ds.nodes = S.keep(upload(nodes)); ds.numNodes = N;
   ds.leaves = S.keep(upload(leaves)); ds.numLeaves = (uint32_t)leaves.size();
+  // K1w's private copies (mi_scene::hot): the nodes in hot-first order with their successors renumbered, the records moved along
+  std::vector<uint32_t> hotOrder(N), hotLink(N);
+  {
+    std::vector<GNode> hotNodes(N);
+    if (N) {
+      hot_first_order(reinterpret_cast<const HotNode*>(nodes.data()), N, hotOrder.data());
+      hot_permute_nodes(reinterpret_cast<const HotNode*>(nodes.data()), N, hotOrder.data(), reinterpret_cast<HotNode*>(hotNodes.data()), hotLink.data());
+      S.hot.share.resize(N);
+      hot_prefix_share(reinterpret_cast<const HotNode*>(nodes.data()), N, hotOrder.data(), S.hot.share.data());
+    }
+    // (a leaf's record carries the node that follows it: a plain record in triBase - the walk reads it with primID's 16 bytes, nothing
+    // on the device reads the triangle's index base -, a pre-rotated block in its first word, above the kind: that word loses the geomID
+    // bits the shared blocks carry, which no walk reads - the hit's geomID and primID come from the plain record, whose type word stays)
+    std::vector<GLeaf> hotLeaves(N);
+    for (uint32_t k = 0; k < N; ++k) { hotLeaves[k] = leaves[hotOrder[k]]; if (isLeafNode[hotOrder[k]]) hotLeaves[k].triBase = hotLink[k]; }
+    S.hot.nodes = S.keep(upload(hotNodes));
+    S.hot.leaves = S.keep(upload(hotLeaves));
+  }
   {
     // the primitive-test part of every record once per shear axis (GLeafRot, trace_kernels.hpp): a triangle's vertices with their
     // components rotated so that component kz comes last - (kx, ky, kz) = (kz + 1, kz + 2, kz) mod 3, permute_kz - other records as they are
@@ -621,12 +688,20 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
         }
       }
     ds.leavesRot = S.keep(upload(rot));
+    std::vector<GLeafRot> hotRot(rot.size());
+    for (uint32_t k = 0; k < N; ++k) {
+      hotRot[k] = rot[hotOrder[k]];
+      if (isLeafNode[hotOrder[k]]) for (uint32_t kz = 0; kz < 3; ++kz) hotRot[k].b[kz].type = hotLink[k] | leaf_kind(leaves[hotOrder[k]]);
+    }
+    S.hot.rot = S.keep(upload(hotRot));
   }
   ds.matIDs = S.keep(upload(std::vector<uint32_t>(d.mat_ids, d.mat_ids + d.num_mat_ids)));
   ds.materials = S.keep(upload(std::vector<mi_material>(d.materials, d.materials + d.num_materials)));
   ds.numMaterials = d.num_materials;
   ds.hasNormals = d.num_normals ? 1u : 0u;
   ds.leafNormals = nullptr;
+  S.hot.leafNormals = nullptr;
+  S.hot.valid = true;
   if (ds.hasNormals) {
     std::vector<float> ln(9 * leaves.size(), 0.f);
     for (size_t k = 0; k < leaves.size(); ++k) {
@@ -641,6 +716,9 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
       }
     }
     ds.leafNormals = S.keep(upload(ln));
+    std::vector<float> hotLn(ln.size());
+    for (uint32_t k = 0; k < N; ++k) memcpy(&hotLn[9 * (size_t)k], &ln[9 * (size_t)hotOrder[k]], 9 * sizeof(float));
+    S.hot.leafNormals = S.keep(upload(hotLn));
     ds.meshTris = S.keep(upload(std::vector<uint16_t>(d.mesh_tris, d.mesh_tris + 3 * (size_t)d.num_tris)));
     ds.meshNormals = S.keep(upload(std::vector<mi_vec3>(d.mesh_normals, d.mesh_normals + d.num_normals)));
     ds.geomFirstVertex = S.keep(upload(geomFirstVertex));
@@ -815,7 +893,7 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream);
 void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
   refitTables(S);
   mi_scene::Refit& R = S.refit;
-  DeviceScene& ds = S.ds;
+  DeviceScene& ds = S.touchArrays();      // (K1w's private copies retire here: the update writes the shared arrays)
   const uint32_t N = ds.numNodes;
   RefitGeom g;
   g.verts = u.mesh_verts ? (const mi_vec3*)u.mesh_verts : R.d_verts;
@@ -881,6 +959,7 @@ void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
   HIP_CHECK(hipStreamSynchronize(stream));
   if (timing) { float w = 0.f; HIP_CHECK(hipEventElapsedTime(&w, R.ev[3], R.ev[1])); R.ms[2] = w; }
   ++S.live.applied;
+  S.freeRetiredHot();
   if (!N) return;
   R.live = scratch;
   if (N > 1) {      // the root's box as buildDeviceScene sets it (root_start)
@@ -1107,8 +1186,9 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
   // tables: the update's allocations, made once (a rebuild reads nothing of the tables, and writes them below)
   refitAlloc(S);
   rebuildTables(S);
-  S.live.maxLeafDepth = rebuildPasses(S, S.refit, S.rebuild, S.ds, stream, "mi_scene_rebuild", true);
+  S.live.maxLeafDepth = rebuildPasses(S, S.refit, S.rebuild, S.touchArrays(), stream, "mi_scene_rebuild", true);
   rebuildBaseline(S, stream);
+  S.freeRetiredHot();
   return S.live.maxLeafDepth;
 }
 
@@ -1208,10 +1288,12 @@ uint32_t setGeometry(mi_scene& S, const mi_scene_geometry& g, hipStream_t stream
   const mi_scene::Refit& oR = S.refit;
   std::vector<const void*> old = {o.nodes, o.leaves, o.leavesRot, o.matIDs, o.materials, o.leafNormals, o.meshTris, o.meshNormals, o.geomFirstVertex,
                                   oR.d_prims, oR.d_order, oR.d_boxes, oR.d_cnodes[0], oR.d_cnodes[1], oR.d_levelStart, oR.d_verts, oR.d_spheres, oR.d_discs,
-                                  S.rebuild.d_canon, S.live.d_cost};
+                                  S.rebuild.d_canon, S.live.d_cost,
+                                  S.hot.nodes, S.hot.leaves, S.hot.rot, S.hot.leafNormals};      // (the private copies were the old contents')
   if (B.d_primBoxes != S.rebuild.d_primBoxes) for (void* p : rebuildScratchBuffers(S.rebuild)) old.push_back(p);
   for (const void* p : old) S.release(p);
-  S.ds = ds;
+  S.hot = mi_scene::HotCopy{};
+  S.touchArrays() = ds;
   S.refit = std::move(R);
   S.rebuild = B;
   S.live.d_cost = nullptr;                       // (sized for the old node count: sceneCost allocates it again)
@@ -1362,6 +1444,27 @@ void launchWavefront(mi_scene& S, mi_trace_result* d_rays, uint32_t cnt, hipStre
       if (S.opt.sayGrid) fprintf(stderr, "mi_raylib: grid %u workgroups = %u units x %u resident\n", grid(kern, 256, 0), units, S.residentBlocks(reinterpret_cast<const void*>(kern), 256, 0));
       hipLaunchKernelGGL(kern, dim3(grid(kern, 256, 0)), dim3(256), 0, stream, dsv, d_rays, cnt, workCounter, 0u, S.opt.tune, tileW, exs);
     };
+#define MI_K1W_HOT(BL, BA, RO) path_trace_wavefront_kernel<false, false, BL, 6, false, 0, true, false, false, true, BA, RO, true>
+    // Option "hot_nodes": the HOT builds (trace_wavefront.hpp) walk the scene's private, hot-first copies and stage their first nodes in
+    // dynamic LDS - as many as asked for, as the copy has, and as fit without costing a resident workgroup. Plain renders only, while the
+    // copies stand for the shared arrays (mi_scene::touchArrays); false = nothing launched: the caller goes on to today's kernel.
+    const bool hotOn = plain && S.opt.hotNodes != 0 && S.hot.valid && S.ds.numNodes > 0;
+    auto goHot = [&](auto kern, uint32_t threads) -> bool {
+      const uint32_t room = S.hotRoom(reinterpret_cast<const void*>(kern), (int)threads);
+      const uint32_t count = std::min(std::min(S.opt.hotNodes < 0 ? ~0u : (uint32_t)S.opt.hotNodes, S.ds.numNodes), room / (uint32_t)sizeof(GNode));
+      if (!count) return false;
+      if (S.opt.hotNodes < 0) {
+        // auto: decided from the prefix the plain build of this scene's kind stages, whichever build is being launched (the instrumented one has room for more)
+        const uint32_t plainRoom = S.ds.hasNormals ? S.hotRoom(reinterpret_cast<const void*>(MI_K1W_HOT(kHotThreads, true, false)), (int)kHotThreads)
+                                                   : S.hotRoom(reinterpret_cast<const void*>(MI_K1W_HOT(kHotThreads, false, true)), (int)kHotThreads);
+        const uint32_t ref = std::min(S.ds.numNodes, plainRoom / (uint32_t)sizeof(GNode));
+        if (!ref || S.hot.share[ref - 1] < kHotAutoShare) return false;
+      }
+      const uint32_t wgs = grid(kern, threads, room);
+      if (S.opt.sayGrid) fprintf(stderr, "mi_raylib: grid %u workgroups of %u threads, %u hot nodes of %u that fit\n", wgs, threads, count, room / (uint32_t)sizeof(GNode));
+      hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), (size_t)count * sizeof(GNode), stream, S.hotView(), d_rays, cnt, workCounter, count, S.opt.tune, tileW, exs);
+      return true;
+    };
     if (S.opt.doubleFallback) {
       // the ALLOW_DOUBLE_FALLBACK=1 variant: the phase-scheduled kernel's 4-wave build with the binary64 edge functions compiled in
       go(path_trace_wavefront_kernel<STATS, false, 256, 4, false, 2, false, true>);
@@ -1432,13 +1535,20 @@ void launchWavefront(mi_scene& S, mi_trace_result* d_rays, uint32_t cnt, hipStre
       // registers at 80 and loses 8 % (test_scene.dae: 292 against 271 ms per 1000 spp, profiles/r05_k1w_leaf_ab.txt): not built.
       const bool lean = S.opt.leanHit && !S.ds.hasNormals;
       const bool rot = lean && S.opt.leafRot && S.ds.leavesRot != nullptr;
+      bool launched = false;
+      if (hotOn && rot) launched = goHot(MI_K1W_HOT(kHotThreads, false, true), kHotThreads);
+      else if (hotOn && !lean) launched = goHot(MI_K1W_HOT(kHotThreads, true, false), kHotThreads);
 #define MI_K1W(SL, BA, RO) path_trace_wavefront_kernel<false, false, 256, 6, false, SL, true, false, false, true, BA, RO>
-      if (plain) { if (rot) go(MI_K1W(0, false, true)); else if (lean) go(MI_K1W(0, false, false)); else go(MI_K1W(0, true, false)); }
+      if (launched) {}
+      else if (plain) { if (rot) go(MI_K1W(0, false, true)); else if (lean) go(MI_K1W(0, false, false)); else go(MI_K1W(0, true, false)); }
       else { if (rot) go(MI_K1W(1, false, true)); else if (lean) go(MI_K1W(1, false, false)); else go(MI_K1W(1, true, false)); }
 #undef MI_K1W
+    } else if (STATS && hotOn && goHot(path_trace_wavefront_kernel<true, false, 256, 4, false, 2, false, false, false, true, true, false, true>, 256)) {
+      // (the instrumented HOT build: the same walk of the private copies, its runs counted - mi_get_hot_stats)
     } else {
       go(path_trace_wavefront_kernel<STATS, false, 256>);               // the instrumented build (and, in the variants build, option waves = 4)
     }
+#undef MI_K1W_HOT
     if (segmented) hipLaunchKernelGGL(segment_combine_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream, d_rays, cnt, exs.segments, slot.d_segPart, segBase ? 1u : 0u);
   }
 }
@@ -2237,6 +2347,17 @@ int mi_get_pool_stats(mi_scene* scene, uint64_t stats[8]) {      // (zeros in a 
     unsigned long long h[32];
     HIP_CHECK(hipMemcpy(h, scene->d_counters, sizeof h, hipMemcpyDeviceToHost));
     for (int i = 0; i < 8; ++i) stats[i] = h[16 + i];
+  });
+}
+
+int mi_get_hot_stats(mi_scene* scene, uint64_t stats[5]) {
+  if (!scene || !stats) { g_err = "mi_get_hot_stats: null argument"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    HIP_CHECK(hipDeviceSynchronize());
+    unsigned long long h[32];
+    HIP_CHECK(hipMemcpy(h, scene->d_counters, sizeof h, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 5; ++i) stats[i] = h[24 + i];
   });
 }
 

@@ -110,12 +110,13 @@ constexpr WaveTune kDefaultTune = {8, 16, 24, 48, 3, 4, 6, 1, 1, 40, 0};      //
 // the three selects of the closest-hit update and three registers of the walk are dead weight there. Bit-identical by construction
 // (nothing reads them); launchWavefront picks it by the scene's hasNormals.
 template <bool STATS, bool LDS_NODES, int BLOCK, int WAVES_PER_SIMD = 4, bool SPEC = false, int SLOTS = 2, bool FIXED_TUNE = false, bool DF = false, bool FAST = false, bool MERGE = true,
-          bool BARY = true, bool ROT = false>
-__global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? WAVES_PER_SIMD : 1) path_trace_wavefront_kernel(DeviceScene sc, mi_trace_result* rays, uint32_t n,
+          bool BARY = true, bool ROT = false, bool HOT = false>
+__global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIMD > 4) ? WAVES_PER_SIMD : 1) path_trace_wavefront_kernel(DeviceScene sc, mi_trace_result* rays, uint32_t n,
                                                                    uint32_t* workCounter, uint32_t ldsNodeCount, WaveTune tuneArg, uint32_t tileStreamW, WaveExtras ex) {
   const WaveTune tune = FIXED_TUNE ? kDefaultTune : tuneArg;
+  static_assert(!HOT || (MERGE && !SPEC && !FAST && !LDS_NODES && !DF), "HOT is a form of the default kernel's plain-render builds");
   const bool slots = (SLOTS == 2) ? (ex.slotColor != nullptr) : (SLOTS == 1);
-  constexpr bool kFirstInSetup = SLOTS != 0 && MERGE && !SPEC && !FAST && !LDS_NODES && !DF;      // (see the cast set-up of the merged SHADE / GEN turn)
+  constexpr bool kFirstInSetup = SLOTS != 0 && MERGE && !SPEC && !FAST && !LDS_NODES && !DF && !HOT;      // (see the cast set-up of the merged SHADE / GEN turn)
   __shared__ float sinTbl[92];
   // the materials a hit is shaded with, when the scene has few (the built-in scenes have 8, test_scene.dae 9): SHADE
   // otherwise waits for two dependent global loads, leaf record then material
@@ -129,13 +130,18 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char dynLds[];
   load_sin_table(sinTbl);
-  if (LDS_NODES) {
-    // stage the first ldsNodeCount nodes (preorder prefix) once per workgroup, 16 B per lane per step
+  // HOT (scene option "hot_nodes"): sc.nodes / leaves / leavesRot / leafNormals are K1w's private, hot-first copies (hot_order.hpp)
+  // and the walk is layout-free: a lane that stops at a primitive stands AT its node, and takes the node that follows from the
+  // record's load. Every workgroup stages the first ldsNodeCount nodes of the copy; a run of box tests whose lanes all stand
+  // inside that prefix runs from LDS (the choice is wave-uniform, made once per run: no step ever pays for both paths).
+  if (LDS_NODES || HOT) {
+    // stage the first ldsNodeCount nodes (LDS_NODES: a preorder prefix of the shared array) once per workgroup, 16 B per lane per step
     const uint4* src = reinterpret_cast<const uint4*>(sc.nodes);
     uint4* dst = reinterpret_cast<uint4*>(dynLds);
     for (uint32_t k = threadIdx.x; k < ldsNodeCount * 2; k += blockDim.x) dst[k] = src[k];
     __syncthreads();
   }
+  const uint32_t hotBytes = HOT ? (ldsNodeCount << 5) : 0u;      // (the host keeps ldsNodeCount <= numNodes)
 
   const uint32_t lane = threadIdx.x & 63;
   const uint32_t fetchChunk = ex.fetchChunk ? ex.fetchChunk : 64u;
@@ -195,6 +201,8 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
   uint32_t casts = 0, paths = 0;       // wave-uniform: counted per turn from the turn's ballots, so they live in scalar registers
   // STATS only: per-wave phase executions and the lanes that were active in them (wave-uniform values)
   uint32_t itN = 0, itL = 0, itS = 0, itG = 0, lnN = 0, lnL = 0, lnS = 0, lnG = 0;
+  uint32_t itH = 0, lnH = 0, itC = 0, lnC = 0;      // (instrumented HOT build) box-test steps that ran from LDS and their lanes, the steps that ran from global memory and theirs
+  unsigned long long visHot = 0;      // ... and the box tests of nodes inside the staged prefix, whichever way they were loaded (per lane)
   uint32_t itQ = 0, lnQ = 0;      // (instrumented build) primitive-test turns that hold a sphere or disc lane, and those lanes
   unsigned long long tTrav = 0, tShade = 0, tGen = 0, tLoop0 = STATS ? __builtin_amdgcn_s_memtime() : 0ull;   // STATS: shader cycles per phase
 
@@ -314,16 +322,18 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
       // back-to-back tests narrow the exec mask from that condition directly instead of re-reading `ph`.
       // deferTag (the spelled-out run of box tests only): the lane's phase is not updated test by test; the phase of
       // every lane that took part is derived once, behind the run, from the node value it stopped with.
-      auto nodeBodyT = [&](auto exactTag, auto deferTag) -> bool {
+      auto nodeBodyT = [&](auto exactTag, auto deferTag, auto ldsTag) -> bool {
         {
           GNode nd;
           typedef uint32_t ProbeVec __attribute__((ext_vector_type(4)));
           ProbeVec probeLoad = {0u, 0u, 0u, 0u};
           if (!FIXED_TUNE && (tune.probe & 1u)) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(probeLoad) : "v"(node), "s"(sc.nodes) : "memory");
           // (uniform base + 32-bit byte offset: the load takes the scalar-base form, one shift instead of 64-bit address math)
-          if (LDS_NODES && node < (ldsNodeCount << 5)) nd = *reinterpret_cast<const GNode*>(dynLds + node);
+          if constexpr (HOT && decltype(ldsTag)::value) nd = *reinterpret_cast<const GNode*>(dynLds + node);       // (two ds_read_b128)
+          else if (LDS_NODES && node < (ldsNodeCount << 5)) nd = *reinterpret_cast<const GNode*>(dynLds + node);
           else nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + node);
           if (STATS) cs.nodes++;
+          if (STATS && HOT && node < hotBytes) visHot++;
           // Box test (CompactBVH2Node.cpp:5-22, intersectRaySlab CompactBVH2Node.hpp:14-50): box_hit_span of trace_kernels.hpp,
           // spelled out here because hipcc schedules this kernel differently when the same arithmetic comes through the helper.
           // Fast form: with finite origin and finite inverse direction no slab product can be NaN, and for
@@ -387,8 +397,9 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
           // so reads as "stop"). A lane that stops at a primitive stands at node = leaf + 1 once the flag is taken off:
           // the record it waits for is leaves[node - 1], nothing is carried from this step to the LEAF turn.
           node = boxHit ? nd.hit : nd.link;
+          // (an LDS run compares with the staged prefix's end instead: a cold node reads as "stop" too, and the lane stays in NODE)
           if constexpr (decltype(deferTag)::value) {
-            return node < numNodes;                              // the phase is derived once, behind the run of box tests
+            return node < ((HOT && decltype(ldsTag)::value) ? hotBytes : numNodes);      // the phase is derived once, behind the run of box tests
           } else {
             if (node & kLeafFlag) { node &= ~kLeafFlag; ph = PH_LEAF; return false; }
             if (node >= numNodes) { ph = PH_SHADE; return false; }
@@ -396,8 +407,12 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
           }
         }
       };
-      auto nodeBody = [&]() -> bool { return nodeBodyT(std::false_type{}, std::true_type{}); };               // the common case: no lane needs the literal test
-      auto nodeStep = [&]() { if (ph == PH_NODE) (void)(anyExact ? nodeBodyT(std::true_type{}, std::false_type{}) : nodeBodyT(std::false_type{}, std::false_type{})); };
+      auto nodeBody = [&]() -> bool { return nodeBodyT(std::false_type{}, std::true_type{}, std::false_type{}); };               // the common case: no lane needs the literal test
+      auto nodeBodyH = [&]() -> bool { return nodeBodyT(std::false_type{}, std::true_type{}, std::true_type{}); };             // ... and every lane of the run stands in the staged prefix (HOT)
+      auto nodeStep = [&]() { if (ph == PH_NODE) (void)(anyExact ? nodeBodyT(std::true_type{}, std::false_type{}, std::false_type{}) : nodeBodyT(std::false_type{}, std::false_type{}, std::false_type{})); };
+      // (instrumented HOT build: the same choice per step, so that the counters describe what the plain build does per run)
+      auto nodeStepH = [&]() { if (ph == PH_NODE && node < hotBytes) (void)nodeBodyT(std::false_type{}, std::false_type{}, std::true_type{}); };
+      auto coldLanes = [&]() -> unsigned long long { return __ballot(ph == PH_NODE && node >= hotBytes); };
       for (;;) {
         const uint32_t stay = cN;
         const uint32_t cP = SPEC ? (uint32_t)__popcll(__ballot(pend1 != 0xFFFFFFFFu)) : 0u;
@@ -409,12 +424,44 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
           const uint32_t extra = min(stay / tune.dbl, tune.maxExtra);       // wave-uniform
           if (STATS) {
             // instrumented build: the same tests, one exec region each, counted
+            if (HOT && !anyExact && coldLanes() == 0ull) {
+              // an LDS run, as the plain build takes it: the lanes that reach a cold node sit the rest of the run out
+              itH++; lnH += stay;
+              nodeStepH();
+              for (uint32_t e = 0; e < extra; ++e) {
+                const uint32_t in = (uint32_t)__popcll(__ballot(ph == PH_NODE && node < hotBytes));
+                itN++; lnN += in; itH++; lnH += in;
+                nodeStepH();
+              }
+            } else {
+            if (HOT) { itC++; lnC += stay; }
             nodeStep();
-            for (uint32_t e = 0; e < extra; ++e) { itN++; lnN += (uint32_t)__popcll(__ballot(ph == PH_NODE)); nodeStep(); }
+            for (uint32_t e = 0; e < extra; ++e) { const uint32_t in = (uint32_t)__popcll(__ballot(ph == PH_NODE)); itN++; lnN += in; if (HOT) { itC++; lnC += in; } nodeStep(); }
+            }
           } else if (anyExact) {
             // (a lane of this burst needs the literal compare/select box test: the rolled form carries it)
             nodeStep();
             for (uint32_t e = 0; e < extra; ++e) nodeStep();
+          } else if (HOT && coldLanes() == 0ull) {
+            // the same run with every load a pair of ds_read_b128 and the prefix's end for the array's: no lane of the wave stands at a cold node
+            if (ph == PH_NODE) {
+              bool go = nodeBodyH();
+              if (extra >= 1 && go) { go = nodeBodyH();
+                if (extra >= 2 && go) { go = nodeBodyH();
+                  if (extra >= 3 && go) { go = nodeBodyH();
+                    if (extra >= 4 && go) { go = nodeBodyH();
+                      if (extra >= 5 && go) { go = nodeBodyH();
+                        if (extra >= 6 && go) { go = nodeBodyH();
+                          if (extra >= 7 && go) (void)nodeBodyH();
+                        }
+                      }
+                    }
+                  }
+                }
+              }
+              ph = (node & kLeafFlag) ? PH_LEAF : ((node >= numNodes) ? PH_SHADE : PH_NODE);      // (a lane that stopped at a cold node stays in NODE)
+              node &= ~kLeafFlag;
+            }
           } else if (ph == PH_NODE) {
             // spelled out rather than looped: straight-line code, and each further test runs under the previous
             // one's "still walking" condition instead of re-reading `ph`
@@ -481,21 +528,25 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
           } else
           if (ph == PH_LEAF) {
             if (STATS) cs.leaves++;
-            const uint32_t atLeaf = (node >> 5) - 1u;   // the leaf the lane stopped at (its link is the node after it)
+            const uint32_t atLeaf = HOT ? (node >> 5) : (node >> 5) - 1u;   // the leaf the lane stopped at (its link is the node after it; HOT: the lane stands at the leaf itself)
+            const uint32_t recNode = HOT ? node : node - 32u;
             // (uniform base + 32-bit byte offset, as for the nodes: a 64-byte record per 32-byte node)
             GLeaf L;
             if constexpr (ROT) {
               // the block of the cast's shear axis: the same three loads (16 + 16 + 8 bytes), the vertices arrive rotated
-              const GLeafBlock B = *reinterpret_cast<const GLeafBlock*>(reinterpret_cast<const char*>(sc.leavesRot) + ((node - 32u) << 2) + sh.kz * 40u);
+              const GLeafBlock B = *reinterpret_cast<const GLeafBlock*>(reinterpret_cast<const char*>(sc.leavesRot) + (recNode << 2) + sh.kz * 40u);
               L.type = B.type;
 #pragma unroll
               for (int q = 0; q < 9; ++q) L.f[q] = B.f[q];
             } else {
-              L = *reinterpret_cast<const GLeaf*>(reinterpret_cast<const char*>(sc.leaves) + ((node - 32u) << 1));
+              L = *reinterpret_cast<const GLeaf*>(reinterpret_cast<const char*>(sc.leaves) + (recNode << 1));
             }
             float t, b0 = 0.f, b1 = 0.f, b2 = 0.f;
             bool cand;
-            const uint32_t kind = leaf_kind(L);
+            // HOT: the private records carry the node that follows the leaf - a pre-rotated block in its first word (kind in the low five
+            // bits, the successor's byte offset above), a plain record where the walk never reads (triBase: the same 16-byte load as primID)
+            const uint32_t kind = (HOT && ROT) ? (L.type & 31u) : leaf_kind(L);
+            if constexpr (HOT) node = ROT ? (L.type & ~31u) : L.triBase;
             if (STATS) { const unsigned long long qm = __ballot(kind != LEAF_TRI); itQ += qm ? 1u : 0u; lnQ += (uint32_t)__popcll(qm); }
             if (kind == LEAF_TRI) {
               if constexpr (ROT) t = intersect_triangle<DF, true>(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), permute_kz(o, sh.kz), sh, b0, b1, b2);
@@ -520,7 +571,7 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
           // so a box test follows at once (tune.leafThenNode) and the vote after it sees its outcome
           if (tune.leafThenNode) {
             if (STATS) { itN++; lnN += (uint32_t)__popcll(__ballot(ph == PH_NODE)); }
-            nodeStep();
+            nodeStep();      // (from global memory in the HOT builds too: with the choice the 80-register builds spill, and the frame is no faster - profiles/r06_k1w_hot_nodes_ab.txt)
             ++steps;
           }
         }
@@ -846,10 +897,18 @@ __global__ void __launch_bounds__(BLOCK, (BLOCK == 256 && WAVES_PER_SIMD > 4) ? 
     for (uint32_t k = envNext + lane; k < envEnd; k += 64u) ex.index[k] = k < padEnd ? envFill : kEnvHole;
   }
   flush_stats(sc, lane == 0 ? casts : 0u, cs, lane == 0 ? paths : 0u);
+  if (STATS && HOT) {
+    for (int off = 32; off > 0; off >>= 1) visHot += __shfl_down(visHot, off);
+    if (lane == 0) atomicAdd(&sc.counters[28], visHot);
+  }
   if (STATS && lane == 0) {
     atomicAdd(&sc.counters[4], (unsigned long long)itN); atomicAdd(&sc.counters[5], (unsigned long long)lnN);
     atomicAdd(&sc.counters[6], (unsigned long long)itL); atomicAdd(&sc.counters[7], (unsigned long long)lnL);
     atomicAdd(&sc.counters[16], (unsigned long long)itQ); atomicAdd(&sc.counters[17], (unsigned long long)lnQ);      // (read through mi_get_pool_stats: slots 0 and 1; the pool kernel is not this kernel)
+    if (HOT) {
+      atomicAdd(&sc.counters[24], (unsigned long long)itH); atomicAdd(&sc.counters[25], (unsigned long long)lnH);      // (slots of their own, read through mi_get_hot_stats)
+      atomicAdd(&sc.counters[26], (unsigned long long)itC); atomicAdd(&sc.counters[27], (unsigned long long)lnC);
+    }
     atomicAdd(&sc.counters[8], (unsigned long long)itS); atomicAdd(&sc.counters[9], (unsigned long long)lnS);
     atomicAdd(&sc.counters[10], (unsigned long long)itG); atomicAdd(&sc.counters[11], (unsigned long long)lnG);
     atomicAdd(&sc.counters[12], tTrav); atomicAdd(&sc.counters[13], tShade); atomicAdd(&sc.counters[14], tGen);
