@@ -298,6 +298,45 @@ enum { MI_SIGN_INSIDE = 0, MI_SIGN_DISTANCE = 1 };
 int mi_point_sign_device(mi_scene* scene, int kind, const void* d_points, void* d_out, const float dir[3], size_t n, void* hip_stream);
 int mi_point_sign(mi_scene* scene, int kind, const mi_point* points, void* out, const float dir[3], size_t n);
 
+/* Crossing lists: EVERY crossing of each of n caller-supplied rays with t_min < t < t_max, sorted along the ray (Open3D's
+ * list_intersections) - where a ray enters and leaves things, which mi_query (the first crossing) and mi_count_query (their number)
+ * cannot say. Two steps: the offsets of the rays' segments, then the fill of a buffer the caller sized from them.
+ * The record: t, the ids as mi_query_hit carries them, flags = 0 or MI_CROSS_FAR (a sphere's far root t1; its near root t0 carries
+ * 0), ray = the index of the ray the record belongs to. The empty record is {+inf, MI_INVALID_PRIM, MI_INVALID_GEOM,
+ * MI_FLAG_ESCAPED, ray}.
+ * Acceptance: a crossing is listed exactly when mi_count_query counts it - the same walk over the FIXED interval, the same box
+ * test, primitive test and double_fallback behaviour; a sphere gives both roots of the formula above with their t (sphere_roots in
+ * ipu_ray_lib_amd/csrc/cross_math.hpp, mi_sphere_roots_host in mi_scene_host.h). The set of crossings is therefore a function of
+ * the ray and the geometry alone, and the order is by a key of the crossing itself - t; then geom_id; then prim_id; then a sphere's
+ * near root before its far root (t compares as a float: -0 == +0) -, so a list is the same bytes after a refit, a rebuild or
+ * mi_scene_set_geometry of the same contents.
+ * mi_list_offsets_device: d_rays = n mi_ray, d_offsets = n + 1 uint64_t, DEVICE memory. d_offsets[0] = 0, d_offsets[i + 1] -
+ *   d_offsets[i] = the crossing count of ray i (mi_count_query's), d_offsets[n] = their total. 64 bit: no total overflows. Form: the
+ *   count walk, then a prefix sum in place (three small launches; scratch per stream, grown on demand, kept by the scene).
+ * mi_list_fill_device: d_offsets = n + 1 uint64_t, d_hits = `capacity` mi_crossing, DEVICE memory. Ray i owns the records
+ *   [d_offsets[i], d_offsets[i + 1]); len = that length, 0 for a decreasing pair. The segment receives the ray's crossings in
+ *   ascending order of the key; when the ray has more than len, the len smallest; when it has fewer, the rest is filled with the
+ *   empty record. NO record at an index >= capacity is ever written, whatever the offsets hold: a segment is cut at capacity (it
+ *   then holds the smallest crossings that fit). The offsets may come from mi_list_offsets_device - every crossing - or from the
+ *   caller: d_offsets[i] = K i gives the first K crossings of every ray, padded. Offsets made for one state of the scene and
+ *   filled against another are legal: truncated or padded segments. Offsets that make segments of different rays overlap give
+ *   unspecified records inside those segments, and still no write outside them.
+ *   Form: one thread per ray inserts each crossing at its sorted place in the ray's own segment: O(crossings x len) record moves.
+ * Host entries: the same on HOST buffers, synchronous, in batches of mi_scene_set_ray_batch rays; offsets and the `ray` field are
+ *   global across batches (`ray` is the index modulo 2^32). The device staging of the hits grows on demand and goes with the scene.
+ * Ordering, destruction and groups: those of mi_count_query_device. n == 0 is a no-op; an empty scene gives zero offsets and padded
+ * segments. MI_ERR_INVALID_ARG, before any device work and without reading the scene: a null scene or buffer, rays or hits that
+ * are not 16-byte aligned, offsets that are not 8-byte aligned, or more rays in one launch (host entries: in one batch) than the
+ * 32-bit work index allows (0xFFBFFFFF).
+ * Options: double_fallback applies; fast, query_kernel and query_tune do NOT. Counters: each of the four calls adds n to casts and,
+ * under full_stats, its box tests and primitive tests (the fill's equal the offsets' and mi_count_query's for the same rays). */
+typedef struct { float t; uint32_t primID; uint16_t geomID; uint16_t flags; uint32_t ray; } mi_crossing;   /* 16 B */
+#define MI_CROSS_FAR ((uint16_t)8)   /* a sphere's far root t1 */
+int mi_list_offsets_device(mi_scene* scene, const void* d_rays, uint64_t* d_offsets /* n + 1 */, size_t n, void* hip_stream);
+int mi_list_fill_device(mi_scene* scene, const void* d_rays, const uint64_t* d_offsets, mi_crossing* d_hits, size_t capacity, size_t n, void* hip_stream);
+int mi_list_offsets(mi_scene* scene, const mi_ray* rays, uint64_t* offsets /* n + 1 */, size_t n);
+int mi_list_fill(mi_scene* scene, const mi_ray* rays, const uint64_t* offsets, mi_crossing* hits, size_t capacity, size_t n);
+
 /* Geometry updates: new positions for the primitives of a live scene, the topology kept - triangles, geometry list, materials and
  * the BVH's shape - and every BVH box recomputed on the device (a refit: Embree's RTC_BUILD_QUALITY_REFIT commit, OptiX's
  * OPTIX_BUILD_OPERATION_UPDATE). Any pointer may be NULL = keep; a non-NULL array must have exactly the scene's count (a NULL array

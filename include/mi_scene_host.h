@@ -116,6 +116,13 @@ int mi_point_query_host(const mi_scene_desc* desc, int kind, const mi_point* poi
 uint32_t mi_sphere_crossings_host(const float centre[3], float radius2, const float origin[3], const float direction[3],
                                   float t_min, float t_max);
 
+/* The same crossings with their t, as a crossing list reports them (mi_list_fill, mi_raylib.h; sphere_roots of cross_math.hpp): a
+ * mask of the accepted roots - bit 0: the near root, written to t[0]; bit 1: the far root (MI_CROSS_FAR), written to t[1] -, whose
+ * number of set bits is mi_sphere_crossings_host of the same arguments. A line that misses the sphere leaves t as it was. A null
+ * pointer gives 0. */
+uint32_t mi_sphere_roots_host(const float centre[3], float radius2, const float origin[3], const float direction[3],
+                              float t_min, float t_max, float t[2]);
+
 /* The hot-first order of the private copy of the walk's arrays that plain renders may walk (scene option "hot_nodes", mi_raylib.h),
  * from the functions the device library's upload runs (ipu_ray_lib_amd/csrc/hot_order.hpp). For num_nodes compact nodes (a depth-first
  * BVH2) it writes, each num_nodes entries long: preorder - the 32-byte device nodes of the shared array (six floats min/max per axis,

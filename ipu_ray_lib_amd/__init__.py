@@ -48,11 +48,16 @@ POINT = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("radius", "<f4")])
 POINT_HIT = np.dtype([("dist", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("point", VEC3),
                       ("b1", "<f4"), ("b2", "<f4")])
 
+# mi_crossing: one record of a crossing list (IpuScene.list_crossings / first_crossings / list_fill_device)
+CROSSING = np.dtype([("t", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("ray", "<u4")])
+
+assert CROSSING.itemsize == 16
 assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
 assert POINT.itemsize == 16 and POINT_HIT.itemsize == 32
 assert BVH_NODE.itemsize == 24 and MATERIAL.itemsize == 36 and MESH_INFO.itemsize == 16 and GEOM_REF.itemsize == 4
 
 FLAG_ERROR, FLAG_ESCAPED, FLAG_INSIDE = 1, 2, 4
+CROSS_FAR = 8      # MI_CROSS_FAR: a crossing record's flag for a sphere's far root
 INVALID_GEOM, INVALID_PRIM = 0xFFFF, 0xFFFFFFFF
 MODE_SHADOW_TRACE, MODE_PATH_TRACE = 0, 1
 QUERY_CLOSEST, QUERY_ANY = 0, 1
@@ -183,6 +188,8 @@ def host_lib() -> C.CDLL:
         lib.mi_point_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
+        lib.mi_sphere_roots_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)]
+        lib.mi_sphere_roots_host.restype = C.c_uint32
         lib.mi_hot_nodes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mi_hot_walk.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]
         lib.mi_hot_walk.restype = C.c_uint32
@@ -268,6 +275,10 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_point_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_count_query.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
         lib.mi_count_query_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_list_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_list_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_list_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        lib.mi_list_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         lib.mi_point_sign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t]
         lib.mi_point_sign_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
@@ -518,6 +529,17 @@ def sphere_crossings_host(centre, radius2, origin, direction, t_min=0.0, t_max=f
     c, o, d = ((C.c_float * 3)(*[float(np.float32(x)) for x in v]) for v in (centre, origin, direction))
     return int(host_lib().mi_sphere_crossings_host(c, C.c_float(float(np.float32(radius2))), o, d, C.c_float(float(np.float32(t_min))),
                                                    C.c_float(float(np.float32(t_max)))))
+
+
+def sphere_roots_host(centre, radius2, origin, direction, t_min=0.0, t_max=float("inf")):
+    """mi_sphere_roots_host: the crossings sphere_crossings_host counts, with their t, as a crossing list reports them. Returns
+    (mask, t0, t1): bit 0 of mask = the near root t0 is accepted, bit 1 = the far root t1 is (the one marked CROSS_FAR); t0 and t1
+    are binary32 values as Python floats, NaN when the line misses the sphere."""
+    c, o, d = ((C.c_float * 3)(*[float(np.float32(x)) for x in v]) for v in (centre, origin, direction))
+    t = (C.c_float * 2)(float("nan"), float("nan"))
+    mask = int(host_lib().mi_sphere_roots_host(c, C.c_float(float(np.float32(radius2))), o, d, C.c_float(float(np.float32(t_min))),
+                                               C.c_float(float(np.float32(t_max))), t))
+    return mask, float(t[0]), float(t[1])
 
 
 def _geometry_array(a, dtype, width):
@@ -834,6 +856,113 @@ class IpuScene:
         halves = raw.view(torch.int16)
         return {"dist": raw[:, 0], "inside": (halves[:, 5] & FLAG_INSIDE) != 0, "prim_id": words[:, 1],
                 "geom_id": halves[:, 4].to(torch.int32), "point": raw[:, 3:6]}
+
+    # -- crossing lists (mi_list_offsets*, mi_list_fill*): every crossing of every ray, sorted along the ray ------------------------------
+    @staticmethod
+    def _ray_source(rays: np.ndarray) -> np.ndarray:
+        assert rays.dtype == RAY and rays.ndim == 1
+        return rays if (rays.flags["C_CONTIGUOUS"] and rays.ctypes.data % 16 == 0) else _aligned_copy(rays)
+
+    def list_offsets(self, rays: np.ndarray) -> np.ndarray:
+        """mi_list_offsets: a uint64 array of rays.size + 1 offsets - 0, then the running total of count_crossings(rays)."""
+        src = self._ray_source(rays)
+        offsets = np.zeros(src.size + 1, np.uint64)
+        self._check(self._lib.mi_list_offsets(self._h, src.ctypes.data, offsets.ctypes.data, src.size))
+        return offsets
+
+    def list_fill(self, rays: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
+        """mi_list_fill: ray i's crossings, sorted, into hits[offsets[i]:offsets[i + 1]] (a CROSSING array at a 16-byte aligned
+        address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity` (None: hits.size) is written."""
+        src = self._ray_source(rays)
+        assert offsets.dtype == np.uint64 and offsets.ndim == 1 and offsets.size == src.size + 1 and offsets.flags["C_CONTIGUOUS"]
+        assert hits.dtype == CROSSING and hits.flags["C_CONTIGUOUS"]
+        capacity = hits.size if capacity is None else int(capacity)
+        assert 0 <= capacity <= hits.size
+        self._check(self._lib.mi_list_fill(self._h, src.ctypes.data, offsets.ctypes.data, hits.ctypes.data, capacity, src.size))
+        return hits
+
+    def list_crossings(self, rays: np.ndarray):
+        """Every surface each ray crosses with tMin < t < tMax (a RAY array, host memory), as (offsets, hits): offsets uint64
+        [n + 1], hits a CROSSING array of offsets[n] records; hits[offsets[i]:offsets[i + 1]] are ray i's crossings in ascending
+        order of t (then geomID, primID, a sphere's near root before its far root, which carries CROSS_FAR). The crossings are
+        those count_crossings counts. Synchronous; batched by setRayBatch."""
+        offsets = self.list_offsets(rays)
+        total = int(offsets[-1])
+        hits = aligned_bytes(max(total, 1) * CROSSING.itemsize).view(CROSSING)      # (the entry refuses a null buffer)
+        self.list_fill(rays, offsets, hits, total)
+        return offsets, hits[:total]
+
+    def first_crossings(self, rays: np.ndarray, k: int) -> np.ndarray:
+        """The first k crossings of every ray in that order: a CROSSING array [n, k]; rays with fewer are padded with the empty
+        record (t = +inf, INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
+        n, k = rays.size, int(k)
+        assert k >= 0
+        offsets = (np.arange(n + 1, dtype=np.uint64) * np.uint64(k)).astype(np.uint64)
+        hits = aligned_bytes(max(n * k, 1) * CROSSING.itemsize).view(CROSSING)
+        self.list_fill(rays, offsets, hits, n * k)
+        return hits[:n * k].reshape(n, k)
+
+    def list_offsets_device(self, d_rays: int, d_offsets: int, n: int, stream: int = 0):
+        """mi_list_offsets_device on device pointers (n RAY records in, n + 1 uint64 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_list_offsets_device(self._h, C.c_void_p(d_rays), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
+
+    def list_fill_device(self, d_rays: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
+        """mi_list_fill_device on device pointers (n RAY records and n + 1 uint64 in, `capacity` CROSSING records out), asynchronous
+        on `stream`."""
+        self._check(self._lib.mi_list_fill_device(self._h, C.c_void_p(d_rays), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
+                                                  int(n), C.c_void_p(stream)))
+
+    @staticmethod
+    def _torch_rays(what, origins, directions, t_min, t_max):
+        import torch
+        o = origins.to(torch.float32)
+        d = directions.to(torch.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape or not o.is_cuda or d.device != o.device:
+            raise ValueError(f"{what}: origins and directions must be [N, 3] tensors on one GPU")
+        n = o.shape[0]
+
+        def column(x):
+            return torch.as_tensor(x, dtype=torch.float32, device=o.device).expand(n).reshape(n, 1)
+
+        return torch.cat([o, column(t_min), d, column(t_max)], dim=1).contiguous(), n      # [N, 8] = n mi_ray
+
+    @staticmethod
+    def _crossing_columns(raw):
+        """The fields of [..., 4] int32 crossing records as tensors."""
+        import torch
+        halves = raw.view(torch.int16)
+        return {"ray_ids": raw[..., 3].to(torch.int64) & 0xFFFFFFFF, "t": raw.view(torch.float32)[..., 0], "prim_id": raw[..., 1],
+                "geom_id": halves[..., 4].to(torch.int32), "far": (halves[..., 5] & CROSS_FAR) != 0}
+
+    def cast_all(self, origins, directions, t_min=0.0, t_max=float("inf")) -> dict:
+        """Torch convenience over mi_list_offsets_device + mi_list_fill_device (Open3D's list_intersections): float32 device tensors
+        of shape [N, 3] (t_min / t_max: numbers or [N] tensors), enqueued on torch.cuda.current_stream(). It runs the offsets,
+        reads the total with one .item() (the one synchronisation), then allocates and fills. Returns device tensors: {"ray_splits"
+        [N + 1] int64, and per crossing, ray by ray in ascending t: "ray_ids" int64, "t", "prim_id" int32, "geom_id" int32, "far"
+        bool (a sphere's far root)}."""
+        import torch
+        rays, n = self._torch_rays("cast_all", origins, directions, t_min, t_max)
+        stream = torch.cuda.current_stream(rays.device).cuda_stream
+        splits = torch.zeros(n + 1, dtype=torch.int64, device=rays.device)
+        self.list_offsets_device(rays.data_ptr(), splits.data_ptr(), n, stream)
+        total = int(splits[-1].item())
+        raw = torch.empty((max(total, 1), 4), dtype=torch.int32, device=rays.device)
+        self.list_fill_device(rays.data_ptr(), splits.data_ptr(), raw.data_ptr(), total, n, stream)
+        out = self._crossing_columns(raw[:total])
+        out["ray_splits"] = splits
+        return out
+
+    def cast_first(self, origins, directions, k: int, t_min=0.0, t_max=float("inf")) -> dict:
+        """The first k crossings of every ray, as cast_all's fields with shape [N, k] (no "ray_splits"): rays with fewer are padded
+        with t = +inf and prim_id = geom_id = -1. One launch on torch.cuda.current_stream(), no synchronisation."""
+        import torch
+        rays, n = self._torch_rays("cast_first", origins, directions, t_min, t_max)
+        k = int(k)
+        stream = torch.cuda.current_stream(rays.device).cuda_stream
+        offsets = torch.arange(n + 1, dtype=torch.int64, device=rays.device) * k
+        raw = torch.empty((max(n * k, 1), 4), dtype=torch.int32, device=rays.device)
+        self.list_fill_device(rays.data_ptr(), offsets.data_ptr(), raw.data_ptr(), n * k, n, stream)
+        return self._crossing_columns(raw[:n * k].reshape(n, k, 4))
 
     # -- geometry updates (mi_scene_update*): new primitive positions, the BVH refit on the device ------------------------------------
     def update_geometry(self, vertices=None, normals=None, spheres=None, discs=None) -> "IpuScene":

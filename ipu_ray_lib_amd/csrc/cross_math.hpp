@@ -1,6 +1,7 @@
 // cross_math.hpp — the arithmetic of crossing counts that has no reference counterpart (mi_count_query / mi_point_sign,
 // include/mi_raylib.h): how often a ray crosses a sphere's shell inside its interval. One definition, compiled by hipcc for
-// count_crossings (count_kernels.hpp) and by g++ for mi_sphere_crossings_host (host/cross_host.cpp): a sequence of single
+// count_crossings (count_kernels.hpp) and list_crossings (list_kernels.hpp) and by g++ for mi_sphere_crossings_host and
+// mi_sphere_roots_host (host/cross_host.cpp): a sequence of single
 // binary32 operations in the order written (no contraction, correctly rounded divide and sqrt on both sides), so the two return
 // the same bits. A dot product is (x x' + y y') + z z' (ray_math.h dot).
 #pragma once
@@ -27,6 +28,23 @@ MI_HD uint32_t sphere_crossings(f3 c, float radius2, f3 o, f3 d, float tMin, flo
   const float td = sqrtf((radius2 - l2) / dd);
   const float t0 = tca - td, t1 = tca + td;
   return (uint32_t)(t0 > tMin && t0 < tMax) + (uint32_t)(t1 > tMin && t1 < tMax);
+}
+
+// The same crossings with their t, for the crossing lists (mi_list_fill, list_kernels.hpp): the operations of sphere_crossings in
+// the same order, so popcount(sphere_roots(...)) == sphere_crossings(...) bit for bit of every input. Returns a mask of the
+// accepted roots - bit 0: the near root t0, written to t[0]; bit 1: the far root t1, written to t[1] (the one a list marks
+// MI_CROSS_FAR). When the line misses the sphere (or l2 is NaN) t[] is left as it was and the mask is 0.
+MI_HD uint32_t sphere_roots(f3 c, float radius2, f3 o, f3 d, float tMin, float tMax, float t[2]) {
+  const f3 f = c - o;
+  const float dd = dot(d, d);
+  const float tca = dot(f, d) / dd;
+  const f3 l = f - d * tca;
+  const float l2 = dot(l, l);
+  if (!(l2 <= radius2)) return 0u;
+  const float td = sqrtf((radius2 - l2) / dd);
+  const float t0 = tca - td, t1 = tca + td;
+  t[0] = t0; t[1] = t1;
+  return (uint32_t)(t0 > tMin && t0 < tMax) | ((uint32_t)(t1 > tMin && t1 < tMax) << 1);
 }
 
 }  // namespace mi

@@ -20,6 +20,7 @@
 #include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
 #include "point_kernels.hpp"         // point queries: the nearest primitive of each given point (mi_point_query / mi_point_query_device)
 #include "count_kernels.hpp"         // crossing counts, inside tests and signed distance (mi_count_query*, mi_point_sign*)
+#include "list_kernels.hpp"          // crossing lists: offsets and the sorted fill (mi_list_offsets*, mi_list_fill*)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
 #include "canon_kernels.hpp"         // new contents for a live scene: the canonical primitive table on the device (mi_scene_set_geometry*)
@@ -336,6 +337,7 @@ struct LaunchSlot {
   float2* d_coords = nullptr; size_t coordsCap = 0;         // the stream's pixel coordinates, compact (WaveExtras::coords)
   uint32_t* d_poolScratch = nullptr; size_t poolScratchWords = 0;   // kernel 3 (variants build): [PG_WORDS][slots of the grid]
   hipEvent_t lastWork = nullptr;                              // recorded behind everything the scene enqueued on `stream` (launchRender): what ~mi_scene waits for
+  uint64_t* d_scanSums = nullptr; size_t scanSumsCap = 0;     // crossing lists (launchListOffsets): the tile sums of the prefix sum
 };
 
 struct mi_scene {
@@ -506,8 +508,8 @@ struct mi_scene {
     for (hipStream_t q : {nifSplitMlp, nifSplitTrace, debugStream}) if (q) (void)hipStreamDestroy(q);
     if (splitFirst) (void)hipEventDestroy(splitFirst);
     if (d_segTotal) (void)hipFree(d_segTotal);
-    for (LaunchSlot& l : slots) { if (l.lastWork) (void)hipEventDestroy(l.lastWork); if (l.d_workCounter) (void)hipFree(l.d_workCounter); if (l.d_segPart) (void)hipFree(l.d_segPart); if (l.d_coords) (void)hipFree(l.d_coords); if (l.d_poolScratch) (void)hipFree(l.d_poolScratch); }
-    for (int i = 0; i < 2; ++i) { if (d_qRays[i]) (void)hipFree(d_qRays[i]); if (d_qOut[i]) (void)hipFree(d_qOut[i]); }
+    for (LaunchSlot& l : slots) { if (l.lastWork) (void)hipEventDestroy(l.lastWork); if (l.d_workCounter) (void)hipFree(l.d_workCounter); if (l.d_segPart) (void)hipFree(l.d_segPart); if (l.d_coords) (void)hipFree(l.d_coords); if (l.d_poolScratch) (void)hipFree(l.d_poolScratch); if (l.d_scanSums) (void)hipFree(l.d_scanSums); }
+    for (int i = 0; i < 2; ++i) { if (d_qRays[i]) (void)hipFree(d_qRays[i]); if (d_qOut[i]) (void)hipFree(d_qOut[i]); if (d_listHits[i]) (void)hipFree(d_listHits[i]); }
     for (int i = 0; i < 2; ++i) { if (d_batch[i]) (void)hipFree(d_batch[i]); if (pipeStream[i]) (void)hipStreamDestroy(pipeStream[i]); }
     if (nifDone) (void)hipEventDestroy(nifDone);
     for (auto& e : nifTimes) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
@@ -533,6 +535,8 @@ struct mi_scene {
   }
   // the launch slot of a stream (created on first use; a scene is thread-compatible, not thread-safe)
   LaunchSlot& slotFor(hipStream_t stream);
+  // mi_list_fill's staging of a batch's records, one per pipeline slot, grown on demand (last: nothing before it moves)
+  mi_crossing* d_listHits[2] = {nullptr, nullptr}; size_t listHitsCap[2] = {0, 0};
 };
 
 LaunchSlot& mi_scene::slotFor(hipStream_t stream) {
@@ -1904,6 +1908,130 @@ void pipelinedQuery(mi_scene* scene, const void* in, size_t inSize, void* out, s
   } catch (...) { (void)hipDeviceSynchronize(); throw; }
 }
 
+// Crossing lists, step 1 (mi_list_offsets_device): d_incl[i] = the crossings of rays 0 .. i, i.e. the caller's offsets from their
+// second entry on. The count walk (list_count_kernel: count_crossings, builds picked as launchCountQuery picks them) writes the
+// counts as 64 bits, the prefix sum runs in place on them: tile sums -> their scan by one workgroup -> every tile's scan with its
+// base; a batch of one tile is the last launch alone. The tile sums live in the stream's launch slot: allocated when a call finds
+// too little room, never otherwise. Records the slot's lastWork event, as launchQuery does.
+void launchListOffsets(mi_scene& S, const mi_ray* d_rays, uint64_t* d_incl, size_t n, hipStream_t stream) {
+  if (n == 0) return;
+  if (n > kMaxWorkItems) throw ArgError("mi_list_offsets: more rays than one launch indexes (kMaxWorkItems)");
+  const uint32_t cnt = (uint32_t)n;
+  LaunchSlot& slot = S.slotFor(stream);
+  const uint32_t tiles = (cnt + kScanTile - 1) / kScanTile;
+  if (tiles > 1 && slot.scanSumsCap < tiles) {
+    if (slot.d_scanSums) { HIP_CHECK(hipStreamSynchronize(stream)); (void)hipFree(slot.d_scanSums); slot.d_scanSums = nullptr; slot.scanSumsCap = 0; }
+    const size_t room = std::max<size_t>(tiles, 1024);
+    HIP_CHECK(hipMalloc(&slot.d_scanSums, room * sizeof(uint64_t)));
+    slot.scanSumsCap = room;
+  }
+  const DeviceScene dsv = S.ds;
+  const dim3 block(256), grid((cnt + 255) / 256);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_rays, d_incl, cnt); };
+  if (S.opt.doubleFallback) go(list_count_kernel<false, true>);
+  else if (S.opt.fullStats) go(list_count_kernel<true, false>);
+  else go(list_count_kernel<false, false>);
+  HIP_CHECK(hipGetLastError());
+  if (tiles > 1) {
+    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(tiles), dim3(kScanThreads), 0, stream, d_incl, slot.d_scanSums, cnt);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanThreads), 0, stream, slot.d_scanSums, tiles);
+  }
+  hipLaunchKernelGGL(scan_apply_kernel, dim3(tiles), dim3(kScanThreads), 0, stream, d_incl, tiles > 1 ? slot.d_scanSums : nullptr, cnt);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
+}
+
+// Crossing lists, step 2 (mi_list_fill_device): list_fill_kernel, one thread per ray (list_kernels.hpp). rayBase: the index of the
+// launch's first ray in the caller's numbering (the host entry's batches). Builds as launchCountQuery; records lastWork.
+void launchListFill(mi_scene& S, const mi_ray* d_rays, const uint64_t* d_offsets, mi_crossing* d_hits, size_t capacity, uint32_t rayBase, size_t n, hipStream_t stream) {
+  if (n == 0) return;
+  if (n > kMaxWorkItems) throw ArgError("mi_list_fill: more rays than one launch indexes (kMaxWorkItems)");
+  const uint32_t cnt = (uint32_t)n;
+  LaunchSlot& slot = S.slotFor(stream);
+  const DeviceScene dsv = S.ds;
+  const dim3 block(256), grid((cnt + 255) / 256);
+  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_rays, d_offsets, d_hits, (uint64_t)capacity, rayBase, cnt); };
+  if (S.opt.doubleFallback) go(list_fill_kernel<false, true>);
+  else if (S.opt.fullStats) go(list_fill_kernel<true, false>);
+  else go(list_fill_kernel<false, false>);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
+}
+
+// Argument rules shared by the four crossing-list entries (hits: only the fill's); touches neither the scene nor a device.
+bool listArgsBad(const char* fn, const mi_scene* scene, const void* rays, const void* offsets, const void* hits, bool fill, size_t n, size_t limit) {
+  const char* why = nullptr;
+  if (!scene) why = "null scene";
+  else if (n == 0) return false;
+  else if (!rays || !offsets || (fill && !hits)) why = "null buffer";
+  else if ((uintptr_t)rays % 16) why = "rays must be 16-byte aligned";
+  else if ((uintptr_t)offsets % 8) why = "offsets must be 8-byte aligned";
+  else if (fill && (uintptr_t)hits % 16) why = "hits must be 16-byte aligned";
+  else if (n > limit) why = "more rays than one launch indexes (kMaxWorkItems)";
+  if (!why) return false;
+  g_err = std::string(fn) + ": " + why;
+  return true;
+}
+
+// mi_list_fill on host buffers: mi_query's pipeline (two slots, its ray and result buffers - the result buffer carries a batch's
+// offsets in) plus a staging buffer of records per slot. A batch's segments are packed from 0 in the staging - the device sees
+// offsets of its own, cut at `capacity` here already - and copied to where the caller's offsets put them: in one piece when the
+// batch's offsets ascend (neighbouring segments then touch), ray by ray otherwise.
+void listFillHost(mi_scene* scene, const mi_ray* rays, const uint64_t* offsets, mi_crossing* hits, size_t capacity, size_t n, size_t batch) {
+  HIP_CHECK(hipSetDevice(scene->device));
+  const size_t numBatches = (n + batch - 1) / batch;
+  const int slots = numBatches > 1 ? 2 : 1;
+  std::vector<uint64_t> local[2];
+  std::vector<mi_crossing> bounce;
+  try {
+    for (int i = 0; i < slots; ++i) {
+      if (scene->qCap[i] < batch) {
+        if (scene->d_qRays[i] || scene->d_qOut[i]) HIP_CHECK(hipDeviceSynchronize());
+        for (void** p : {&scene->d_qRays[i], &scene->d_qOut[i]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        scene->qCap[i] = 0;
+        HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * sizeof(mi_ray)));
+        HIP_CHECK(hipMalloc(&scene->d_qOut[i], batch * sizeof(mi_query_hit)));      // (room for batch + 1 offsets)
+        scene->qCap[i] = batch;
+      }
+      if (!scene->pipeStream[i]) HIP_CHECK(hipStreamCreateWithFlags(&scene->pipeStream[i], hipStreamNonBlocking));
+    }
+    for (size_t b = 0; b < numBatches; ++b) {
+      const int i = (int)(b % slots);
+      hipStream_t st = scene->pipeStream[i];
+      if (b >= (size_t)slots) HIP_CHECK(hipStreamSynchronize(st));      // local[i] and the staging are free again
+      const size_t first = b * batch, cnt = std::min(batch, n - first);
+      std::vector<uint64_t>& loc = local[i];
+      loc.resize(cnt + 1);
+      loc[0] = 0;
+      bool ascending = true;
+      for (size_t j = 0; j < cnt; ++j) {
+        const uint64_t lo = offsets[first + j], hi = offsets[first + j + 1];
+        ascending = ascending && hi >= lo;
+        loc[j + 1] = loc[j] + ((hi > lo && lo < capacity) ? std::min<uint64_t>(hi, capacity) - lo : 0);
+      }
+      const size_t need = (size_t)loc[cnt];
+      if (scene->listHitsCap[i] < need) {
+        if (scene->d_listHits[i]) { (void)hipFree(scene->d_listHits[i]); scene->d_listHits[i] = nullptr; scene->listHitsCap[i] = 0; }
+        HIP_CHECK(hipMalloc(&scene->d_listHits[i], need * sizeof(mi_crossing)));
+        scene->listHitsCap[i] = need;
+      }
+      HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], rays + first, cnt * sizeof(mi_ray), hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipMemcpyAsync(scene->d_qOut[i], loc.data(), (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      launchListFill(*scene, static_cast<const mi_ray*>(scene->d_qRays[i]), static_cast<const uint64_t*>(scene->d_qOut[i]), scene->d_listHits[i], need, (uint32_t)first, cnt, st);
+      if (!need) continue;
+      if (ascending) {
+        HIP_CHECK(hipMemcpyAsync(hits + offsets[first], scene->d_listHits[i], need * sizeof(mi_crossing), hipMemcpyDeviceToHost, st));
+      } else {
+        bounce.resize(need);
+        HIP_CHECK(hipMemcpyAsync(bounce.data(), scene->d_listHits[i], need * sizeof(mi_crossing), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (size_t j = 0; j < cnt; ++j) if (loc[j + 1] > loc[j]) std::memcpy(hits + offsets[first + j], bounce.data() + loc[j], (size_t)(loc[j + 1] - loc[j]) * sizeof(mi_crossing));
+      }
+    }
+    for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
+  } catch (...) { (void)hipDeviceSynchronize(); throw; }
+}
+
 // One wave that samples the work counter of `hip_stream`'s persistent launches `n` times, `period_ticks` (100-MHz ticks) apart, into
 // d_samples as pairs {s_memrealtime, counter}: how fast a launch hands its work units out over its life - the ramp at its start, the
 // moment the queue runs empty, the drain behind it (tools/launch_progress.py). It runs on a stream of the scene's own beside the launch it
@@ -2305,6 +2433,53 @@ int mi_point_sign(mi_scene* scene, int kind, const mi_point* points, void* out, 
       launchPointSign(*scene, kind, static_cast<const mi_point*>(d_in), d_out, d, cnt, st);
     });
   });
+}
+
+int mi_list_offsets_device(mi_scene* scene, const void* d_rays, uint64_t* d_offsets, size_t n, void* hip_stream) {
+  if (listArgsBad("mi_list_offsets_device", scene, d_rays, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
+    launchListOffsets(*scene, static_cast<const mi_ray*>(d_rays), d_offsets + 1, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_list_fill_device(mi_scene* scene, const void* d_rays, const uint64_t* d_offsets, mi_crossing* d_hits, size_t capacity, size_t n, void* hip_stream) {
+  if (listArgsBad("mi_list_fill_device", scene, d_rays, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    launchListFill(*scene, static_cast<const mi_ray*>(d_rays), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_list_offsets(mi_scene* scene, const mi_ray* rays, uint64_t* offsets, size_t n) {
+  if (listArgsBad("mi_list_offsets", scene, rays, offsets, nullptr, false, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  // (the host stream is cut into batches of mi_scene_set_ray_batch rays: the work-index limit applies per batch)
+  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
+  if (batch > kMaxWorkItems) { g_err = "mi_list_offsets: more rays per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    // every batch's prefix sum starts at 0 on the device; what precedes the batch is added here, batch by batch
+    offsets[0] = 0;
+    pipelinedQuery(scene, rays, sizeof(mi_ray), offsets + 1, sizeof(uint64_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchListOffsets(*scene, static_cast<const mi_ray*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
+    });
+    for (size_t first = batch; first < n; first += batch) {
+      const uint64_t base = offsets[first];
+      const size_t cnt = std::min(batch, n - first);
+      for (size_t j = 1; j <= cnt; ++j) offsets[first + j] += base;
+    }
+  });
+}
+
+int mi_list_fill(mi_scene* scene, const mi_ray* rays, const uint64_t* offsets, mi_crossing* hits, size_t capacity, size_t n) {
+  if (listArgsBad("mi_list_fill", scene, rays, offsets, hits, true, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
+  if (batch > kMaxWorkItems) { g_err = "mi_list_fill: more rays per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { listFillHost(scene, rays, offsets, hits, capacity, n, batch); });
 }
 
 int mi_scene_set_option(mi_scene* scene, const char* key, const char* value) {
