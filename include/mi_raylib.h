@@ -236,6 +236,56 @@ int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n)
 int mi_point_query_device(mi_scene* scene, int kind, const void* d_points, void* d_out, size_t n, void* hip_stream);
 int mi_point_query(mi_scene* scene, int kind, const mi_point* points, void* out, size_t n);
 
+/* Neighbour lists: EVERY primitive of the scene's CURRENT BVH strictly within the radius of each of n caller-supplied points, nearest
+ * first (PCL's radiusSearch / nearestKSearch, Open3D's search_radius_vector_3d / search_knn_vector_3d, trimesh's nearby_faces) -
+ * which mi_point_query (the nearest one, or whether there is one) cannot say. Two steps, as for the crossing lists (mi_list_*
+ * below): the offsets of the points' segments, then the fill of a buffer the caller sized from them.
+ * The record: dist2 = the SQUARED distance as the walk compares it (sqrtf is monotone but not injective: a list sorted by dist2 and
+ * stored as distances would hide its own tie order), the ids as mi_point_hit carries them, flags = 0, point = the index of the query
+ * the record belongs to. The empty record is {+inf, MI_INVALID_PRIM, MI_INVALID_GEOM, MI_FLAG_ESCAPED, point}. The closest point
+ * itself is not in the record.
+ * Acceptance: the walk, the box distance db, the closest point q of a primitive and d2 = dot(p - q, p - q) are mi_point_query's,
+ * in its arithmetic (ipu_ray_lib_amd/csrc/point_math.hpp); r2 = radius * radius. A primitive is a neighbour exactly when its leaf
+ * is reached and d2 < r2: strictly - a primitive exactly at the radius is not listed -, and a NaN d2 never qualifies. A query
+ * mi_point_query does not walk (a coordinate that is not finite, a NaN or negative radius) and an empty scene have no neighbours;
+ * radius = +inf is legal.
+ * Order: by a key of the neighbour itself - dist2 as a float; then geom_id; then prim_id -, NOT by visit order: a list is the same
+ * bytes after a refit, a rebuild or mi_scene_set_geometry of the same contents. MI_POINT_CLOSEST breaks ties by preorder instead, so
+ * on an exact tie of distances its answer and a list's first record can name different primitives (at the same distance).
+ * mi_near_offsets_device: d_points = n mi_point, d_offsets = n + 1 uint64_t, DEVICE memory. d_offsets[0] = 0, d_offsets[i + 1] -
+ *   d_offsets[i] = the number of neighbours of point i, d_offsets[n] = their total (64 bit). The count walk runs over the FIXED
+ *   bound: a node is entered when db < r2, so the set of neighbours is a function of the point and the geometry alone. Form: the
+ *   count walk, then the crossing lists' prefix sum in place (their scratch per stream).
+ * mi_near_fill_device: d_offsets = n + 1 uint64_t, d_hits = `capacity` mi_neighbour, DEVICE memory. Point i owns the records
+ *   [d_offsets[i], d_offsets[i + 1]) cut at capacity; len = that length, 0 for a decreasing pair or a start at or past capacity,
+ *   exactly as in mi_list_fill_device. NO record at an index >= capacity is ever written and none outside the segment, whatever the
+ *   offsets hold. A point with len == 0 is not walked. Otherwise one thread per point walks with held = 0 records in its segment:
+ *     a node is entered when db < r2 while held < len; once held == len, when db < r2 && db <= seg[len - 1].dist2 (<=: an
+ *     equal-distance primitive with smaller ids must still displace the last record);
+ *     an accepted neighbour (d2 < r2) is inserted at its sorted place in seg[0 .. held): appended while held < len; once held ==
+ *     len it is dropped when it does not sort before seg[len - 1], and otherwise displaces that record;
+ *   and what the walk leaves unused is padded with the empty record. The contract is THIS walk; mi_near_fill_host runs it
+ *   statement for statement. With offsets from mi_near_offsets* a segment is full only once the point's last neighbour is placed,
+ *   so the fill gives exactly the fixed-radius walk's list: every neighbour, sorted (the boxes it passes from then on hold no
+ *   neighbour; under full_stats it counts no more visits than the offsets' walk). With d_offsets[i] = K i it is a K-nearest query within the radius, padded; with
+ *   radius = +inf the K nearest primitives, at a cost that shrinks with the bound instead of a walk of the whole tree.
+ *   Mathematically the pruned result is the len smallest of the unpruned list; that is stated as a property, not as the definition,
+ *   because a box distance db and the distance d2 of a primitive inside the box are each rounded, and db <= d2 is not guaranteed to
+ *   the last ulp in binary32. Overlapping segments of different points give unspecified records inside them.
+ * Host entries: the same on HOST buffers, synchronous, in batches of mi_scene_set_ray_batch points; offsets and the `point` field
+ *   are global across batches (`point` is the index modulo 2^32). They share mi_list_fill's device staging.
+ * Ordering, destruction, groups, batches and stream rules: those of mi_point_query_device / mi_point_query. n == 0 is a no-op.
+ * MI_ERR_INVALID_ARG, before any device work and without reading the scene: a null scene or buffer, points or hits that are not
+ * 16-byte aligned, offsets that are not 8-byte aligned, or more points in one launch (host entries: in one batch) than the 32-bit
+ * work index allows (0xFFBFFFFF).
+ * Options: none apply (one kernel, one arithmetic, as for point queries). Counters: nothing is added to casts or paths; under
+ * full_stats the box tests are added to "nodes visited" and the primitive evaluations to "leaf tests". */
+typedef struct { float dist2; uint32_t primID; uint16_t geomID; uint16_t flags; uint32_t point; } mi_neighbour;   /* 16 B */
+int mi_near_offsets_device(mi_scene* scene, const void* d_points, uint64_t* d_offsets /* n + 1 */, size_t n, void* hip_stream);
+int mi_near_fill_device(mi_scene* scene, const void* d_points, const uint64_t* d_offsets, mi_neighbour* d_hits, size_t capacity, size_t n, void* hip_stream);
+int mi_near_offsets(mi_scene* scene, const mi_point* points, uint64_t* offsets /* n + 1 */, size_t n);
+int mi_near_fill(mi_scene* scene, const mi_point* points, const uint64_t* offsets, mi_neighbour* hits, size_t capacity, size_t n);
+
 /* Crossing counts: for each of n caller-supplied rays, how many surfaces of the scene's CURRENT BVH it crosses with t_min < t < t_max
  * (Open3D's count_intersections). A closest-hit cast prunes what lies behind its hit and cannot say this; callers of mi_query would
  * need one round trip per surface layer.

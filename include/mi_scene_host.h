@@ -109,6 +109,19 @@ double mi_bvh_cost_estimate(const double cost[3]);
  * leaf whose geometry, primitive or vertex index is out of range. */
 int mi_point_query_host(const mi_scene_desc* desc, int kind, const mi_point* points, void* out, size_t n, uint64_t visits[2]);
 
+/* Neighbour lists on the host: the twins of mi_near_offsets* / mi_near_fill* (mi_raylib.h, where the contract is written), over
+ * desc->bvh_nodes and desc's arrays as mi_point_query_host reads them and through the same code (point_math.hpp). offsets: n + 1
+ * uint64_t, written by mi_near_offsets_host (0, then the running total of the points' neighbour counts, the count walk over the
+ * fixed bound) and read by mi_near_fill_host, which runs the fill's walk - the bound lowered to the last record's dist2 once a
+ * segment is full - statement for statement and writes `hits` as the device writes it: nothing at or past `capacity`, nothing
+ * outside a segment, a point with an empty segment not walked. No alignment asked. They return the bytes the device returns;
+ * visits (may be NULL) receives {box tests, primitive evaluations} summed over the n points, what the device adds to "nodes visited"
+ * and "leaf tests" under option full_stats. MI_ERR_INVALID_ARG, with the function's name in mi_host_last_error: a null desc, a null
+ * buffer with n > 0, nodes that are not a depth-first BVH2, a leaf whose geometry, primitive or vertex index is out of range. */
+int mi_near_offsets_host(const mi_scene_desc* desc, const mi_point* points, uint64_t* offsets /* n + 1 */, size_t n, uint64_t visits[2]);
+int mi_near_fill_host(const mi_scene_desc* desc, const mi_point* points, const uint64_t* offsets, mi_neighbour* hits, size_t capacity,
+                      size_t n, uint64_t visits[2]);
+
 /* Sphere crossings on the host: how often the ray origin + t direction, t_min < t < t_max, crosses the shell of the sphere (centre,
  * radius2 = the squared radius) - 0, 1 or 2 -, from the definition the crossing-count kernels run (mi_count_query / mi_point_sign,
  * mi_raylib.h, where the formula is written; ipu_ray_lib_amd/csrc/cross_math.hpp). The triangle and disc tests of a crossing count

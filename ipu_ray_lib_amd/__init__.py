@@ -51,7 +51,10 @@ POINT_HIT = np.dtype([("dist", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("f
 # mi_crossing: one record of a crossing list (IpuScene.list_crossings / first_crossings / list_fill_device)
 CROSSING = np.dtype([("t", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("ray", "<u4")])
 
-assert CROSSING.itemsize == 16
+# mi_neighbour: one record of a neighbour list (IpuScene.neighbours / k_nearest / near_fill_device)
+NEIGHBOUR = np.dtype([("dist2", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("point", "<u4")])
+
+assert CROSSING.itemsize == 16 and NEIGHBOUR.itemsize == 16
 assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
 assert POINT.itemsize == 16 and POINT_HIT.itemsize == 32
 assert BVH_NODE.itemsize == 24 and MATERIAL.itemsize == 36 and MESH_INFO.itemsize == 16 and GEOM_REF.itemsize == 4
@@ -186,6 +189,8 @@ def host_lib() -> C.CDLL:
         lib.mi_build_lbvh_compact.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         lib.mi_canonical_prims.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         lib.mi_point_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_near_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_near_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
         lib.mi_sphere_roots_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)]
@@ -279,6 +284,10 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_list_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_list_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         lib.mi_list_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        lib.mi_near_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_near_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_near_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        lib.mi_near_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         lib.mi_point_sign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t]
         lib.mi_point_sign_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
@@ -490,6 +499,37 @@ def point_query_host(desc: SceneDesc, kind: int, points: np.ndarray):
     _check_host(host_lib().mi_point_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
                                                out.ctypes.data if src.size else None, src.size, visits))
     return (out.view(np.bool_) if kind == POINT_WITHIN else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def near_offsets_host(desc: SceneDesc, points: np.ndarray):
+    """mi_near_offsets_host: the host twin of IpuScene.near_offsets on desc's arrays and nodes - the same uint64 offsets. Returns
+    (offsets, visits), visits as point_query_host's."""
+    assert points.dtype == POINT and points.ndim == 1
+    src = np.ascontiguousarray(points)
+    offsets = np.zeros(src.size + 1, np.uint64)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_near_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
+    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def near_fill_host(desc: SceneDesc, points: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
+    """mi_near_fill_host: the host twin of IpuScene.near_fill - the same bytes. Returns (recs, visits): recs is `hits` (a NEIGHBOUR
+    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
+    nothing at or past `capacity` (None: recs.size) is written."""
+    assert points.dtype == POINT and points.ndim == 1
+    src = np.ascontiguousarray(points)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    assert offsets.ndim == 1 and offsets.size == src.size + 1
+    if hits is None:
+        size = int(offsets.max()) if capacity is None else int(capacity)
+        hits = np.zeros(max(size, 1), NEIGHBOUR)[:size]
+    assert hits.dtype == NEIGHBOUR and hits.flags["C_CONTIGUOUS"]
+    capacity = hits.size if capacity is None else int(capacity)
+    assert 0 <= capacity <= hits.size
+    visits = (C.c_uint64 * 2)()
+    base = hits.ctypes.data if hits.size else np.zeros(1, NEIGHBOUR).ctypes.data
+    _check_host(host_lib().mi_near_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
+    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
 
 
 DEVICE_NODE = np.dtype([("box", "<f4", (6,)), ("link", "<u4"), ("hit", "<u4")])     # the 32-byte device node: min/max per axis, two byte-offset successors
@@ -795,6 +835,114 @@ class IpuScene:
         halves = raw.view(torch.int16)
         return {"dist": raw[:, 0], "prim_id": words[:, 1], "geom_id": halves[:, 4].to(torch.int32),
                 "point": raw[:, 3:6], "bary": raw[:, 6:8]}
+
+    # -- neighbour lists (mi_near_offsets*, mi_near_fill*): every primitive within each point's radius, nearest first ---------------
+    @staticmethod
+    def _point_source(points: np.ndarray) -> np.ndarray:
+        assert points.dtype == POINT and points.ndim == 1
+        return points if (points.flags["C_CONTIGUOUS"] and points.ctypes.data % 16 == 0) else _aligned_copy(points)
+
+    def near_offsets(self, points: np.ndarray) -> np.ndarray:
+        """mi_near_offsets: a uint64 array of points.size + 1 offsets - 0, then the running total of the number of primitives
+        strictly within each point's radius (a POINT array, host memory)."""
+        src = self._point_source(points)
+        offsets = np.zeros(src.size + 1, np.uint64)
+        self._check(self._lib.mi_near_offsets(self._h, src.ctypes.data, offsets.ctypes.data, src.size))
+        return offsets
+
+    def near_fill(self, points: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
+        """mi_near_fill: point i's neighbours, nearest first, into hits[offsets[i]:offsets[i + 1]] (a NEIGHBOUR array at a 16-byte
+        aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity` (None: hits.size) is
+        written."""
+        src = self._point_source(points)
+        assert offsets.dtype == np.uint64 and offsets.ndim == 1 and offsets.size == src.size + 1 and offsets.flags["C_CONTIGUOUS"]
+        assert hits.dtype == NEIGHBOUR and hits.flags["C_CONTIGUOUS"]
+        capacity = hits.size if capacity is None else int(capacity)
+        assert 0 <= capacity <= hits.size
+        self._check(self._lib.mi_near_fill(self._h, src.ctypes.data, offsets.ctypes.data, hits.ctypes.data, capacity, src.size))
+        return hits
+
+    def neighbours(self, points: np.ndarray):
+        """Every primitive strictly within each point's radius (a POINT array, host memory), as (offsets, recs): offsets uint64
+        [n + 1], recs a NEIGHBOUR array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are point i's neighbours in ascending
+        order of dist2 (the SQUARED distance; then geomID, primID). Synchronous; batched by setRayBatch."""
+        offsets = self.near_offsets(points)
+        total = int(offsets[-1])
+        recs = aligned_bytes(max(total, 1) * NEIGHBOUR.itemsize).view(NEIGHBOUR)      # (the entry refuses a null buffer)
+        self.near_fill(points, offsets, recs, total)
+        return offsets, recs[:total]
+
+    def k_nearest(self, points: np.ndarray, k: int) -> np.ndarray:
+        """The k nearest primitives strictly within each point's radius, in that order: a NEIGHBOUR array [n, k]; points with fewer
+        are padded with the empty record (dist2 = +inf, INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass; the walk
+        shrinks its bound to the k-th distance kept, so radius = inf does not walk the whole tree."""
+        n, k = points.size, int(k)
+        assert k >= 0
+        offsets = (np.arange(n + 1, dtype=np.uint64) * np.uint64(k)).astype(np.uint64)
+        recs = aligned_bytes(max(n * k, 1) * NEIGHBOUR.itemsize).view(NEIGHBOUR)
+        self.near_fill(points, offsets, recs, n * k)
+        return recs[:n * k].reshape(n, k)
+
+    def near_offsets_device(self, d_points: int, d_offsets: int, n: int, stream: int = 0):
+        """mi_near_offsets_device on device pointers (n POINT records in, n + 1 uint64 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_near_offsets_device(self._h, C.c_void_p(d_points), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
+
+    def near_fill_device(self, d_points: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
+        """mi_near_fill_device on device pointers (n POINT records and n + 1 uint64 in, `capacity` NEIGHBOUR records out),
+        asynchronous on `stream`."""
+        self._check(self._lib.mi_near_fill_device(self._h, C.c_void_p(d_points), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
+                                                  int(n), C.c_void_p(stream)))
+
+    @staticmethod
+    def _torch_points(what, points, radius):
+        import torch
+        p = points.to(torch.float32)
+        if p.ndim != 2 or p.shape[1] != 3 or not p.is_cuda:
+            raise ValueError(f"{what}: points must be an [N, 3] tensor on a GPU")
+        n = p.shape[0]
+        r = torch.as_tensor(radius, dtype=torch.float32, device=p.device).expand(n).reshape(n, 1)
+        return torch.cat([p, r], dim=1).contiguous(), n      # [N, 4] = n mi_point
+
+    @staticmethod
+    def _neighbour_columns(raw):
+        """The fields of [..., 4] int32 neighbour records as tensors."""
+        import torch
+        halves = raw.view(torch.int16)
+        return {"point_ids": raw[..., 3].to(torch.int64) & 0xFFFFFFFF, "dist2": raw.view(torch.float32)[..., 0], "prim_id": raw[..., 1],
+                "geom_id": halves[..., 4].to(torch.int32)}
+
+    def ball_query(self, points, radius) -> dict:
+        """Torch convenience over mi_near_offsets_device + mi_near_fill_device (Open3D's search_radius_vector_3d): a float32 device
+        tensor of shape [N, 3] (radius: a number or an [N] tensor), enqueued on torch.cuda.current_stream(). It runs the offsets,
+        reads the total with one .item() (the one synchronisation), then allocates and fills. Returns device tensors: {"offsets"
+        [N + 1] int64, and per neighbour, point by point, nearest first: "point_ids" int64, "dist2" (squared), "prim_id" int32,
+        "geom_id" int32}."""
+        import torch
+        pts, n = self._torch_points("ball_query", points, radius)
+        stream = torch.cuda.current_stream(pts.device).cuda_stream
+        splits = torch.zeros(n + 1, dtype=torch.int64, device=pts.device)
+        self.near_offsets_device(pts.data_ptr(), splits.data_ptr(), n, stream)
+        total = int(splits[-1].item()) if n else 0
+        raw = torch.empty((max(total, 1), 4), dtype=torch.int32, device=pts.device)
+        self.near_fill_device(pts.data_ptr(), splits.data_ptr(), raw.data_ptr(), total, n, stream)
+        out = self._neighbour_columns(raw[:total])
+        out["offsets"] = splits
+        return out
+
+    def knn(self, points, k: int, radius=float("inf")) -> dict:
+        """The k nearest primitives of every point strictly within `radius`, as [N, k] columns {"dist2", "prim_id", "geom_id",
+        "point_ids"} and "offsets" [N + 1] int64 (= k i): points with fewer are padded with dist2 = +inf and prim_id = geom_id = -1.
+        One launch on torch.cuda.current_stream(), no synchronisation."""
+        import torch
+        pts, n = self._torch_points("knn", points, radius)
+        k = int(k)
+        stream = torch.cuda.current_stream(pts.device).cuda_stream
+        offsets = torch.arange(n + 1, dtype=torch.int64, device=pts.device) * k
+        raw = torch.empty((max(n * k, 1), 4), dtype=torch.int32, device=pts.device)
+        self.near_fill_device(pts.data_ptr(), offsets.data_ptr(), raw.data_ptr(), n * k, n, stream)
+        out = self._neighbour_columns(raw[:n * k].reshape(n, k, 4))
+        out["offsets"] = offsets
+        return out
 
     # -- crossing counts, inside tests, signed distance (mi_count_query*, mi_point_sign*) -----------------------------------------------
     def count_crossings(self, rays: np.ndarray) -> np.ndarray:

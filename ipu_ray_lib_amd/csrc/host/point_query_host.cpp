@@ -26,10 +26,10 @@ struct WalkNode {
   uint16_t geomID;
 };
 constexpr uint32_t kInterior = 0xFFFFFFFFu;
-}  // namespace
 
-void pointQueryHost(const mi_scene_desc& d, int kind, const mi_point* points, void* out, size_t n, uint64_t* visits) {
-  auto need = [](bool ok, const char* what) { if (!ok) throw std::invalid_argument(std::string("mi_point_query_host: ") + what); };
+// The walk's table of desc's nodes; fn: the entry's name, for the message of what is refused.
+std::vector<WalkNode> walkTable(const mi_scene_desc& d, const char* fn) {
+  auto need = [fn](bool ok, const char* what) { if (!ok) throw std::invalid_argument(std::string(fn) + ": " + what); };
   const uint32_t N = d.num_nodes;
   need(N == 0 || d.bvh_nodes, "bvh_nodes is null");
   need(d.num_geometry == 0 || d.geometry, "geometry is null");
@@ -82,6 +82,13 @@ void pointQueryHost(const mi_scene_desc& d, int kind, const mi_point* points, vo
     }
   }
   need(N == 0 || nodes[0].skip == N, "BVH root does not span the node array");
+  return nodes;
+}
+}  // namespace
+
+void pointQueryHost(const mi_scene_desc& d, int kind, const mi_point* points, void* out, size_t n, uint64_t* visits) {
+  const std::vector<WalkNode> nodes = walkTable(d, "mi_point_query_host");
+  const uint32_t N = d.num_nodes;
 
   uint64_t boxTests = 0, primEvals = 0;
   for (size_t k = 0; k < n; ++k) {
@@ -123,6 +130,98 @@ void pointQueryHost(const mi_scene_desc& d, int kind, const mi_point* points, vo
       h.dist = pt.radius; h.prim_id = MI_INVALID_PRIM; h.geom_id = MI_INVALID_GEOM; h.flags = MI_FLAG_ESCAPED;
     }
     memcpy(static_cast<char*>(out) + k * sizeof h, &h, sizeof h);      // (the caller's buffer need not be aligned)
+  }
+  if (visits) { visits[0] = boxTests; visits[1] = primEvals; }
+}
+
+// ---- neighbour lists: the host twins of near_count_kernel / near_fill_kernel (near_kernels.hpp, mi_near_offsets* / mi_near_fill*) ----
+namespace {
+// near_walk of near_kernels.hpp over the table: a node is entered when db < r2 && db <= bound (bound: +inf, or what accept lowered
+// it to); accept(d2, node index) for each primitive of a reached leaf with d2 < r2.
+template <class Accept>
+void nearWalk(const std::vector<WalkNode>& nodes, const mi_point& pt, float& bound, uint64_t& boxTests, uint64_t& primEvals, const Accept& accept) {
+  const f3 p = mk(pt.x, pt.y, pt.z);
+  const float r2 = pt.radius * pt.radius;
+  const uint32_t end = point_query_valid(p, pt.radius) ? (uint32_t)nodes.size() : 0u;
+  uint32_t i = 0;
+  while (i < end) {
+    const WalkNode& w = nodes[i];
+    ++boxTests;
+    const float db = point_box_dist2(w.minx, w.maxx, w.miny, w.maxy, w.minz, w.maxz, p);
+    const bool enter = db < r2 && db <= bound;
+    if (!enter) { i = w.skip; continue; }
+    if (w.kind == kInterior) { ++i; continue; }
+    ++primEvals;
+    const ClosestPoint c = closest_on_prim(w.kind, w.f, p);
+    const float d2 = point_dist2(p, c.q);
+    if (d2 < r2) accept(d2, i);
+    i = w.skip;
+  }
+}
+
+// a sorts before b: dist2 as a float, then geomID, then primID
+bool neighbourBefore(const mi_neighbour& a, const mi_neighbour& b) {
+  if (a.dist2 < b.dist2) return true;
+  if (!(a.dist2 == b.dist2)) return false;
+  return a.geomID != b.geomID ? a.geomID < b.geomID : a.primID < b.primID;
+}
+}  // namespace
+
+void nearOffsetsHost(const mi_scene_desc& d, const mi_point* points, uint64_t* offsets, size_t n, uint64_t* visits) {
+  const std::vector<WalkNode> nodes = walkTable(d, "mi_near_offsets_host");
+  uint64_t boxTests = 0, primEvals = 0, total = 0;
+  if (n) memcpy(offsets, &total, sizeof total);      // (the caller's buffers need not be aligned)
+  for (size_t k = 0; k < n; ++k) {
+    mi_point pt;
+    memcpy(&pt, points + k, sizeof pt);
+    float bound = kInf;
+    nearWalk(nodes, pt, bound, boxTests, primEvals, [&](float, uint32_t) { ++total; });
+    memcpy(reinterpret_cast<char*>(offsets) + (k + 1) * sizeof total, &total, sizeof total);
+  }
+  if (visits) { visits[0] = boxTests; visits[1] = primEvals; }
+}
+
+void nearFillHost(const mi_scene_desc& d, const mi_point* points, const uint64_t* offsets, mi_neighbour* hits, size_t capacity, size_t n, uint64_t* visits) {
+  const std::vector<WalkNode> nodes = walkTable(d, "mi_near_fill_host");
+  uint64_t boxTests = 0, primEvals = 0;
+  std::vector<mi_neighbour> seg;      // the point's segment, copied out once the walk is done (the caller's buffer need not be aligned)
+  for (size_t k = 0; k < n; ++k) {
+    uint64_t lo, hi;
+    memcpy(&lo, reinterpret_cast<const char*>(offsets) + k * sizeof lo, sizeof lo);
+    memcpy(&hi, reinterpret_cast<const char*>(offsets) + (k + 1) * sizeof hi, sizeof hi);
+    uint64_t len = 0;
+    if (hi > lo && lo < capacity) len = (hi < capacity ? hi : capacity) - lo;
+    if (!len) continue;
+    mi_point pt;
+    memcpy(&pt, points + k, sizeof pt);
+    seg.resize((size_t)len);
+    uint64_t held = 0;
+    mi_neighbour tail = {};
+    float bound = kInf;
+    nearWalk(nodes, pt, bound, boxTests, primEvals, [&](float d2, uint32_t at) {
+      const mi_neighbour rec = {d2, nodes[at].primID, nodes[at].geomID, 0, (uint32_t)k};
+      uint64_t j;
+      if (held < len) {
+        j = held++;
+      } else {
+        if (!neighbourBefore(rec, tail)) return;
+        j = len - 1;
+      }
+      const bool last = j == len - 1;
+      mi_neighbour end = rec;
+      while (j > 0) {
+        const mi_neighbour prev = seg[j - 1];
+        if (!neighbourBefore(rec, prev)) break;
+        seg[j] = prev;
+        if (j == len - 1) end = prev;
+        --j;
+      }
+      seg[j] = rec;
+      if (last) { tail = end; bound = end.dist2; }
+    });
+    const mi_neighbour pad = {kInf, MI_INVALID_PRIM, MI_INVALID_GEOM, MI_FLAG_ESCAPED, (uint32_t)k};
+    for (uint64_t j = held; j < len; ++j) seg[j] = pad;
+    memcpy(reinterpret_cast<char*>(hits) + lo * sizeof(mi_neighbour), seg.data(), (size_t)len * sizeof(mi_neighbour));
   }
   if (visits) { visits[0] = boxTests; visits[1] = primEvals; }
 }

@@ -167,6 +167,19 @@ int mi_point_query_host(const mi_scene_desc* desc, int kind, const mi_point* poi
   return guarded([&] { pointQueryHost(*desc, kind, points, out, n, visits); });
 }
 
+// Neighbour lists: the host twins of mi_near_offsets* / mi_near_fill* (point_query_host.cpp)
+int mi_near_offsets_host(const mi_scene_desc* desc, const mi_point* points, uint64_t* offsets, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_near_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!points || !offsets)) { g_err = "mi_near_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { nearOffsetsHost(*desc, points, offsets, n, visits); });
+}
+
+int mi_near_fill_host(const mi_scene_desc* desc, const mi_point* points, const uint64_t* offsets, mi_neighbour* hits, size_t capacity, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_near_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!points || !offsets || !hits)) { g_err = "mi_near_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { nearFillHost(*desc, points, offsets, hits, capacity, n, visits); });
+}
+
 // The canonical primitive table of desc's arrays: the host twin of canon_prim_kernel (canon_kernels.hpp, mi_scene_set_geometry*) -
 // the same prefix, the same search and record per canonical index (canon_prims.hpp), the same checks with mi_scene_create's words
 int mi_canonical_prims(const mi_scene_desc* desc, void* out, uint32_t capacity, uint32_t* count) {

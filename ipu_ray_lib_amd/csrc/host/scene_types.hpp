@@ -101,6 +101,9 @@ void refitCompactBvh(const mi_scene_desc& desc, mi_bvh_node* out);
 void buildLbvhCompact(const mi_scene_desc& desc, std::vector<mi_bvh_node>& nodes, uint32_t& maxDepth);
 // point_query_host.cpp: the host twin of mi_point_query (visits: {box tests, primitive evaluations}, may be null)
 void pointQueryHost(const mi_scene_desc& desc, int kind, const mi_point* points, void* out, size_t n, uint64_t* visits);
+// point_query_host.cpp: the host twins of mi_near_offsets / mi_near_fill (the same visits)
+void nearOffsetsHost(const mi_scene_desc& desc, const mi_point* points, uint64_t* offsets, size_t n, uint64_t* visits);
+void nearFillHost(const mi_scene_desc& desc, const mi_point* points, const uint64_t* offsets, mi_neighbour* hits, size_t capacity, size_t n, uint64_t* visits);
 
 // glb_reader.cpp: meshes of a glTF-binary file with node transforms baked in, file order kept
 std::vector<TriMesh> loadGlbMeshes(const std::string& path, bool loadNormals);

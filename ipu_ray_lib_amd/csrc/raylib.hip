@@ -21,6 +21,7 @@
 #include "point_kernels.hpp"         // point queries: the nearest primitive of each given point (mi_point_query / mi_point_query_device)
 #include "count_kernels.hpp"         // crossing counts, inside tests and signed distance (mi_count_query*, mi_point_sign*)
 #include "list_kernels.hpp"          // crossing lists: offsets and the sorted fill (mi_list_offsets*, mi_list_fill*)
+#include "near_kernels.hpp"          // neighbour lists: every primitive within a point's radius, nearest first (mi_near_offsets*, mi_near_fill*)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
 #include "canon_kernels.hpp"         // new contents for a live scene: the canonical primitive table on the device (mi_scene_set_geometry*)
@@ -535,7 +536,7 @@ struct mi_scene {
   }
   // the launch slot of a stream (created on first use; a scene is thread-compatible, not thread-safe)
   LaunchSlot& slotFor(hipStream_t stream);
-  // mi_list_fill's staging of a batch's records, one per pipeline slot, grown on demand (last: nothing before it moves)
+  // mi_list_fill's and mi_near_fill's staging of a batch's 16-byte records, one per pipeline slot, grown on demand (last: nothing before it moves)
   mi_crossing* d_listHits[2] = {nullptr, nullptr}; size_t listHitsCap[2] = {0, 0};
 };
 
@@ -1973,11 +1974,13 @@ bool listArgsBad(const char* fn, const mi_scene* scene, const void* rays, const 
   return true;
 }
 
-// mi_list_fill on host buffers: mi_query's pipeline (two slots, its ray and result buffers - the result buffer carries a batch's
+// mi_list_fill and mi_near_fill on host buffers (in: rays or points of inSize bytes; hits: 16-byte records of either kind;
+// launch(d_in, d_offsets, d_hits, capacity, base, cnt, stream) enqueues one batch's fill): mi_query's pipeline (two slots, its ray and result buffers - the result buffer carries a batch's
 // offsets in) plus a staging buffer of records per slot. A batch's segments are packed from 0 in the staging - the device sees
 // offsets of its own, cut at `capacity` here already - and copied to where the caller's offsets put them: in one piece when the
 // batch's offsets ascend (neighbouring segments then touch), ray by ray otherwise.
-void listFillHost(mi_scene* scene, const mi_ray* rays, const uint64_t* offsets, mi_crossing* hits, size_t capacity, size_t n, size_t batch) {
+template <class Launch>
+void listFillHost(mi_scene* scene, const void* in, size_t inSize, const uint64_t* offsets, mi_crossing* hits, size_t capacity, size_t n, size_t batch, const Launch& launch) {
   HIP_CHECK(hipSetDevice(scene->device));
   const size_t numBatches = (n + batch - 1) / batch;
   const int slots = numBatches > 1 ? 2 : 1;
@@ -2015,9 +2018,9 @@ void listFillHost(mi_scene* scene, const mi_ray* rays, const uint64_t* offsets, 
         HIP_CHECK(hipMalloc(&scene->d_listHits[i], need * sizeof(mi_crossing)));
         scene->listHitsCap[i] = need;
       }
-      HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], rays + first, cnt * sizeof(mi_ray), hipMemcpyHostToDevice, st));
+      HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], static_cast<const char*>(in) + first * inSize, cnt * inSize, hipMemcpyHostToDevice, st));
       HIP_CHECK(hipMemcpyAsync(scene->d_qOut[i], loc.data(), (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-      launchListFill(*scene, static_cast<const mi_ray*>(scene->d_qRays[i]), static_cast<const uint64_t*>(scene->d_qOut[i]), scene->d_listHits[i], need, (uint32_t)first, cnt, st);
+      launch(scene->d_qRays[i], static_cast<const uint64_t*>(scene->d_qOut[i]), scene->d_listHits[i], need, (uint32_t)first, cnt, st);
       if (!need) continue;
       if (ascending) {
         HIP_CHECK(hipMemcpyAsync(hits + offsets[first], scene->d_listHits[i], need * sizeof(mi_crossing), hipMemcpyDeviceToHost, st));
@@ -2030,6 +2033,65 @@ void listFillHost(mi_scene* scene, const mi_ray* rays, const uint64_t* offsets, 
     }
     for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
   } catch (...) { (void)hipDeviceSynchronize(); throw; }
+}
+
+// Neighbour lists, step 1 (mi_near_offsets_device): d_incl[i] = the neighbours of points 0 .. i, i.e. the caller's offsets from their
+// second entry on. near_count_kernel (near_kernels.hpp) writes the counts as 64 bits, the prefix sum is launchListOffsets': the same
+// kernels in place, the tile sums in the stream's launch slot. full_stats picks the instrumented build; no other option applies.
+void launchNearOffsets(mi_scene& S, const mi_point* d_points, uint64_t* d_incl, size_t n, hipStream_t stream) {
+  if (n == 0) return;
+  if (n > kMaxWorkItems) throw ArgError("mi_near_offsets: more points than one launch indexes (kMaxWorkItems)");
+  const uint32_t cnt = (uint32_t)n;
+  LaunchSlot& slot = S.slotFor(stream);
+  const uint32_t tiles = (cnt + kScanTile - 1) / kScanTile;
+  if (tiles > 1 && slot.scanSumsCap < tiles) {
+    if (slot.d_scanSums) { HIP_CHECK(hipStreamSynchronize(stream)); (void)hipFree(slot.d_scanSums); slot.d_scanSums = nullptr; slot.scanSumsCap = 0; }
+    const size_t room = std::max<size_t>(tiles, 1024);
+    HIP_CHECK(hipMalloc(&slot.d_scanSums, room * sizeof(uint64_t)));
+    slot.scanSumsCap = room;
+  }
+  const DeviceScene dsv = S.ds;
+  const dim3 block(256), grid((cnt + 255) / 256);
+  if (S.opt.fullStats) hipLaunchKernelGGL(near_count_kernel<true>, grid, block, 0, stream, dsv, d_points, d_incl, cnt);
+  else hipLaunchKernelGGL(near_count_kernel<false>, grid, block, 0, stream, dsv, d_points, d_incl, cnt);
+  HIP_CHECK(hipGetLastError());
+  if (tiles > 1) {
+    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(tiles), dim3(kScanThreads), 0, stream, d_incl, slot.d_scanSums, cnt);
+    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanThreads), 0, stream, slot.d_scanSums, tiles);
+  }
+  hipLaunchKernelGGL(scan_apply_kernel, dim3(tiles), dim3(kScanThreads), 0, stream, d_incl, tiles > 1 ? slot.d_scanSums : nullptr, cnt);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
+}
+
+// Neighbour lists, step 2 (mi_near_fill_device): near_fill_kernel, one thread per point (near_kernels.hpp). pointBase: the index of
+// the launch's first point in the caller's numbering (the host entry's batches). Records lastWork.
+void launchNearFill(mi_scene& S, const mi_point* d_points, const uint64_t* d_offsets, mi_neighbour* d_hits, size_t capacity, uint32_t pointBase, size_t n, hipStream_t stream) {
+  if (n == 0) return;
+  if (n > kMaxWorkItems) throw ArgError("mi_near_fill: more points than one launch indexes (kMaxWorkItems)");
+  const uint32_t cnt = (uint32_t)n;
+  LaunchSlot& slot = S.slotFor(stream);
+  const DeviceScene dsv = S.ds;
+  const dim3 block(256), grid((cnt + 255) / 256);
+  if (S.opt.fullStats) hipLaunchKernelGGL(near_fill_kernel<true>, grid, block, 0, stream, dsv, d_points, d_offsets, d_hits, (uint64_t)capacity, pointBase, cnt);
+  else hipLaunchKernelGGL(near_fill_kernel<false>, grid, block, 0, stream, dsv, d_points, d_offsets, d_hits, (uint64_t)capacity, pointBase, cnt);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
+}
+
+// Argument rules shared by the four neighbour-list entries (hits: only the fill's); touches neither the scene nor a device.
+bool nearArgsBad(const char* fn, const mi_scene* scene, const void* points, const void* offsets, const void* hits, bool fill, size_t n, size_t limit) {
+  const char* why = nullptr;
+  if (!scene) why = "null scene";
+  else if (n == 0) return false;
+  else if (!points || !offsets || (fill && !hits)) why = "null buffer";
+  else if ((uintptr_t)points % 16) why = "points must be 16-byte aligned";
+  else if ((uintptr_t)offsets % 8) why = "offsets must be 8-byte aligned";
+  else if (fill && (uintptr_t)hits % 16) why = "hits must be 16-byte aligned";
+  else if (n > limit) why = "more points than one launch indexes (kMaxWorkItems)";
+  if (!why) return false;
+  g_err = std::string(fn) + ": " + why;
+  return true;
 }
 
 // One wave that samples the work counter of `hip_stream`'s persistent launches `n` times, `period_ticks` (100-MHz ticks) apart, into
@@ -2479,7 +2541,63 @@ int mi_list_fill(mi_scene* scene, const mi_ray* rays, const uint64_t* offsets, m
   if (n == 0) return MI_OK;
   const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
   if (batch > kMaxWorkItems) { g_err = "mi_list_fill: more rays per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { listFillHost(scene, rays, offsets, hits, capacity, n, batch); });
+  return guarded([&] {
+    listFillHost(scene, rays, sizeof(mi_ray), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_crossing* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
+      launchListFill(*scene, static_cast<const mi_ray*>(d_in), d_off, d_hits, cap, base, cnt, st);
+    });
+  });
+}
+
+int mi_near_offsets_device(mi_scene* scene, const void* d_points, uint64_t* d_offsets, size_t n, void* hip_stream) {
+  if (nearArgsBad("mi_near_offsets_device", scene, d_points, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
+    launchNearOffsets(*scene, static_cast<const mi_point*>(d_points), d_offsets + 1, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_near_fill_device(mi_scene* scene, const void* d_points, const uint64_t* d_offsets, mi_neighbour* d_hits, size_t capacity, size_t n, void* hip_stream) {
+  if (nearArgsBad("mi_near_fill_device", scene, d_points, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return guarded([&] {
+    HIP_CHECK(hipSetDevice(scene->device));
+    launchNearFill(*scene, static_cast<const mi_point*>(d_points), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_near_offsets(mi_scene* scene, const mi_point* points, uint64_t* offsets, size_t n) {
+  if (nearArgsBad("mi_near_offsets", scene, points, offsets, nullptr, false, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  // (the host stream is cut into batches of mi_scene_set_ray_batch points: the work-index limit applies per batch)
+  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
+  if (batch > kMaxWorkItems) { g_err = "mi_near_offsets: more points per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    // every batch's prefix sum starts at 0 on the device; what precedes the batch is added here, batch by batch
+    offsets[0] = 0;
+    pipelinedQuery(scene, points, sizeof(mi_point), offsets + 1, sizeof(uint64_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchNearOffsets(*scene, static_cast<const mi_point*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
+    });
+    for (size_t first = batch; first < n; first += batch) {
+      const uint64_t base = offsets[first];
+      const size_t cnt = std::min(batch, n - first);
+      for (size_t j = 1; j <= cnt; ++j) offsets[first + j] += base;
+    }
+  });
+}
+
+int mi_near_fill(mi_scene* scene, const mi_point* points, const uint64_t* offsets, mi_neighbour* hits, size_t capacity, size_t n) {
+  if (nearArgsBad("mi_near_fill", scene, points, offsets, hits, true, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
+  if (batch > kMaxWorkItems) { g_err = "mi_near_fill: more points per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
+  static_assert(sizeof(mi_neighbour) == sizeof(mi_crossing), "the staging of the list fills holds 16-byte records of either kind");
+  return guarded([&] {
+    listFillHost(scene, points, sizeof(mi_point), offsets, reinterpret_cast<mi_crossing*>(hits), capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_crossing* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
+      launchNearFill(*scene, static_cast<const mi_point*>(d_in), d_off, reinterpret_cast<mi_neighbour*>(d_hits), cap, base, cnt, st);
+    });
+  });
 }
 
 int mi_scene_set_option(mi_scene* scene, const char* key, const char* value) {
