@@ -746,10 +746,119 @@ class IpuScene:
         """Trace a DEVICE-resident ray stream (e.g. a torch uint8 tensor's data_ptr) asynchronously."""
         self._check(self._lib.mi_render_device(self._h, mode, C.c_void_p(d_rays_ptr), n, C.c_void_p(stream)))
 
+    # -- what the query wrappers below share ---------------------------------------------------------------------------------------
+    @staticmethod
+    def _source(arr: np.ndarray, dtype) -> np.ndarray:
+        """A 1-d `dtype` array as the host entries take it: contiguous, at a 16-byte aligned address (a copy where it is not)."""
+        assert arr.dtype == dtype and arr.ndim == 1
+        return arr if (arr.flags["C_CONTIGUOUS"] and arr.ctypes.data % 16 == 0) else _aligned_copy(arr)
+
+    @staticmethod
+    def _torch_rays(what, origins, directions, t_min, t_max):
+        import torch
+        o = origins.to(torch.float32)
+        d = directions.to(torch.float32)
+        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape or not o.is_cuda or d.device != o.device:
+            raise ValueError(f"{what}: origins and directions must be [N, 3] tensors on one GPU")
+        n = o.shape[0]
+
+        def column(x):
+            return torch.as_tensor(x, dtype=torch.float32, device=o.device).expand(n).reshape(n, 1)
+
+        return torch.cat([o, column(t_min), d, column(t_max)], dim=1).contiguous(), n      # [N, 8] = n mi_ray
+
+    @staticmethod
+    def _torch_points(what, points, radius):
+        import torch
+        p = points.to(torch.float32)
+        if p.ndim != 2 or p.shape[1] != 3 or not p.is_cuda:
+            raise ValueError(f"{what}: points must be an [N, 3] tensor on a GPU")
+        n = p.shape[0]
+        r = torch.as_tensor(radius, dtype=torch.float32, device=p.device).expand(n).reshape(n, 1)
+        return torch.cat([p, r], dim=1).contiguous(), n      # [N, 4] = n mi_point
+
+    @staticmethod
+    def _torch_records(items, n, entry, *args):
+        """What `entry(*args, d_items, d_out, n, ..., stream)` writes as 32-byte records, on torch's current stream: an [N, 8]
+        float32 tensor; `_torch_flags`: its one byte per item, as bools."""
+        import torch
+        raw = torch.empty((n, 8), dtype=torch.float32, device=items.device)
+        entry(*args, items.data_ptr(), raw.data_ptr(), n, stream=torch.cuda.current_stream(items.device).cuda_stream)
+        return raw
+
+    @staticmethod
+    def _torch_flags(items, n, entry, *args):
+        import torch
+        out = torch.empty(n, dtype=torch.uint8, device=items.device)
+        entry(*args, items.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(items.device).cuda_stream)
+        return out.bool()
+
+    @staticmethod
+    def _hit_columns(raw, first, vector):
+        """The fields of [N, 8] float32 hit records (mi_query_hit, mi_point_hit) as tensors; `first`, `vector`: what the record's
+        first float and its three floats are called."""
+        import torch
+        words, halves = raw.view(torch.int32), raw.view(torch.int16)
+        return {first: raw[:, 0], "prim_id": words[:, 1], "geom_id": halves[:, 4].to(torch.int32), "flags": halves[:, 5],
+                vector: raw[:, 3:6], "bary": raw[:, 6:8]}
+
+    # the two list families (crossings of rays, neighbours of points) differ in their entries and their 16-byte record
+    def _offsets_host(self, entry, src: np.ndarray) -> np.ndarray:
+        offsets = np.zeros(src.size + 1, np.uint64)
+        self._check(entry(self._h, src.ctypes.data, offsets.ctypes.data, src.size))
+        return offsets
+
+    def _fill_host(self, entry, rec, src: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity) -> np.ndarray:
+        assert offsets.dtype == np.uint64 and offsets.ndim == 1 and offsets.size == src.size + 1 and offsets.flags["C_CONTIGUOUS"]
+        assert hits.dtype == rec and hits.flags["C_CONTIGUOUS"]
+        capacity = hits.size if capacity is None else int(capacity)
+        assert 0 <= capacity <= hits.size
+        self._check(entry(self._h, src.ctypes.data, offsets.ctypes.data, hits.ctypes.data, capacity, src.size))
+        return hits
+
+    @staticmethod
+    def _all_lists(offsets_of, fill, rec, items: np.ndarray):
+        offsets = offsets_of(items)
+        total = int(offsets[-1])
+        recs = aligned_bytes(max(total, 1) * rec.itemsize).view(rec)      # (the entry refuses a null buffer)
+        fill(items, offsets, recs, total)
+        return offsets, recs[:total]
+
+    @staticmethod
+    def _first_k(fill, rec, items: np.ndarray, k: int) -> np.ndarray:
+        n, k = items.size, int(k)
+        assert k >= 0
+        offsets = (np.arange(n + 1, dtype=np.uint64) * np.uint64(k)).astype(np.uint64)
+        recs = aligned_bytes(max(n * k, 1) * rec.itemsize).view(rec)
+        fill(items, offsets, recs, n * k)
+        return recs[:n * k].reshape(n, k)
+
+    @staticmethod
+    def _torch_all_lists(offsets_device, fill_device, items, n, sync_when_empty: bool):
+        """(offsets [N + 1] int64, records [total, 4] int32) on torch's current stream: the offsets, one .item() for the total,
+        then the fill."""
+        import torch
+        stream = torch.cuda.current_stream(items.device).cuda_stream
+        splits = torch.zeros(n + 1, dtype=torch.int64, device=items.device)
+        offsets_device(items.data_ptr(), splits.data_ptr(), n, stream)
+        total = int(splits[-1].item()) if (n or sync_when_empty) else 0
+        raw = torch.empty((max(total, 1), 4), dtype=torch.int32, device=items.device)
+        fill_device(items.data_ptr(), splits.data_ptr(), raw.data_ptr(), total, n, stream)
+        return splits, raw[:total]
+
+    @staticmethod
+    def _torch_first_k(fill_device, items, n, k: int):
+        """(offsets [N + 1] int64 = k i, records [N, k, 4] int32): one launch on torch's current stream, no synchronisation."""
+        import torch
+        k = int(k)
+        offsets = torch.arange(n + 1, dtype=torch.int64, device=items.device) * k
+        raw = torch.empty((max(n * k, 1), 4), dtype=torch.int32, device=items.device)
+        fill_device(items.data_ptr(), offsets.data_ptr(), raw.data_ptr(), n * k, n, torch.cuda.current_stream(items.device).cuda_stream)
+        return offsets, raw[:n * k].reshape(n, k, 4)
+
     # -- ray queries (mi_query / mi_query_device): CompactBvh::intersect / ::occluded per given ray, no shading --------------
     def _query_host(self, kind: int, rays: np.ndarray, out: np.ndarray) -> np.ndarray:
-        assert rays.dtype == RAY and rays.ndim == 1
-        src = rays if (rays.flags["C_CONTIGUOUS"] and rays.ctypes.data % 16 == 0) else _aligned_copy(rays)
+        src = self._source(rays, RAY)
         self._check(self._lib.mi_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
         return out
 
@@ -769,34 +878,15 @@ class IpuScene:
         """Torch convenience over mi_query_device: float32 device tensors of shape [N, 3] (t_min / t_max: numbers or [N]
         tensors), enqueued on torch.cuda.current_stream(). Returns device tensors: closest hit {"t" [N], "prim_id" [N] int32,
         "geom_id" [N] int32 (-1 on a miss, for both), "normal" [N, 3], "bary" [N, 2] (b1, b2)}; any hit {"occluded" [N] bool}."""
-        import torch
-        o = origins.to(torch.float32)
-        d = directions.to(torch.float32)
-        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape or not o.is_cuda or d.device != o.device:
-            raise ValueError("cast: origins and directions must be [N, 3] tensors on one GPU")
-        n = o.shape[0]
-
-        def column(x):
-            x = torch.as_tensor(x, dtype=torch.float32, device=o.device)
-            return x.expand(n).reshape(n, 1)
-
-        rays = torch.cat([o, column(t_min), d, column(t_max)], dim=1).contiguous()      # [N, 8] = n mi_ray
-        stream = torch.cuda.current_stream(o.device).cuda_stream
+        rays, n = self._torch_rays("cast", origins, directions, t_min, t_max)
         if any_hit:
-            out = torch.empty(n, dtype=torch.uint8, device=o.device)
-            self.query_device(QUERY_ANY, rays.data_ptr(), out.data_ptr(), n, stream)
-            return {"occluded": out.bool()}
-        raw = torch.empty((n, 8), dtype=torch.float32, device=o.device)
-        self.query_device(QUERY_CLOSEST, rays.data_ptr(), raw.data_ptr(), n, stream)
-        words = raw.view(torch.int32)
-        halves = raw.view(torch.int16)
-        return {"t": raw[:, 0], "prim_id": words[:, 1], "geom_id": halves[:, 4].to(torch.int32),
-                "normal": raw[:, 3:6], "bary": raw[:, 6:8]}
+            return {"occluded": self._torch_flags(rays, n, self.query_device, QUERY_ANY)}
+        cols = self._hit_columns(self._torch_records(rays, n, self.query_device, QUERY_CLOSEST), "t", "normal")
+        return {f: cols[f] for f in ("t", "prim_id", "geom_id", "normal", "bary")}
 
     # -- point queries (mi_point_query / mi_point_query_device): the nearest primitive within each point's radius -----------------
     def _point_query_host(self, kind: int, points: np.ndarray, out: np.ndarray) -> np.ndarray:
-        assert points.dtype == POINT and points.ndim == 1
-        src = points if (points.flags["C_CONTIGUOUS"] and points.ctypes.data % 16 == 0) else _aligned_copy(points)
+        src = self._source(points, POINT)
         self._check(self._lib.mi_point_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
         return out
 
@@ -817,71 +907,35 @@ class IpuScene:
         """Torch convenience over mi_point_query_device: a float32 device tensor of shape [N, 3] (radius: a number or an [N]
         tensor), enqueued on torch.cuda.current_stream(). Returns device tensors: {"dist" [N], "prim_id" [N] int32, "geom_id" [N]
         int32 (-1 when nothing was found, for both), "point" [N, 3], "bary" [N, 2] (b1, b2)}; within=True: {"within" [N] bool}."""
-        import torch
-        p = points.to(torch.float32)
-        if p.ndim != 2 or p.shape[1] != 3 or not p.is_cuda:
-            raise ValueError("nearest: points must be an [N, 3] tensor on a GPU")
-        n = p.shape[0]
-        r = torch.as_tensor(radius, dtype=torch.float32, device=p.device).expand(n).reshape(n, 1)
-        pts = torch.cat([p, r], dim=1).contiguous()      # [N, 4] = n mi_point
-        stream = torch.cuda.current_stream(p.device).cuda_stream
+        pts, n = self._torch_points("nearest", points, radius)
         if within:
-            out = torch.empty(n, dtype=torch.uint8, device=p.device)
-            self.point_query_device(POINT_WITHIN, pts.data_ptr(), out.data_ptr(), n, stream)
-            return {"within": out.bool()}
-        raw = torch.empty((n, 8), dtype=torch.float32, device=p.device)
-        self.point_query_device(POINT_CLOSEST, pts.data_ptr(), raw.data_ptr(), n, stream)
-        words = raw.view(torch.int32)
-        halves = raw.view(torch.int16)
-        return {"dist": raw[:, 0], "prim_id": words[:, 1], "geom_id": halves[:, 4].to(torch.int32),
-                "point": raw[:, 3:6], "bary": raw[:, 6:8]}
+            return {"within": self._torch_flags(pts, n, self.point_query_device, POINT_WITHIN)}
+        cols = self._hit_columns(self._torch_records(pts, n, self.point_query_device, POINT_CLOSEST), "dist", "point")
+        return {f: cols[f] for f in ("dist", "prim_id", "geom_id", "point", "bary")}
 
     # -- neighbour lists (mi_near_offsets*, mi_near_fill*): every primitive within each point's radius, nearest first ---------------
-    @staticmethod
-    def _point_source(points: np.ndarray) -> np.ndarray:
-        assert points.dtype == POINT and points.ndim == 1
-        return points if (points.flags["C_CONTIGUOUS"] and points.ctypes.data % 16 == 0) else _aligned_copy(points)
-
     def near_offsets(self, points: np.ndarray) -> np.ndarray:
         """mi_near_offsets: a uint64 array of points.size + 1 offsets - 0, then the running total of the number of primitives
         strictly within each point's radius (a POINT array, host memory)."""
-        src = self._point_source(points)
-        offsets = np.zeros(src.size + 1, np.uint64)
-        self._check(self._lib.mi_near_offsets(self._h, src.ctypes.data, offsets.ctypes.data, src.size))
-        return offsets
+        return self._offsets_host(self._lib.mi_near_offsets, self._source(points, POINT))
 
     def near_fill(self, points: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
         """mi_near_fill: point i's neighbours, nearest first, into hits[offsets[i]:offsets[i + 1]] (a NEIGHBOUR array at a 16-byte
         aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity` (None: hits.size) is
         written."""
-        src = self._point_source(points)
-        assert offsets.dtype == np.uint64 and offsets.ndim == 1 and offsets.size == src.size + 1 and offsets.flags["C_CONTIGUOUS"]
-        assert hits.dtype == NEIGHBOUR and hits.flags["C_CONTIGUOUS"]
-        capacity = hits.size if capacity is None else int(capacity)
-        assert 0 <= capacity <= hits.size
-        self._check(self._lib.mi_near_fill(self._h, src.ctypes.data, offsets.ctypes.data, hits.ctypes.data, capacity, src.size))
-        return hits
+        return self._fill_host(self._lib.mi_near_fill, NEIGHBOUR, self._source(points, POINT), offsets, hits, capacity)
 
     def neighbours(self, points: np.ndarray):
         """Every primitive strictly within each point's radius (a POINT array, host memory), as (offsets, recs): offsets uint64
         [n + 1], recs a NEIGHBOUR array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are point i's neighbours in ascending
         order of dist2 (the SQUARED distance; then geomID, primID). Synchronous; batched by setRayBatch."""
-        offsets = self.near_offsets(points)
-        total = int(offsets[-1])
-        recs = aligned_bytes(max(total, 1) * NEIGHBOUR.itemsize).view(NEIGHBOUR)      # (the entry refuses a null buffer)
-        self.near_fill(points, offsets, recs, total)
-        return offsets, recs[:total]
+        return self._all_lists(self.near_offsets, self.near_fill, NEIGHBOUR, points)
 
     def k_nearest(self, points: np.ndarray, k: int) -> np.ndarray:
         """The k nearest primitives strictly within each point's radius, in that order: a NEIGHBOUR array [n, k]; points with fewer
         are padded with the empty record (dist2 = +inf, INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass; the walk
         shrinks its bound to the k-th distance kept, so radius = inf does not walk the whole tree."""
-        n, k = points.size, int(k)
-        assert k >= 0
-        offsets = (np.arange(n + 1, dtype=np.uint64) * np.uint64(k)).astype(np.uint64)
-        recs = aligned_bytes(max(n * k, 1) * NEIGHBOUR.itemsize).view(NEIGHBOUR)
-        self.near_fill(points, offsets, recs, n * k)
-        return recs[:n * k].reshape(n, k)
+        return self._first_k(self.near_fill, NEIGHBOUR, points, k)
 
     def near_offsets_device(self, d_points: int, d_offsets: int, n: int, stream: int = 0):
         """mi_near_offsets_device on device pointers (n POINT records in, n + 1 uint64 out), asynchronous on `stream`."""
@@ -892,16 +946,6 @@ class IpuScene:
         asynchronous on `stream`."""
         self._check(self._lib.mi_near_fill_device(self._h, C.c_void_p(d_points), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
                                                   int(n), C.c_void_p(stream)))
-
-    @staticmethod
-    def _torch_points(what, points, radius):
-        import torch
-        p = points.to(torch.float32)
-        if p.ndim != 2 or p.shape[1] != 3 or not p.is_cuda:
-            raise ValueError(f"{what}: points must be an [N, 3] tensor on a GPU")
-        n = p.shape[0]
-        r = torch.as_tensor(radius, dtype=torch.float32, device=p.device).expand(n).reshape(n, 1)
-        return torch.cat([p, r], dim=1).contiguous(), n      # [N, 4] = n mi_point
 
     @staticmethod
     def _neighbour_columns(raw):
@@ -917,39 +961,23 @@ class IpuScene:
         reads the total with one .item() (the one synchronisation), then allocates and fills. Returns device tensors: {"offsets"
         [N + 1] int64, and per neighbour, point by point, nearest first: "point_ids" int64, "dist2" (squared), "prim_id" int32,
         "geom_id" int32}."""
-        import torch
         pts, n = self._torch_points("ball_query", points, radius)
-        stream = torch.cuda.current_stream(pts.device).cuda_stream
-        splits = torch.zeros(n + 1, dtype=torch.int64, device=pts.device)
-        self.near_offsets_device(pts.data_ptr(), splits.data_ptr(), n, stream)
-        total = int(splits[-1].item()) if n else 0
-        raw = torch.empty((max(total, 1), 4), dtype=torch.int32, device=pts.device)
-        self.near_fill_device(pts.data_ptr(), splits.data_ptr(), raw.data_ptr(), total, n, stream)
-        out = self._neighbour_columns(raw[:total])
-        out["offsets"] = splits
-        return out
+        splits, raw = self._torch_all_lists(self.near_offsets_device, self.near_fill_device, pts, n, sync_when_empty=False)
+        return {**self._neighbour_columns(raw), "offsets": splits}
 
     def knn(self, points, k: int, radius=float("inf")) -> dict:
         """The k nearest primitives of every point strictly within `radius`, as [N, k] columns {"dist2", "prim_id", "geom_id",
         "point_ids"} and "offsets" [N + 1] int64 (= k i): points with fewer are padded with dist2 = +inf and prim_id = geom_id = -1.
         One launch on torch.cuda.current_stream(), no synchronisation."""
-        import torch
         pts, n = self._torch_points("knn", points, radius)
-        k = int(k)
-        stream = torch.cuda.current_stream(pts.device).cuda_stream
-        offsets = torch.arange(n + 1, dtype=torch.int64, device=pts.device) * k
-        raw = torch.empty((max(n * k, 1), 4), dtype=torch.int32, device=pts.device)
-        self.near_fill_device(pts.data_ptr(), offsets.data_ptr(), raw.data_ptr(), n * k, n, stream)
-        out = self._neighbour_columns(raw[:n * k].reshape(n, k, 4))
-        out["offsets"] = offsets
-        return out
+        offsets, raw = self._torch_first_k(self.near_fill_device, pts, n, k)
+        return {**self._neighbour_columns(raw), "offsets": offsets}
 
     # -- crossing counts, inside tests, signed distance (mi_count_query*, mi_point_sign*) -----------------------------------------------
     def count_crossings(self, rays: np.ndarray) -> np.ndarray:
         """How many surfaces each ray crosses with tMin < t < tMax (a RAY array, host memory): a uint32 array. A sphere counts
         both of its roots. Synchronous; batched by setRayBatch."""
-        assert rays.dtype == RAY and rays.ndim == 1
-        src = rays if (rays.flags["C_CONTIGUOUS"] and rays.ctypes.data % 16 == 0) else _aligned_copy(rays)
+        src = self._source(rays, RAY)
         out = np.zeros(src.size, np.uint32)
         self._check(self._lib.mi_count_query(self._h, src.ctypes.data, out.ctypes.data, src.size))
         return out
@@ -964,8 +992,7 @@ class IpuScene:
         return None if direction is None else (C.c_float * 3)(*[float(x) for x in direction])
 
     def _point_sign_host(self, kind: int, points: np.ndarray, out: np.ndarray, direction) -> np.ndarray:
-        assert points.dtype == POINT and points.ndim == 1
-        src = points if (points.flags["C_CONTIGUOUS"] and points.ctypes.data % 16 == 0) else _aligned_copy(points)
+        src = self._source(points, POINT)
         self._check(self._lib.mi_point_sign(self._h, kind, src.ctypes.data, out.ctypes.data, self._direction(direction), src.size))
         return out
 
@@ -990,65 +1017,33 @@ class IpuScene:
         (radius: a number or an [N] tensor), enqueued on torch.cuda.current_stream(). Returns device tensors: {"dist" [N], signed:
         negative inside, "inside" [N] bool, "prim_id" [N] int32, "geom_id" [N] int32 (-1 when nothing was found, for both),
         "point" [N, 3]}."""
-        import torch
-        p = points.to(torch.float32)
-        if p.ndim != 2 or p.shape[1] != 3 or not p.is_cuda:
-            raise ValueError("sdf: points must be an [N, 3] tensor on a GPU")
-        n = p.shape[0]
-        r = torch.as_tensor(radius, dtype=torch.float32, device=p.device).expand(n).reshape(n, 1)
-        pts = torch.cat([p, r], dim=1).contiguous()      # [N, 4] = n mi_point
-        stream = torch.cuda.current_stream(p.device).cuda_stream
-        raw = torch.empty((n, 8), dtype=torch.float32, device=p.device)
-        self.point_sign_device(SIGN_DISTANCE, pts.data_ptr(), raw.data_ptr(), n, direction, stream)
-        words = raw.view(torch.int32)
-        halves = raw.view(torch.int16)
-        return {"dist": raw[:, 0], "inside": (halves[:, 5] & FLAG_INSIDE) != 0, "prim_id": words[:, 1],
-                "geom_id": halves[:, 4].to(torch.int32), "point": raw[:, 3:6]}
+        pts, n = self._torch_points("sdf", points, radius)
+        raw = self._torch_records(pts, n, lambda d_pts, d_out, cnt, stream: self.point_sign_device(SIGN_DISTANCE, d_pts, d_out, cnt, direction, stream))
+        cols = self._hit_columns(raw, "dist", "point")
+        return {"dist": cols["dist"], "inside": (cols["flags"] & FLAG_INSIDE) != 0, "prim_id": cols["prim_id"], "geom_id": cols["geom_id"],
+                "point": cols["point"]}
 
     # -- crossing lists (mi_list_offsets*, mi_list_fill*): every crossing of every ray, sorted along the ray ------------------------------
-    @staticmethod
-    def _ray_source(rays: np.ndarray) -> np.ndarray:
-        assert rays.dtype == RAY and rays.ndim == 1
-        return rays if (rays.flags["C_CONTIGUOUS"] and rays.ctypes.data % 16 == 0) else _aligned_copy(rays)
-
     def list_offsets(self, rays: np.ndarray) -> np.ndarray:
         """mi_list_offsets: a uint64 array of rays.size + 1 offsets - 0, then the running total of count_crossings(rays)."""
-        src = self._ray_source(rays)
-        offsets = np.zeros(src.size + 1, np.uint64)
-        self._check(self._lib.mi_list_offsets(self._h, src.ctypes.data, offsets.ctypes.data, src.size))
-        return offsets
+        return self._offsets_host(self._lib.mi_list_offsets, self._source(rays, RAY))
 
     def list_fill(self, rays: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
         """mi_list_fill: ray i's crossings, sorted, into hits[offsets[i]:offsets[i + 1]] (a CROSSING array at a 16-byte aligned
         address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity` (None: hits.size) is written."""
-        src = self._ray_source(rays)
-        assert offsets.dtype == np.uint64 and offsets.ndim == 1 and offsets.size == src.size + 1 and offsets.flags["C_CONTIGUOUS"]
-        assert hits.dtype == CROSSING and hits.flags["C_CONTIGUOUS"]
-        capacity = hits.size if capacity is None else int(capacity)
-        assert 0 <= capacity <= hits.size
-        self._check(self._lib.mi_list_fill(self._h, src.ctypes.data, offsets.ctypes.data, hits.ctypes.data, capacity, src.size))
-        return hits
+        return self._fill_host(self._lib.mi_list_fill, CROSSING, self._source(rays, RAY), offsets, hits, capacity)
 
     def list_crossings(self, rays: np.ndarray):
         """Every surface each ray crosses with tMin < t < tMax (a RAY array, host memory), as (offsets, hits): offsets uint64
         [n + 1], hits a CROSSING array of offsets[n] records; hits[offsets[i]:offsets[i + 1]] are ray i's crossings in ascending
         order of t (then geomID, primID, a sphere's near root before its far root, which carries CROSS_FAR). The crossings are
         those count_crossings counts. Synchronous; batched by setRayBatch."""
-        offsets = self.list_offsets(rays)
-        total = int(offsets[-1])
-        hits = aligned_bytes(max(total, 1) * CROSSING.itemsize).view(CROSSING)      # (the entry refuses a null buffer)
-        self.list_fill(rays, offsets, hits, total)
-        return offsets, hits[:total]
+        return self._all_lists(self.list_offsets, self.list_fill, CROSSING, rays)
 
     def first_crossings(self, rays: np.ndarray, k: int) -> np.ndarray:
         """The first k crossings of every ray in that order: a CROSSING array [n, k]; rays with fewer are padded with the empty
         record (t = +inf, INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
-        n, k = rays.size, int(k)
-        assert k >= 0
-        offsets = (np.arange(n + 1, dtype=np.uint64) * np.uint64(k)).astype(np.uint64)
-        hits = aligned_bytes(max(n * k, 1) * CROSSING.itemsize).view(CROSSING)
-        self.list_fill(rays, offsets, hits, n * k)
-        return hits[:n * k].reshape(n, k)
+        return self._first_k(self.list_fill, CROSSING, rays, k)
 
     def list_offsets_device(self, d_rays: int, d_offsets: int, n: int, stream: int = 0):
         """mi_list_offsets_device on device pointers (n RAY records in, n + 1 uint64 out), asynchronous on `stream`."""
@@ -1059,20 +1054,6 @@ class IpuScene:
         on `stream`."""
         self._check(self._lib.mi_list_fill_device(self._h, C.c_void_p(d_rays), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
                                                   int(n), C.c_void_p(stream)))
-
-    @staticmethod
-    def _torch_rays(what, origins, directions, t_min, t_max):
-        import torch
-        o = origins.to(torch.float32)
-        d = directions.to(torch.float32)
-        if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape or not o.is_cuda or d.device != o.device:
-            raise ValueError(f"{what}: origins and directions must be [N, 3] tensors on one GPU")
-        n = o.shape[0]
-
-        def column(x):
-            return torch.as_tensor(x, dtype=torch.float32, device=o.device).expand(n).reshape(n, 1)
-
-        return torch.cat([o, column(t_min), d, column(t_max)], dim=1).contiguous(), n      # [N, 8] = n mi_ray
 
     @staticmethod
     def _crossing_columns(raw):
@@ -1088,29 +1069,15 @@ class IpuScene:
         reads the total with one .item() (the one synchronisation), then allocates and fills. Returns device tensors: {"ray_splits"
         [N + 1] int64, and per crossing, ray by ray in ascending t: "ray_ids" int64, "t", "prim_id" int32, "geom_id" int32, "far"
         bool (a sphere's far root)}."""
-        import torch
         rays, n = self._torch_rays("cast_all", origins, directions, t_min, t_max)
-        stream = torch.cuda.current_stream(rays.device).cuda_stream
-        splits = torch.zeros(n + 1, dtype=torch.int64, device=rays.device)
-        self.list_offsets_device(rays.data_ptr(), splits.data_ptr(), n, stream)
-        total = int(splits[-1].item())
-        raw = torch.empty((max(total, 1), 4), dtype=torch.int32, device=rays.device)
-        self.list_fill_device(rays.data_ptr(), splits.data_ptr(), raw.data_ptr(), total, n, stream)
-        out = self._crossing_columns(raw[:total])
-        out["ray_splits"] = splits
-        return out
+        splits, raw = self._torch_all_lists(self.list_offsets_device, self.list_fill_device, rays, n, sync_when_empty=True)
+        return {**self._crossing_columns(raw), "ray_splits": splits}
 
     def cast_first(self, origins, directions, k: int, t_min=0.0, t_max=float("inf")) -> dict:
         """The first k crossings of every ray, as cast_all's fields with shape [N, k] (no "ray_splits"): rays with fewer are padded
         with t = +inf and prim_id = geom_id = -1. One launch on torch.cuda.current_stream(), no synchronisation."""
-        import torch
         rays, n = self._torch_rays("cast_first", origins, directions, t_min, t_max)
-        k = int(k)
-        stream = torch.cuda.current_stream(rays.device).cuda_stream
-        offsets = torch.arange(n + 1, dtype=torch.int64, device=rays.device) * k
-        raw = torch.empty((max(n * k, 1), 4), dtype=torch.int32, device=rays.device)
-        self.list_fill_device(rays.data_ptr(), offsets.data_ptr(), raw.data_ptr(), n * k, n, stream)
-        return self._crossing_columns(raw[:n * k].reshape(n, k, 4))
+        return self._crossing_columns(self._torch_first_k(self.list_fill_device, rays, n, k)[1])
 
     # -- geometry updates (mi_scene_update*): new primitive positions, the BVH refit on the device ------------------------------------
     def update_geometry(self, vertices=None, normals=None, spheres=None, discs=None) -> "IpuScene":

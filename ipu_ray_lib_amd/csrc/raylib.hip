@@ -17,11 +17,11 @@
 #include "trace_kernels.hpp"
 #include "trace_wavefront.hpp"
 #include "hot_order.hpp"
-#include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4 (mi_query / mi_query_device)
-#include "point_kernels.hpp"         // point queries: the nearest primitive of each given point (mi_point_query / mi_point_query_device)
-#include "count_kernels.hpp"         // crossing counts, inside tests and signed distance (mi_count_query*, mi_point_sign*)
-#include "list_kernels.hpp"          // crossing lists: offsets and the sorted fill (mi_list_offsets*, mi_list_fill*)
-#include "near_kernels.hpp"          // neighbour lists: every primitive within a point's radius, nearest first (mi_near_offsets*, mi_near_fill*)
+#include "query_kernels.hpp"         // ray queries: the one-thread-per-ray kernel and K4
+#include "point_kernels.hpp"         // point queries: the nearest primitive of each given point
+#include "count_kernels.hpp"         // crossing counts, inside tests and signed distance
+#include "list_kernels.hpp"          // crossing lists: offsets and the sorted fill
+#include "near_kernels.hpp"          // neighbour lists: every primitive within a point's radius, nearest first (these five: launched and entered in query_drivers.hpp, included below)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
 #include "canon_kernels.hpp"         // new contents for a live scene: the canonical primitive table on the device (mi_scene_set_geometry*)
@@ -338,7 +338,7 @@ struct LaunchSlot {
   float2* d_coords = nullptr; size_t coordsCap = 0;         // the stream's pixel coordinates, compact (WaveExtras::coords)
   uint32_t* d_poolScratch = nullptr; size_t poolScratchWords = 0;   // kernel 3 (variants build): [PG_WORDS][slots of the grid]
   hipEvent_t lastWork = nullptr;                              // recorded behind everything the scene enqueued on `stream` (launchRender): what ~mi_scene waits for
-  uint64_t* d_scanSums = nullptr; size_t scanSumsCap = 0;     // crossing lists (launchListOffsets): the tile sums of the prefix sum
+  uint64_t* d_scanSums = nullptr; size_t scanSumsCap = 0;     // crossing and neighbour lists (scanOffsets): the tile sums of the prefix sum
 };
 
 struct mi_scene {
@@ -537,7 +537,7 @@ struct mi_scene {
   // the launch slot of a stream (created on first use; a scene is thread-compatible, not thread-safe)
   LaunchSlot& slotFor(hipStream_t stream);
   // mi_list_fill's and mi_near_fill's staging of a batch's 16-byte records, one per pipeline slot, grown on demand (last: nothing before it moves)
-  mi_crossing* d_listHits[2] = {nullptr, nullptr}; size_t listHitsCap[2] = {0, 0};
+  void* d_listHits[2] = {nullptr, nullptr}; size_t listHitsCap[2] = {0, 0};
 };
 
 LaunchSlot& mi_scene::slotFor(hipStream_t stream) {
@@ -1713,387 +1713,6 @@ void launchRender(mi_scene& S, int mode, mi_trace_result* d_rays, size_t n, hipS
   HIP_CHECK(hipEventRecord(S.slotFor(stream).lastWork, stream));      // (~mi_scene waits for it)
 }
 
-// Ray queries (mi_query_device): closest hit (MI_QUERY_CLOSEST, n mi_query_hit) or any hit (MI_QUERY_ANY, n bytes) of n
-// caller-supplied rays. Option query_kernel picks the one-thread-per-ray kernel (0) or K4 (1); full_stats, double_fallback and
-// fast pick the build, as for renders (double_fallback has no instrumented build: it takes precedence, as in shadow-trace renders).
-// Records the slot's lastWork event: ~mi_scene waits for the launch.
-void launchQuery(mi_scene& S, int kind, const mi_ray* d_rays, void* d_out, size_t n, hipStream_t stream) {
-  if (n == 0) return;
-  if (n > kMaxWorkItems) throw ArgError("mi_query: more rays than one launch indexes (kMaxWorkItems)");
-  const uint32_t cnt = (uint32_t)n;
-  LaunchSlot& slot = S.slotFor(stream);
-  const DeviceScene dsv = S.ds;      // (queries always start at the root: root_start assumes tMin = 0, tMax = inf)
-  const bool any = kind == MI_QUERY_ANY;
-  if (S.opt.queryKernel == 0) {
-    const dim3 block(256), grid((cnt + 255) / 256);
-    auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_rays, d_out, cnt); };
-#define MI_QP(A) do { if (S.opt.doubleFallback) go(query_plain_kernel<A, false, true, false>); \
-                      else if (S.opt.fast) go(query_plain_kernel<A, false, false, true>); \
-                      else if (S.opt.fullStats) go(query_plain_kernel<A, true, false, false>); \
-                      else go(query_plain_kernel<A, false, false, false>); } while (0)
-    if (any) MI_QP(true); else MI_QP(false);
-#undef MI_QP
-  } else {
-    HIP_CHECK(hipMemsetAsync(slot.d_workCounter, 0, sizeof(uint32_t), stream));
-    // persistent grid: as many workgroups as stay resident, never more than the batch has rays for
-    auto go = [&](auto kern) {
-      const uint32_t perUnit = S.residentBlocks(reinterpret_cast<const void*>(kern), 256, 0);
-      const uint32_t wgs = (uint32_t)std::min<uint64_t>((cnt + 255) / 256, (uint64_t)S.cus() * perUnit);
-      if (S.opt.sayGrid) fprintf(stderr, "mi_raylib: query grid %u workgroups = %u units x %u resident\n", wgs, S.cus(), perUnit);
-      hipLaunchKernelGGL(kern, dim3(wgs), dim3(256), 0, stream, dsv, d_rays, d_out, cnt, slot.d_workCounter, S.opt.queryTune);
-    };
-#define MI_QW(A) do { if (S.opt.doubleFallback) go(query_wave_kernel<A, false, true, false>); \
-                      else if (S.opt.fast) go(query_wave_kernel<A, false, false, true>); \
-                      else if (S.opt.fullStats) go(query_wave_kernel<A, true, false, false>); \
-                      else go(query_wave_kernel<A, false, false, false>); } while (0)
-    if (any) MI_QW(true); else MI_QW(false);
-#undef MI_QW
-  }
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
-}
-
-// Argument rules shared by the two query entries; touches neither the scene nor a device.
-bool queryArgsBad(const char* fn, const mi_scene* scene, int kind, const void* rays, const void* out, size_t n, size_t limit) {
-  const char* why = nullptr;
-  if (!scene) why = "null scene";
-  else if (kind != MI_QUERY_CLOSEST && kind != MI_QUERY_ANY) why = "unknown query kind";
-  else if (n == 0) return false;
-  else if (!rays || !out) why = "null buffer";
-  else if ((uintptr_t)rays % 16 || (uintptr_t)out % 16) why = "buffers must be 16-byte aligned";
-  else if (n > limit) why = "more rays than one launch indexes (kMaxWorkItems)";
-  if (!why) return false;
-  g_err = std::string(fn) + ": " + why;
-  return true;
-}
-
-// Point queries (mi_point_query_device): the nearest primitive within each point's radius (MI_POINT_CLOSEST, n mi_point_hit) or
-// whether there is one (MI_POINT_WITHIN, n bytes), one thread per point (point_kernels.hpp). full_stats picks the instrumented
-// build; the arithmetic options and the query-kernel options do not apply. Records the slot's lastWork event, as launchQuery does:
-// ~mi_scene waits for the launch, and so do update, rebuild and set-geometry before they overwrite a record.
-void launchPointQuery(mi_scene& S, int kind, const mi_point* d_points, void* d_out, size_t n, hipStream_t stream) {
-  if (n == 0) return;
-  if (n > kMaxWorkItems) throw ArgError("mi_point_query: more points than one launch indexes (kMaxWorkItems)");
-  const uint32_t cnt = (uint32_t)n;
-  LaunchSlot& slot = S.slotFor(stream);
-  const DeviceScene dsv = S.ds;
-  const dim3 block(256), grid((cnt + 255) / 256);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_points, d_out, cnt); };
-  if (kind == MI_POINT_WITHIN) { if (S.opt.fullStats) go(point_query_kernel<true, true>); else go(point_query_kernel<true, false>); }
-  else { if (S.opt.fullStats) go(point_query_kernel<false, true>); else go(point_query_kernel<false, false>); }
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
-}
-
-// Argument rules shared by the two point-query entries; touches neither the scene nor a device.
-bool pointArgsBad(const char* fn, const mi_scene* scene, int kind, const void* points, const void* out, size_t n, size_t limit) {
-  const char* why = nullptr;
-  if (!scene) why = "null scene";
-  else if (kind != MI_POINT_CLOSEST && kind != MI_POINT_WITHIN) why = "unknown query kind";
-  else if (n == 0) return false;
-  else if (!points || !out) why = "null buffer";
-  else if ((uintptr_t)points % 16 || (kind == MI_POINT_CLOSEST && (uintptr_t)out % 16)) why = "buffers must be 16-byte aligned";
-  else if (n > limit) why = "more points than one launch indexes (kMaxWorkItems)";
-  if (!why) return false;
-  g_err = std::string(fn) + ": " + why;
-  return true;
-}
-
-// Crossing counts (mi_count_query_device): how many surfaces each of n caller-supplied rays crosses inside its interval, one thread
-// per ray (count_kernels.hpp). double_fallback and full_stats pick the build (double_fallback has no instrumented build: it takes
-// precedence, as in launchQuery); fast, query_kernel and query_tune do not apply. Records the slot's lastWork event, as launchQuery does.
-void launchCountQuery(mi_scene& S, const mi_ray* d_rays, uint32_t* d_counts, size_t n, hipStream_t stream) {
-  if (n == 0) return;
-  if (n > kMaxWorkItems) throw ArgError("mi_count_query: more rays than one launch indexes (kMaxWorkItems)");
-  const uint32_t cnt = (uint32_t)n;
-  LaunchSlot& slot = S.slotFor(stream);
-  const DeviceScene dsv = S.ds;
-  const dim3 block(256), grid((cnt + 255) / 256);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_rays, d_counts, cnt); };
-  if (S.opt.doubleFallback) go(count_query_kernel<false, true>);
-  else if (S.opt.fullStats) go(count_query_kernel<true, false>);
-  else go(count_query_kernel<false, false>);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
-}
-
-// Argument rules shared by the two count-query entries; touches neither the scene nor a device.
-bool countArgsBad(const char* fn, const mi_scene* scene, const void* rays, const void* counts, size_t n, size_t limit) {
-  const char* why = nullptr;
-  if (!scene) why = "null scene";
-  else if (n == 0) return false;
-  else if (!rays || !counts) why = "null buffer";
-  else if ((uintptr_t)rays % 16) why = "rays must be 16-byte aligned";
-  else if ((uintptr_t)counts % 4) why = "counts must be 4-byte aligned";
-  else if (n > limit) why = "more rays than one launch indexes (kMaxWorkItems)";
-  if (!why) return false;
-  g_err = std::string(fn) + ": " + why;
-  return true;
-}
-
-// Inside tests and signed distance (mi_point_sign_device). MI_SIGN_DISTANCE: the point query as mi_point_query_device launches it,
-// then point_sign_kernel, which walks the crossings of each point's ray along `dir` and marks the records of the points inside in
-// place; MI_SIGN_INSIDE: that walk alone, writing bytes. Both on `stream`, the slot's lastWork event behind the last launch.
-void launchPointSign(mi_scene& S, int kind, const mi_point* d_points, void* d_out, f3 dir, size_t n, hipStream_t stream) {
-  if (n == 0) return;
-  if (n > kMaxWorkItems) throw ArgError("mi_point_sign: more points than one launch indexes (kMaxWorkItems)");
-  const uint32_t cnt = (uint32_t)n;
-  LaunchSlot& slot = S.slotFor(stream);
-  const DeviceScene dsv = S.ds;
-  const dim3 block(256), grid((cnt + 255) / 256);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_points, d_out, dir, cnt); };
-#define MI_PS(D) do { if (S.opt.doubleFallback) go(point_sign_kernel<D, false, true>); \
-                      else if (S.opt.fullStats) go(point_sign_kernel<D, true, false>); \
-                      else go(point_sign_kernel<D, false, false>); } while (0)
-  if (kind == MI_SIGN_DISTANCE) {
-    auto first = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_points, d_out, cnt); };
-    if (S.opt.fullStats) first(point_query_kernel<false, true>); else first(point_query_kernel<false, false>);
-    HIP_CHECK(hipGetLastError());
-    MI_PS(true);
-  } else {
-    MI_PS(false);
-  }
-#undef MI_PS
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
-}
-
-// The direction of an inside test: the caller's three floats or the default; a zero, NaN or infinite component is refused (the
-// triangle test shears by the smallest signed component: an axis direction divides by zero there).
-constexpr float kDefaultInsideDir[3] = {1.0f, 0.70710678f, 0.57735027f};
-
-// Argument rules shared by the two point-sign entries; touches neither the scene nor a device.
-bool signArgsBad(const char* fn, const mi_scene* scene, int kind, const void* points, const void* out, const float* dir, size_t n, size_t limit) {
-  const char* why = nullptr;
-  if (!scene) why = "null scene";
-  else if (kind != MI_SIGN_INSIDE && kind != MI_SIGN_DISTANCE) why = "unknown sign kind";
-  else if (dir && !(dir[0] != 0.f && dir[1] != 0.f && dir[2] != 0.f && std::fabs(dir[0]) < kInf && std::fabs(dir[1]) < kInf && std::fabs(dir[2]) < kInf))
-    why = "a direction component is zero, NaN or infinite";
-  else if (n == 0) return false;
-  else if (!points || !out) why = "null buffer";
-  else if ((uintptr_t)points % 16 || (kind == MI_SIGN_DISTANCE && (uintptr_t)out % 16)) why = "buffers must be 16-byte aligned";
-  else if (n > limit) why = "more points than one launch indexes (kMaxWorkItems)";
-  if (!why) return false;
-  g_err = std::string(fn) + ": " + why;
-  return true;
-}
-
-// The host entries of the count and sign queries: mi_query's pipeline and its buffers (a slot holds `batch` 32-byte records in and
-// out: room for rays or points and any of the results). launch(in, out, cnt, stream) enqueues one batch.
-template <class Launch>
-void pipelinedQuery(mi_scene* scene, const void* in, size_t inSize, void* out, size_t outSize, size_t n, size_t batch, const Launch& launch) {
-  HIP_CHECK(hipSetDevice(scene->device));
-  const size_t numBatches = (n + batch - 1) / batch;
-  const int slots = numBatches > 1 ? 2 : 1;
-  try {
-    for (int i = 0; i < slots; ++i) {
-      if (scene->qCap[i] < batch) {
-        if (scene->d_qRays[i] || scene->d_qOut[i]) HIP_CHECK(hipDeviceSynchronize());
-        for (void** p : {&scene->d_qRays[i], &scene->d_qOut[i]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        scene->qCap[i] = 0;
-        HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * sizeof(mi_ray)));
-        HIP_CHECK(hipMalloc(&scene->d_qOut[i], batch * sizeof(mi_query_hit)));
-        scene->qCap[i] = batch;
-      }
-      if (!scene->pipeStream[i]) HIP_CHECK(hipStreamCreateWithFlags(&scene->pipeStream[i], hipStreamNonBlocking));
-    }
-    for (size_t b = 0; b < numBatches; ++b) {
-      const int i = (int)(b % slots);
-      hipStream_t st = scene->pipeStream[i];
-      const size_t first = b * batch, cnt = std::min(batch, n - first);
-      HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], static_cast<const char*>(in) + first * inSize, cnt * inSize, hipMemcpyHostToDevice, st));
-      launch(scene->d_qRays[i], scene->d_qOut[i], cnt, st);
-      HIP_CHECK(hipMemcpyAsync(static_cast<char*>(out) + first * outSize, scene->d_qOut[i], cnt * outSize, hipMemcpyDeviceToHost, st));
-    }
-    for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
-  } catch (...) { (void)hipDeviceSynchronize(); throw; }
-}
-
-// Crossing lists, step 1 (mi_list_offsets_device): d_incl[i] = the crossings of rays 0 .. i, i.e. the caller's offsets from their
-// second entry on. The count walk (list_count_kernel: count_crossings, builds picked as launchCountQuery picks them) writes the
-// counts as 64 bits, the prefix sum runs in place on them: tile sums -> their scan by one workgroup -> every tile's scan with its
-// base; a batch of one tile is the last launch alone. The tile sums live in the stream's launch slot: allocated when a call finds
-// too little room, never otherwise. Records the slot's lastWork event, as launchQuery does.
-void launchListOffsets(mi_scene& S, const mi_ray* d_rays, uint64_t* d_incl, size_t n, hipStream_t stream) {
-  if (n == 0) return;
-  if (n > kMaxWorkItems) throw ArgError("mi_list_offsets: more rays than one launch indexes (kMaxWorkItems)");
-  const uint32_t cnt = (uint32_t)n;
-  LaunchSlot& slot = S.slotFor(stream);
-  const uint32_t tiles = (cnt + kScanTile - 1) / kScanTile;
-  if (tiles > 1 && slot.scanSumsCap < tiles) {
-    if (slot.d_scanSums) { HIP_CHECK(hipStreamSynchronize(stream)); (void)hipFree(slot.d_scanSums); slot.d_scanSums = nullptr; slot.scanSumsCap = 0; }
-    const size_t room = std::max<size_t>(tiles, 1024);
-    HIP_CHECK(hipMalloc(&slot.d_scanSums, room * sizeof(uint64_t)));
-    slot.scanSumsCap = room;
-  }
-  const DeviceScene dsv = S.ds;
-  const dim3 block(256), grid((cnt + 255) / 256);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_rays, d_incl, cnt); };
-  if (S.opt.doubleFallback) go(list_count_kernel<false, true>);
-  else if (S.opt.fullStats) go(list_count_kernel<true, false>);
-  else go(list_count_kernel<false, false>);
-  HIP_CHECK(hipGetLastError());
-  if (tiles > 1) {
-    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(tiles), dim3(kScanThreads), 0, stream, d_incl, slot.d_scanSums, cnt);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanThreads), 0, stream, slot.d_scanSums, tiles);
-  }
-  hipLaunchKernelGGL(scan_apply_kernel, dim3(tiles), dim3(kScanThreads), 0, stream, d_incl, tiles > 1 ? slot.d_scanSums : nullptr, cnt);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
-}
-
-// Crossing lists, step 2 (mi_list_fill_device): list_fill_kernel, one thread per ray (list_kernels.hpp). rayBase: the index of the
-// launch's first ray in the caller's numbering (the host entry's batches). Builds as launchCountQuery; records lastWork.
-void launchListFill(mi_scene& S, const mi_ray* d_rays, const uint64_t* d_offsets, mi_crossing* d_hits, size_t capacity, uint32_t rayBase, size_t n, hipStream_t stream) {
-  if (n == 0) return;
-  if (n > kMaxWorkItems) throw ArgError("mi_list_fill: more rays than one launch indexes (kMaxWorkItems)");
-  const uint32_t cnt = (uint32_t)n;
-  LaunchSlot& slot = S.slotFor(stream);
-  const DeviceScene dsv = S.ds;
-  const dim3 block(256), grid((cnt + 255) / 256);
-  auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, block, 0, stream, dsv, d_rays, d_offsets, d_hits, (uint64_t)capacity, rayBase, cnt); };
-  if (S.opt.doubleFallback) go(list_fill_kernel<false, true>);
-  else if (S.opt.fullStats) go(list_fill_kernel<true, false>);
-  else go(list_fill_kernel<false, false>);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
-}
-
-// Argument rules shared by the four crossing-list entries (hits: only the fill's); touches neither the scene nor a device.
-bool listArgsBad(const char* fn, const mi_scene* scene, const void* rays, const void* offsets, const void* hits, bool fill, size_t n, size_t limit) {
-  const char* why = nullptr;
-  if (!scene) why = "null scene";
-  else if (n == 0) return false;
-  else if (!rays || !offsets || (fill && !hits)) why = "null buffer";
-  else if ((uintptr_t)rays % 16) why = "rays must be 16-byte aligned";
-  else if ((uintptr_t)offsets % 8) why = "offsets must be 8-byte aligned";
-  else if (fill && (uintptr_t)hits % 16) why = "hits must be 16-byte aligned";
-  else if (n > limit) why = "more rays than one launch indexes (kMaxWorkItems)";
-  if (!why) return false;
-  g_err = std::string(fn) + ": " + why;
-  return true;
-}
-
-// mi_list_fill and mi_near_fill on host buffers (in: rays or points of inSize bytes; hits: 16-byte records of either kind;
-// launch(d_in, d_offsets, d_hits, capacity, base, cnt, stream) enqueues one batch's fill): mi_query's pipeline (two slots, its ray and result buffers - the result buffer carries a batch's
-// offsets in) plus a staging buffer of records per slot. A batch's segments are packed from 0 in the staging - the device sees
-// offsets of its own, cut at `capacity` here already - and copied to where the caller's offsets put them: in one piece when the
-// batch's offsets ascend (neighbouring segments then touch), ray by ray otherwise.
-template <class Launch>
-void listFillHost(mi_scene* scene, const void* in, size_t inSize, const uint64_t* offsets, mi_crossing* hits, size_t capacity, size_t n, size_t batch, const Launch& launch) {
-  HIP_CHECK(hipSetDevice(scene->device));
-  const size_t numBatches = (n + batch - 1) / batch;
-  const int slots = numBatches > 1 ? 2 : 1;
-  std::vector<uint64_t> local[2];
-  std::vector<mi_crossing> bounce;
-  try {
-    for (int i = 0; i < slots; ++i) {
-      if (scene->qCap[i] < batch) {
-        if (scene->d_qRays[i] || scene->d_qOut[i]) HIP_CHECK(hipDeviceSynchronize());
-        for (void** p : {&scene->d_qRays[i], &scene->d_qOut[i]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        scene->qCap[i] = 0;
-        HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * sizeof(mi_ray)));
-        HIP_CHECK(hipMalloc(&scene->d_qOut[i], batch * sizeof(mi_query_hit)));      // (room for batch + 1 offsets)
-        scene->qCap[i] = batch;
-      }
-      if (!scene->pipeStream[i]) HIP_CHECK(hipStreamCreateWithFlags(&scene->pipeStream[i], hipStreamNonBlocking));
-    }
-    for (size_t b = 0; b < numBatches; ++b) {
-      const int i = (int)(b % slots);
-      hipStream_t st = scene->pipeStream[i];
-      if (b >= (size_t)slots) HIP_CHECK(hipStreamSynchronize(st));      // local[i] and the staging are free again
-      const size_t first = b * batch, cnt = std::min(batch, n - first);
-      std::vector<uint64_t>& loc = local[i];
-      loc.resize(cnt + 1);
-      loc[0] = 0;
-      bool ascending = true;
-      for (size_t j = 0; j < cnt; ++j) {
-        const uint64_t lo = offsets[first + j], hi = offsets[first + j + 1];
-        ascending = ascending && hi >= lo;
-        loc[j + 1] = loc[j] + ((hi > lo && lo < capacity) ? std::min<uint64_t>(hi, capacity) - lo : 0);
-      }
-      const size_t need = (size_t)loc[cnt];
-      if (scene->listHitsCap[i] < need) {
-        if (scene->d_listHits[i]) { (void)hipFree(scene->d_listHits[i]); scene->d_listHits[i] = nullptr; scene->listHitsCap[i] = 0; }
-        HIP_CHECK(hipMalloc(&scene->d_listHits[i], need * sizeof(mi_crossing)));
-        scene->listHitsCap[i] = need;
-      }
-      HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], static_cast<const char*>(in) + first * inSize, cnt * inSize, hipMemcpyHostToDevice, st));
-      HIP_CHECK(hipMemcpyAsync(scene->d_qOut[i], loc.data(), (cnt + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-      launch(scene->d_qRays[i], static_cast<const uint64_t*>(scene->d_qOut[i]), scene->d_listHits[i], need, (uint32_t)first, cnt, st);
-      if (!need) continue;
-      if (ascending) {
-        HIP_CHECK(hipMemcpyAsync(hits + offsets[first], scene->d_listHits[i], need * sizeof(mi_crossing), hipMemcpyDeviceToHost, st));
-      } else {
-        bounce.resize(need);
-        HIP_CHECK(hipMemcpyAsync(bounce.data(), scene->d_listHits[i], need * sizeof(mi_crossing), hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        for (size_t j = 0; j < cnt; ++j) if (loc[j + 1] > loc[j]) std::memcpy(hits + offsets[first + j], bounce.data() + loc[j], (size_t)(loc[j + 1] - loc[j]) * sizeof(mi_crossing));
-      }
-    }
-    for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
-  } catch (...) { (void)hipDeviceSynchronize(); throw; }
-}
-
-// Neighbour lists, step 1 (mi_near_offsets_device): d_incl[i] = the neighbours of points 0 .. i, i.e. the caller's offsets from their
-// second entry on. near_count_kernel (near_kernels.hpp) writes the counts as 64 bits, the prefix sum is launchListOffsets': the same
-// kernels in place, the tile sums in the stream's launch slot. full_stats picks the instrumented build; no other option applies.
-void launchNearOffsets(mi_scene& S, const mi_point* d_points, uint64_t* d_incl, size_t n, hipStream_t stream) {
-  if (n == 0) return;
-  if (n > kMaxWorkItems) throw ArgError("mi_near_offsets: more points than one launch indexes (kMaxWorkItems)");
-  const uint32_t cnt = (uint32_t)n;
-  LaunchSlot& slot = S.slotFor(stream);
-  const uint32_t tiles = (cnt + kScanTile - 1) / kScanTile;
-  if (tiles > 1 && slot.scanSumsCap < tiles) {
-    if (slot.d_scanSums) { HIP_CHECK(hipStreamSynchronize(stream)); (void)hipFree(slot.d_scanSums); slot.d_scanSums = nullptr; slot.scanSumsCap = 0; }
-    const size_t room = std::max<size_t>(tiles, 1024);
-    HIP_CHECK(hipMalloc(&slot.d_scanSums, room * sizeof(uint64_t)));
-    slot.scanSumsCap = room;
-  }
-  const DeviceScene dsv = S.ds;
-  const dim3 block(256), grid((cnt + 255) / 256);
-  if (S.opt.fullStats) hipLaunchKernelGGL(near_count_kernel<true>, grid, block, 0, stream, dsv, d_points, d_incl, cnt);
-  else hipLaunchKernelGGL(near_count_kernel<false>, grid, block, 0, stream, dsv, d_points, d_incl, cnt);
-  HIP_CHECK(hipGetLastError());
-  if (tiles > 1) {
-    hipLaunchKernelGGL(scan_tile_sums_kernel, dim3(tiles), dim3(kScanThreads), 0, stream, d_incl, slot.d_scanSums, cnt);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kScanThreads), 0, stream, slot.d_scanSums, tiles);
-  }
-  hipLaunchKernelGGL(scan_apply_kernel, dim3(tiles), dim3(kScanThreads), 0, stream, d_incl, tiles > 1 ? slot.d_scanSums : nullptr, cnt);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
-}
-
-// Neighbour lists, step 2 (mi_near_fill_device): near_fill_kernel, one thread per point (near_kernels.hpp). pointBase: the index of
-// the launch's first point in the caller's numbering (the host entry's batches). Records lastWork.
-void launchNearFill(mi_scene& S, const mi_point* d_points, const uint64_t* d_offsets, mi_neighbour* d_hits, size_t capacity, uint32_t pointBase, size_t n, hipStream_t stream) {
-  if (n == 0) return;
-  if (n > kMaxWorkItems) throw ArgError("mi_near_fill: more points than one launch indexes (kMaxWorkItems)");
-  const uint32_t cnt = (uint32_t)n;
-  LaunchSlot& slot = S.slotFor(stream);
-  const DeviceScene dsv = S.ds;
-  const dim3 block(256), grid((cnt + 255) / 256);
-  if (S.opt.fullStats) hipLaunchKernelGGL(near_fill_kernel<true>, grid, block, 0, stream, dsv, d_points, d_offsets, d_hits, (uint64_t)capacity, pointBase, cnt);
-  else hipLaunchKernelGGL(near_fill_kernel<false>, grid, block, 0, stream, dsv, d_points, d_offsets, d_hits, (uint64_t)capacity, pointBase, cnt);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(slot.lastWork, stream));      // (~mi_scene waits for it)
-}
-
-// Argument rules shared by the four neighbour-list entries (hits: only the fill's); touches neither the scene nor a device.
-bool nearArgsBad(const char* fn, const mi_scene* scene, const void* points, const void* offsets, const void* hits, bool fill, size_t n, size_t limit) {
-  const char* why = nullptr;
-  if (!scene) why = "null scene";
-  else if (n == 0) return false;
-  else if (!points || !offsets || (fill && !hits)) why = "null buffer";
-  else if ((uintptr_t)points % 16) why = "points must be 16-byte aligned";
-  else if ((uintptr_t)offsets % 8) why = "offsets must be 8-byte aligned";
-  else if (fill && (uintptr_t)hits % 16) why = "hits must be 16-byte aligned";
-  else if (n > limit) why = "more points than one launch indexes (kMaxWorkItems)";
-  if (!why) return false;
-  g_err = std::string(fn) + ": " + why;
-  return true;
-}
-
 // One wave that samples the work counter of `hip_stream`'s persistent launches `n` times, `period_ticks` (100-MHz ticks) apart, into
 // d_samples as pairs {s_memrealtime, counter}: how fast a launch hands its work units out over its life - the ramp at its start, the
 // moment the queue runs empty, the drain behind it (tools/launch_progress.py). It runs on a stream of the scene's own beside the launch it
@@ -2356,250 +1975,6 @@ int mi_render(mi_scene* scene, int mode, mi_trace_result* rays, size_t n, mi_ray
   });
 }
 
-int mi_query_device(mi_scene* scene, int kind, const void* d_rays, void* d_out, size_t n, void* hip_stream) {
-  if (queryArgsBad("mi_query_device", scene, kind, d_rays, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    launchQuery(*scene, kind, static_cast<const mi_ray*>(d_rays), d_out, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_query(mi_scene* scene, int kind, const mi_ray* rays, void* out, size_t n) {
-  if (queryArgsBad("mi_query", scene, kind, rays, out, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  // (the host stream is cut into batches of mi_scene_set_ray_batch rays: the work-index limit applies per batch)
-  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
-  if (batch > kMaxWorkItems) { g_err = "mi_query: more rays per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    // batches through two slots (device buffers + streams kept by the scene), as mi_render: upload, query and download of batch
-    // b + 1 are enqueued on the other stream while batch b runs
-    const size_t outSize = kind == MI_QUERY_ANY ? 1 : sizeof(mi_query_hit);
-    const size_t numBatches = (n + batch - 1) / batch;
-    const int slots = numBatches > 1 ? 2 : 1;
-    try {
-      for (int i = 0; i < slots; ++i) {
-        if (scene->qCap[i] < batch) {
-          if (scene->d_qRays[i] || scene->d_qOut[i]) HIP_CHECK(hipDeviceSynchronize());
-          for (void** p : {&scene->d_qRays[i], &scene->d_qOut[i]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-          scene->qCap[i] = 0;
-          HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * sizeof(mi_ray)));
-          HIP_CHECK(hipMalloc(&scene->d_qOut[i], batch * sizeof(mi_query_hit)));      // (room for either kind)
-          scene->qCap[i] = batch;
-        }
-        if (!scene->pipeStream[i]) HIP_CHECK(hipStreamCreateWithFlags(&scene->pipeStream[i], hipStreamNonBlocking));
-      }
-      for (size_t b = 0; b < numBatches; ++b) {
-        const int i = (int)(b % slots);
-        hipStream_t st = scene->pipeStream[i];
-        const size_t first = b * batch, cnt = std::min(batch, n - first);
-        HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], rays + first, cnt * sizeof(mi_ray), hipMemcpyHostToDevice, st));
-        launchQuery(*scene, kind, static_cast<const mi_ray*>(scene->d_qRays[i]), scene->d_qOut[i], cnt, st);
-        HIP_CHECK(hipMemcpyAsync(static_cast<char*>(out) + first * outSize, scene->d_qOut[i], cnt * outSize, hipMemcpyDeviceToHost, st));
-      }
-      for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
-    } catch (...) { (void)hipDeviceSynchronize(); throw; }
-  });
-}
-
-int mi_point_query_device(mi_scene* scene, int kind, const void* d_points, void* d_out, size_t n, void* hip_stream) {
-  if (pointArgsBad("mi_point_query_device", scene, kind, d_points, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    launchPointQuery(*scene, kind, static_cast<const mi_point*>(d_points), d_out, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_point_query(mi_scene* scene, int kind, const mi_point* points, void* out, size_t n) {
-  if (pointArgsBad("mi_point_query", scene, kind, points, out, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  // (the host stream is cut into batches of mi_scene_set_ray_batch points: the work-index limit applies per batch)
-  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
-  if (batch > kMaxWorkItems) { g_err = "mi_point_query: more points per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    // mi_query's pipeline and its buffers (a slot holds `batch` 32-byte records in and out: room for 16-byte points and either result)
-    const size_t outSize = kind == MI_POINT_WITHIN ? 1 : sizeof(mi_point_hit);
-    const size_t numBatches = (n + batch - 1) / batch;
-    const int slots = numBatches > 1 ? 2 : 1;
-    try {
-      for (int i = 0; i < slots; ++i) {
-        if (scene->qCap[i] < batch) {
-          if (scene->d_qRays[i] || scene->d_qOut[i]) HIP_CHECK(hipDeviceSynchronize());
-          for (void** p : {&scene->d_qRays[i], &scene->d_qOut[i]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-          scene->qCap[i] = 0;
-          HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * sizeof(mi_ray)));
-          HIP_CHECK(hipMalloc(&scene->d_qOut[i], batch * sizeof(mi_query_hit)));
-          scene->qCap[i] = batch;
-        }
-        if (!scene->pipeStream[i]) HIP_CHECK(hipStreamCreateWithFlags(&scene->pipeStream[i], hipStreamNonBlocking));
-      }
-      for (size_t b = 0; b < numBatches; ++b) {
-        const int i = (int)(b % slots);
-        hipStream_t st = scene->pipeStream[i];
-        const size_t first = b * batch, cnt = std::min(batch, n - first);
-        HIP_CHECK(hipMemcpyAsync(scene->d_qRays[i], points + first, cnt * sizeof(mi_point), hipMemcpyHostToDevice, st));
-        launchPointQuery(*scene, kind, static_cast<const mi_point*>(scene->d_qRays[i]), scene->d_qOut[i], cnt, st);
-        HIP_CHECK(hipMemcpyAsync(static_cast<char*>(out) + first * outSize, scene->d_qOut[i], cnt * outSize, hipMemcpyDeviceToHost, st));
-      }
-      for (int i = 0; i < slots; ++i) HIP_CHECK(hipStreamSynchronize(scene->pipeStream[i]));
-    } catch (...) { (void)hipDeviceSynchronize(); throw; }
-  });
-}
-
-int mi_count_query_device(mi_scene* scene, const void* d_rays, uint32_t* d_counts, size_t n, void* hip_stream) {
-  if (countArgsBad("mi_count_query_device", scene, d_rays, d_counts, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    launchCountQuery(*scene, static_cast<const mi_ray*>(d_rays), d_counts, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_count_query(mi_scene* scene, const mi_ray* rays, uint32_t* counts, size_t n) {
-  if (countArgsBad("mi_count_query", scene, rays, counts, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  // (the host stream is cut into batches of mi_scene_set_ray_batch rays: the work-index limit applies per batch)
-  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
-  if (batch > kMaxWorkItems) { g_err = "mi_count_query: more rays per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] {
-    pipelinedQuery(scene, rays, sizeof(mi_ray), counts, sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchCountQuery(*scene, static_cast<const mi_ray*>(d_in), static_cast<uint32_t*>(d_out), cnt, st);
-    });
-  });
-}
-
-int mi_point_sign_device(mi_scene* scene, int kind, const void* d_points, void* d_out, const float dir[3], size_t n, void* hip_stream) {
-  if (signArgsBad("mi_point_sign_device", scene, kind, d_points, d_out, dir, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const float* dv = dir ? dir : kDefaultInsideDir;
-  const f3 d = mk(dv[0], dv[1], dv[2]);
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    launchPointSign(*scene, kind, static_cast<const mi_point*>(d_points), d_out, d, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_point_sign(mi_scene* scene, int kind, const mi_point* points, void* out, const float dir[3], size_t n) {
-  if (signArgsBad("mi_point_sign", scene, kind, points, out, dir, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  // (the host stream is cut into batches of mi_scene_set_ray_batch points: the work-index limit applies per batch)
-  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
-  if (batch > kMaxWorkItems) { g_err = "mi_point_sign: more points per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
-  const float* dv = dir ? dir : kDefaultInsideDir;
-  const f3 d = mk(dv[0], dv[1], dv[2]);
-  return guarded([&] {
-    pipelinedQuery(scene, points, sizeof(mi_point), out, kind == MI_SIGN_INSIDE ? 1 : sizeof(mi_point_hit), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchPointSign(*scene, kind, static_cast<const mi_point*>(d_in), d_out, d, cnt, st);
-    });
-  });
-}
-
-int mi_list_offsets_device(mi_scene* scene, const void* d_rays, uint64_t* d_offsets, size_t n, void* hip_stream) {
-  if (listArgsBad("mi_list_offsets_device", scene, d_rays, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
-    launchListOffsets(*scene, static_cast<const mi_ray*>(d_rays), d_offsets + 1, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_list_fill_device(mi_scene* scene, const void* d_rays, const uint64_t* d_offsets, mi_crossing* d_hits, size_t capacity, size_t n, void* hip_stream) {
-  if (listArgsBad("mi_list_fill_device", scene, d_rays, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    launchListFill(*scene, static_cast<const mi_ray*>(d_rays), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_list_offsets(mi_scene* scene, const mi_ray* rays, uint64_t* offsets, size_t n) {
-  if (listArgsBad("mi_list_offsets", scene, rays, offsets, nullptr, false, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  // (the host stream is cut into batches of mi_scene_set_ray_batch rays: the work-index limit applies per batch)
-  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
-  if (batch > kMaxWorkItems) { g_err = "mi_list_offsets: more rays per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] {
-    // every batch's prefix sum starts at 0 on the device; what precedes the batch is added here, batch by batch
-    offsets[0] = 0;
-    pipelinedQuery(scene, rays, sizeof(mi_ray), offsets + 1, sizeof(uint64_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchListOffsets(*scene, static_cast<const mi_ray*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
-    });
-    for (size_t first = batch; first < n; first += batch) {
-      const uint64_t base = offsets[first];
-      const size_t cnt = std::min(batch, n - first);
-      for (size_t j = 1; j <= cnt; ++j) offsets[first + j] += base;
-    }
-  });
-}
-
-int mi_list_fill(mi_scene* scene, const mi_ray* rays, const uint64_t* offsets, mi_crossing* hits, size_t capacity, size_t n) {
-  if (listArgsBad("mi_list_fill", scene, rays, offsets, hits, true, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
-  if (batch > kMaxWorkItems) { g_err = "mi_list_fill: more rays per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] {
-    listFillHost(scene, rays, sizeof(mi_ray), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_crossing* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
-      launchListFill(*scene, static_cast<const mi_ray*>(d_in), d_off, d_hits, cap, base, cnt, st);
-    });
-  });
-}
-
-int mi_near_offsets_device(mi_scene* scene, const void* d_points, uint64_t* d_offsets, size_t n, void* hip_stream) {
-  if (nearArgsBad("mi_near_offsets_device", scene, d_points, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
-    launchNearOffsets(*scene, static_cast<const mi_point*>(d_points), d_offsets + 1, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_near_fill_device(mi_scene* scene, const void* d_points, const uint64_t* d_offsets, mi_neighbour* d_hits, size_t capacity, size_t n, void* hip_stream) {
-  if (nearArgsBad("mi_near_fill_device", scene, d_points, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return guarded([&] {
-    HIP_CHECK(hipSetDevice(scene->device));
-    launchNearFill(*scene, static_cast<const mi_point*>(d_points), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_near_offsets(mi_scene* scene, const mi_point* points, uint64_t* offsets, size_t n) {
-  if (nearArgsBad("mi_near_offsets", scene, points, offsets, nullptr, false, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  // (the host stream is cut into batches of mi_scene_set_ray_batch points: the work-index limit applies per batch)
-  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
-  if (batch > kMaxWorkItems) { g_err = "mi_near_offsets: more points per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] {
-    // every batch's prefix sum starts at 0 on the device; what precedes the batch is added here, batch by batch
-    offsets[0] = 0;
-    pipelinedQuery(scene, points, sizeof(mi_point), offsets + 1, sizeof(uint64_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchNearOffsets(*scene, static_cast<const mi_point*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
-    });
-    for (size_t first = batch; first < n; first += batch) {
-      const uint64_t base = offsets[first];
-      const size_t cnt = std::min(batch, n - first);
-      for (size_t j = 1; j <= cnt; ++j) offsets[first + j] += base;
-    }
-  });
-}
-
-int mi_near_fill(mi_scene* scene, const mi_point* points, const uint64_t* offsets, mi_neighbour* hits, size_t capacity, size_t n) {
-  if (nearArgsBad("mi_near_fill", scene, points, offsets, hits, true, n, ~(size_t)0)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = (scene->rayBatch && scene->rayBatch < n) ? scene->rayBatch : n;
-  if (batch > kMaxWorkItems) { g_err = "mi_near_fill: more points per batch than one launch indexes (kMaxWorkItems; see mi_scene_set_ray_batch)"; return MI_ERR_INVALID_ARG; }
-  static_assert(sizeof(mi_neighbour) == sizeof(mi_crossing), "the staging of the list fills holds 16-byte records of either kind");
-  return guarded([&] {
-    listFillHost(scene, points, sizeof(mi_point), offsets, reinterpret_cast<mi_crossing*>(hits), capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_crossing* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
-      launchNearFill(*scene, static_cast<const mi_point*>(d_in), d_off, reinterpret_cast<mi_neighbour*>(d_hits), cap, base, cnt, st);
-    });
-  });
-}
-
 int mi_scene_set_option(mi_scene* scene, const char* key, const char* value) {
   if (!scene || !key || !value) { g_err = "mi_scene_set_option: null argument"; return MI_ERR_INVALID_ARG; }
   // (a value auto_rebuild does not take is refused before the scene is touched)
@@ -2742,6 +2117,7 @@ int mi_nif_infer_device(mi_scene* scene, const float* d_u, const float* d_v, flo
 
 }  // extern "C"
 
+#include "query_drivers.hpp"        // the five query families: launchers, argument rules, the host pipeline, their entries
 #include "group_render.hpp"
 
 #if MI_NIF_STAMPS

@@ -129,6 +129,18 @@ def test_point_sign_argument_rules_need_no_device(variants):
     assert lib.mi_point_sign(scene, 1, None, None, ok, 0) == 0
     assert lib.mi_point_sign_device(scene, 7, p, o, None, 0, None) == 1
     assert lib.mi_point_sign(scene, 0, p, o, vec(0.0, 1.0, 1.0), 0) == 1
+    # a zero, NaN or infinite direction component is refused before n == 0 is looked at, null buffers or not
+    for comp in (0.0, -0.0, nan, inf, -inf):
+        for axis in range(3):
+            d = [1.0, 0.70710678, 0.57735027]
+            d[axis] = comp
+            for kind in (0, 1):
+                assert lib.mi_point_sign_device(scene, kind, None, None, vec(*d), 0, None) == 1, (comp, axis, kind)
+                err = lib.mi_last_error()
+                assert b"mi_point_sign_device" in err and b"direction component is zero, NaN or infinite" in err, (comp, axis, kind, err)
+                assert lib.mi_point_sign(scene, kind, None, None, vec(*d), 0) == 1, (comp, axis, kind)
+                err = lib.mi_last_error()
+                assert b"mi_point_sign:" in err and b"direction component is zero, NaN or infinite" in err, (comp, axis, kind, err)
     # the bytes of MI_SIGN_INSIDE need no alignment: an odd out pointer passes the rules (n == 0, so nothing is launched)
     assert lib.mi_point_sign_device(scene, 0, p, o + 1, ok, 0, None) == 0
     assert bytes(fake.raw) == bytes(4096)

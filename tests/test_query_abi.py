@@ -56,21 +56,23 @@ def test_query_argument_rules_need_no_device(variants):
     out = irl.aligned_bytes(64 * 32)
     r, o = rays.ctypes.data, out.ctypes.data
     bad = {
-        "null scene": (None, 0, r, o, 4),
-        "null rays": (scene, 0, None, o, 4),
-        "null out": (scene, 1, r, None, 4),
-        "unknown kind": (scene, 2, r, o, 4),
-        "negative kind": (scene, -1, r, o, 4),
-        "misaligned rays": (scene, 0, r + 4, o, 4),
-        "misaligned out": (scene, 1, r, o + 8, 4),
-        "too many rays": (scene, 0, r, o, 0xFFBFFFFF + 1),
+        "null scene": ((None, 0, r, o, 4), b"null scene"),
+        "null rays": ((scene, 0, None, o, 4), b"null buffer"),
+        "null out": ((scene, 1, r, None, 4), b"null buffer"),
+        "unknown kind": ((scene, 2, r, o, 4), b"unknown query kind"),
+        "negative kind": ((scene, -1, r, o, 4), b"unknown query kind"),
+        "misaligned rays": ((scene, 0, r + 4, o, 4), b"16-byte aligned"),
+        "misaligned out": ((scene, 1, r, o + 8, 4), b"16-byte aligned"),
+        "too many rays": ((scene, 0, r, o, 0xFFBFFFFF + 1), b"more rays than one launch indexes"),
     }
-    for what, (sc, kind, rp, op, n) in bad.items():
+    for what, ((sc, kind, rp, op, n), words) in bad.items():
         assert lib.mi_query_device(sc, kind, rp, op, n, None) == 1, what          # MI_ERR_INVALID_ARG, not MI_ERR_DEVICE
-        assert b"mi_query_device" in lib.mi_last_error(), what
+        err = lib.mi_last_error()
+        assert b"mi_query_device" in err and words in err, (what, err)
         if what != "too many rays":      # (the host entry applies the limit per batch, which needs the scene)
             assert lib.mi_query(sc, kind, rp, op, n) == 1, what
-            assert b"mi_query" in lib.mi_last_error(), what
+            err = lib.mi_last_error()
+            assert b"mi_query:" in err and words in err, (what, err)
     # n == 0 is a no-op, whatever the buffers
     assert lib.mi_query_device(scene, 0, None, None, 0, None) == 0
     assert lib.mi_query(scene, 1, None, None, 0) == 0
