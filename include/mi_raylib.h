@@ -387,6 +387,83 @@ int mi_list_fill_device(mi_scene* scene, const void* d_rays, const uint64_t* d_o
 int mi_list_offsets(mi_scene* scene, const mi_ray* rays, uint64_t* offsets /* n + 1 */, size_t n);
 int mi_list_fill(mi_scene* scene, const mi_ray* rays, const uint64_t* offsets, mi_crossing* hits, size_t capacity, size_t n);
 
+/* Box queries: the primitives of the scene's CURRENT BVH that TOUCH each of n caller-supplied axis-aligned boxes [lo, hi] - a voxel
+ * (Open3D's VoxelGrid.create_from_triangle_mesh, trimesh's voxelize), a culling or selection cell, a broad-phase cell or a moving
+ * body's bounds (PCL's boxSearch, a physics engine's overlap-box). Every other query here is a ray or a ball; a caller with a box had
+ * to ask mi_near_* about the circumscribed ball and filter. Whether there is one (MI_BOX_ANY), how many (MI_BOX_COUNT), or which:
+ * two steps as for the neighbour lists - the offsets of the boxes' segments, then the fill of a buffer the caller sized from them.
+ * Touching is CLOSED everywhere: contact counts. Queries see SURFACES, as everywhere in this library: a box wholly inside a sphere,
+ * away from its shell, does not touch it.
+ * The box: lo[3] and hi[3]; reserved0 and reserved1 are not read. The record: the ids as mi_point_hit carries them, flags = 0 or
+ * MI_OVERLAP_CONTAINED (the primitive's own bounds, as defined below, lie inside the box, faces included), box = the index of the
+ * query the record belongs to, reserved = 0. The empty record is {MI_INVALID_PRIM, MI_INVALID_GEOM, MI_FLAG_ESCAPED, box, 0}.
+ * Arithmetic: binary32, one rounding per operation in the order written below, no contraction, correctly rounded divide and sqrt;
+ * a dot product is (x x' + y y') + z z'; min and max are compare / select pairs (a < b ? a : b, a > b ? a : b). One definition
+ * (ipu_ray_lib_amd/csrc/box_math.hpp) serves the kernels and the host twins (mi_scene_host.h), which return the same bytes.
+ * Validity: a box with a coordinate that is NaN or infinite, or with lo > hi on an axis, is not walked and finds nothing; so does
+ * an empty scene. lo == hi on an axis is legal: a plane, a line, a point.
+ * The walk is the stackless preorder walk of the point queries - first child first, whatever the box. A node nd is entered when
+ * nd.min <= hi && nd.max >= lo on all three axes (compares, no arithmetic), else passed. At a leaf so reached the primitive is
+ * tested; MI_BOX_ANY stops at the first one that touches.
+ * Every primitive test starts with the primitive's OWN bounds [mn, mx] against the box, in the same compares: not touching unless
+ * mn <= hi && mx >= lo on all axes; CONTAINED exactly when mn >= lo && mx <= hi on all axes.
+ * Triangle (a, b, c): mn, mx = the per-axis min and max of the vertices (no arithmetic: the bounds test and CONTAINED are exact).
+ *   Touching at once when a vertex v has lo <= v <= hi on all axes. Otherwise Akenine-Moller's separating-axis test in centre /
+ *   half-extent form: cb = 0.5 lo + 0.5 hi, h = 0.5 hi - 0.5 lo, v0 = a - cb, v1 = b - cb, v2 = c - cb, e0 = v1 - v0, e1 = v2 - v1,
+ *   e2 = v0 - v2. For e = e0, e1, e2 in turn, with p_i over the three moved vertices:
+ *     p_i = e.y v_i.z - e.z v_i.y, r = h.y |e.z| + h.z |e.y|;   p_i = e.z v_i.x - e.x v_i.z, r = h.x |e.z| + h.z |e.x|;
+ *     p_i = e.x v_i.y - e.y v_i.x, r = h.x |e.y| + h.y |e.x|;
+ *   then the plane: nrm = cross(e0, e1), p = nrm.v0 (for all three), r = (h.x |nrm.x| + h.y |nrm.y|) + h.z |nrm.z|. An axis separates
+ *   when min p_i > r || max p_i < -r, evaluated as (p_0 > r && p_1 > r && p_2 > r) || (p_0 < -r && p_1 < -r && p_2 < -r): a NaN
+ *   never separates, so a box so large that its products overflow errs towards listing. The triangle touches when no axis separates
+ *   (the box's own three axes were the bounds test). A collapsed triangle needs no special case: zero axes separate nothing.
+ * Sphere (centre c, radius, r2 = radius radius as the scene holds it): mn = c - radius, mx = c + radius (one rounded operation
+ *   each). dmin2 = mi_point_query's box distance db of c from [lo, hi]; per axis f = max(|c - lo|, |hi - c|), dmax2 = (fx fx + fy fy)
+ *   + fz fz, the squared distance of the farthest corner. Touching when !(dmin2 > r2) && !(dmax2 < r2): the shell is reached from
+ *   outside and from inside.
+ * Disc (centre c, normal n as given, r2 = r r as the scene holds it): CONSERVATIVE - three necessary conditions that must all hold.
+ *   r' = sqrtf(r2), nn = n.n, per axis t = 1 - n_i n_i / nn, t = t > 0 ? t : 0, half extent r' sqrtf(t): mn = c - ext, mx = c + ext,
+ *   the disc's tight bounds, which the box must meet (and which decide CONTAINED). The box meets the disc's plane: s = n.(cb - c),
+ *   rr = (h.x |n.x| + h.y |n.y|) + h.z |n.z|, !(|s| > rr). The box meets the ball of radius r about c: !(db of c > r2). No touching
+ *   disc is missed, up to the rounding of these operations; a box that passes the disc's rim within its own size may list it without
+ *   touching it. An exact disc test is not offered.
+ * Order: records are sorted by the key (geom_id, prim_id), ascending; keys are unique within a box. This IS the definition - there is
+ * no distance bound to round -: a segment shorter than the box's count holds the len smallest keys, and a list is the same bytes
+ * after a refit, a rebuild or mi_scene_set_geometry of the same contents.
+ * mi_box_query_device: d_boxes = n mi_box, d_out = n uint8_t, 1 = a primitive touches the box (MI_BOX_ANY; the bytes need no
+ *   alignment) or n uint32_t counts (MI_BOX_COUNT), DEVICE memory.
+ * mi_box_offsets_device: d_offsets = n + 1 uint64_t: d_offsets[0] = 0, d_offsets[i + 1] - d_offsets[i] = the count of box i,
+ *   d_offsets[n] = their total (64 bit). Form: the count walk, then the crossing lists' prefix sum in place (their scratch per stream).
+ * mi_box_fill_device: d_offsets = n + 1 uint64_t, d_hits = `capacity` mi_overlap, DEVICE memory. Box i owns the records
+ *   [d_offsets[i], d_offsets[i + 1]) cut at capacity; len = that length, 0 for a decreasing pair or a start at or past capacity,
+ *   exactly as in mi_near_fill_device. NO record at an index >= capacity is ever written and none outside the segment, whatever the
+ *   offsets hold. A box with len == 0 is not walked. Otherwise the segment receives the len smallest keys of the box's touching
+ *   primitives, ascending, and what they leave unused is the empty record. The key has no spatial bound, so the fill walks exactly
+ *   what the count walk walks: under full_stats its visits equal mi_box_offsets' over the boxes whose segment is not empty.
+ *   Caller-made offsets are legal: d_offsets[i] = K i gives the K smallest keys of every box, padded. Overlapping segments of
+ *   different boxes give unspecified records inside them.
+ *   Form: one thread per box keeps the len smallest keys as a binary max-heap inside the segment - O(count log len) record moves,
+ *   where an insertion sort would move O(count len) - and heap-sorts it in place.
+ * Host entries: the same on HOST buffers, synchronous, in batches of mi_scene_set_ray_batch boxes; offsets and the `box` field are
+ *   global across batches (`box` is the index modulo 2^32). The fill shares mi_list_fill's device staging.
+ * Asynchrony, ordering against update / rebuild / set-geometry, destruction, groups, batches and stream rules: those of
+ * mi_point_query_device / mi_point_query and mi_near_*. n == 0 is a no-op. MI_ERR_INVALID_ARG, before any device work and without
+ * reading the scene: a null scene or buffer, an unknown kind ("unknown box kind"), boxes or hits that are not 16-byte aligned, counts
+ * that are not 4-byte aligned, offsets that are not 8-byte aligned, or more boxes in one launch (host entries: in one batch) than the
+ * 32-bit work index allows (0xFFBFFFFF).
+ * Options: none apply (one kernel, one arithmetic). Counters: nothing is added to casts or paths; under full_stats the box tests are
+ * added to "nodes visited" and the primitive tests to "leaf tests". */
+typedef struct { float lo[3]; uint32_t reserved0; float hi[3]; uint32_t reserved1; } mi_box;      /* 32 B, 16-byte aligned loads */
+typedef struct { uint32_t primID; uint16_t geomID; uint16_t flags; uint32_t box; uint32_t reserved; } mi_overlap;   /* 16 B */
+#define MI_OVERLAP_CONTAINED ((uint16_t)16)   /* the primitive's own bounds lie inside the box (closed) */
+enum { MI_BOX_ANY = 0, MI_BOX_COUNT = 1 };
+int mi_box_query_device(mi_scene* scene, int kind, const void* d_boxes, void* d_out, size_t n, void* hip_stream);
+int mi_box_query(mi_scene* scene, int kind, const mi_box* boxes, void* out, size_t n);
+int mi_box_offsets_device(mi_scene* scene, const void* d_boxes, uint64_t* d_offsets /* n + 1 */, size_t n, void* hip_stream);
+int mi_box_fill_device(mi_scene* scene, const void* d_boxes, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream);
+int mi_box_offsets(mi_scene* scene, const mi_box* boxes, uint64_t* offsets /* n + 1 */, size_t n);
+int mi_box_fill(mi_scene* scene, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n);
+
 /* Geometry updates: new positions for the primitives of a live scene, the topology kept - triangles, geometry list, materials and
  * the BVH's shape - and every BVH box recomputed on the device (a refit: Embree's RTC_BUILD_QUALITY_REFIT commit, OptiX's
  * OPTIX_BUILD_OPERATION_UPDATE). Any pointer may be NULL = keep; a non-NULL array must have exactly the scene's count (a NULL array

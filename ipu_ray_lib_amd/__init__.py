@@ -54,7 +54,12 @@ CROSSING = np.dtype([("t", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("flags
 # mi_neighbour: one record of a neighbour list (IpuScene.neighbours / k_nearest / near_fill_device)
 NEIGHBOUR = np.dtype([("dist2", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("point", "<u4")])
 
+# mi_box / mi_overlap: a box query and one record of its list (IpuScene.touches / count_overlaps / list_overlaps / box_fill_device)
+BOX = np.dtype([("lo", "<f4", (3,)), ("reserved0", "<u4"), ("hi", "<f4", (3,)), ("reserved1", "<u4")])
+OVERLAP = np.dtype([("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("box", "<u4"), ("reserved", "<u4")])
+
 assert CROSSING.itemsize == 16 and NEIGHBOUR.itemsize == 16
+assert BOX.itemsize == 32 and OVERLAP.itemsize == 16
 assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
 assert POINT.itemsize == 16 and POINT_HIT.itemsize == 32
 assert BVH_NODE.itemsize == 24 and MATERIAL.itemsize == 36 and MESH_INFO.itemsize == 16 and GEOM_REF.itemsize == 4
@@ -65,6 +70,8 @@ INVALID_GEOM, INVALID_PRIM = 0xFFFF, 0xFFFFFFFF
 MODE_SHADOW_TRACE, MODE_PATH_TRACE = 0, 1
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 POINT_CLOSEST, POINT_WITHIN = 0, 1
+BOX_ANY, BOX_COUNT = 0, 1
+OVERLAP_CONTAINED = 16      # MI_OVERLAP_CONTAINED: the primitive's own bounds lie inside the box
 SIGN_INSIDE, SIGN_DISTANCE = 0, 1
 # the ray direction of an inside test when none is given (mi_point_sign: no zero component, off the diagonals of axis-aligned boxes)
 DEFAULT_INSIDE_DIR = (1.0, 0.70710678, 0.57735027)
@@ -191,6 +198,9 @@ def host_lib() -> C.CDLL:
         lib.mi_point_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_near_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_near_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_box_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_box_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_box_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
         lib.mi_sphere_roots_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)]
@@ -288,6 +298,12 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_near_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_near_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         lib.mi_near_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        lib.mi_box_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_box_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_box_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_box_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_box_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        lib.mi_box_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         lib.mi_point_sign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t]
         lib.mi_point_sign_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
@@ -529,6 +545,49 @@ def near_fill_host(desc: SceneDesc, points: np.ndarray, offsets: np.ndarray, cap
     visits = (C.c_uint64 * 2)()
     base = hits.ctypes.data if hits.size else np.zeros(1, NEIGHBOUR).ctypes.data
     _check_host(host_lib().mi_near_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
+    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def box_query_host(desc: SceneDesc, kind: int, boxes: np.ndarray):
+    """mi_box_query_host: the host twin of IpuScene.touches / .count_overlaps on desc's arrays and nodes - the same bytes. Returns
+    (out, visits): a bool array (BOX_ANY) or a uint32 array (BOX_COUNT), and {"box_tests", "prim_evals"} summed over the boxes (what
+    the device counts as nodes visited / leaf tests under option full_stats)."""
+    assert boxes.dtype == BOX and boxes.ndim == 1
+    src = np.ascontiguousarray(boxes)
+    out = np.zeros(src.size, np.uint8 if kind == BOX_ANY else np.uint32)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_box_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
+                                             out.ctypes.data if src.size else None, src.size, visits))
+    return (out.view(np.bool_) if kind == BOX_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def box_offsets_host(desc: SceneDesc, boxes: np.ndarray):
+    """mi_box_offsets_host: the host twin of IpuScene.box_offsets - the same uint64 offsets. Returns (offsets, visits)."""
+    assert boxes.dtype == BOX and boxes.ndim == 1
+    src = np.ascontiguousarray(boxes)
+    offsets = np.zeros(src.size + 1, np.uint64)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_box_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
+    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def box_fill_host(desc: SceneDesc, boxes: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
+    """mi_box_fill_host: the host twin of IpuScene.box_fill - the same bytes. Returns (recs, visits): recs is `hits` (an OVERLAP
+    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
+    nothing at or past `capacity` (None: recs.size) is written."""
+    assert boxes.dtype == BOX and boxes.ndim == 1
+    src = np.ascontiguousarray(boxes)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    assert offsets.ndim == 1 and offsets.size == src.size + 1
+    if hits is None:
+        size = int(offsets.max()) if capacity is None else int(capacity)
+        hits = np.zeros(max(size, 1), OVERLAP)[:size]
+    assert hits.dtype == OVERLAP and hits.flags["C_CONTIGUOUS"]
+    capacity = hits.size if capacity is None else int(capacity)
+    assert 0 <= capacity <= hits.size
+    visits = (C.c_uint64 * 2)()
+    base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
+    _check_host(host_lib().mi_box_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
     return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
 
 
@@ -972,6 +1031,102 @@ class IpuScene:
         pts, n = self._torch_points("knn", points, radius)
         offsets, raw = self._torch_first_k(self.near_fill_device, pts, n, k)
         return {**self._neighbour_columns(raw), "offsets": offsets}
+
+    # -- box queries (mi_box_query*, mi_box_offsets*, mi_box_fill*): every primitive that touches each box, by (geomID, primID) ------
+    def _box_query_host(self, kind: int, boxes: np.ndarray, out: np.ndarray) -> np.ndarray:
+        src = self._source(boxes, BOX)
+        self._check(self._lib.mi_box_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
+        return out
+
+    def touches(self, boxes: np.ndarray) -> np.ndarray:
+        """Whether some primitive touches each box (a BOX array, host memory; contact counts): a bool array. Synchronous; batched
+        by setRayBatch."""
+        return self._box_query_host(BOX_ANY, boxes, aligned_bytes(boxes.size)).view(np.bool_)
+
+    def count_overlaps(self, boxes: np.ndarray) -> np.ndarray:
+        """How many primitives touch each box (a BOX array, host memory): a uint32 array."""
+        return self._box_query_host(BOX_COUNT, boxes, np.zeros(boxes.size, np.uint32))
+
+    def box_offsets(self, boxes: np.ndarray) -> np.ndarray:
+        """mi_box_offsets: a uint64 array of boxes.size + 1 offsets - 0, then the running total of count_overlaps(boxes)."""
+        return self._offsets_host(self._lib.mi_box_offsets, self._source(boxes, BOX))
+
+    def box_fill(self, boxes: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
+        """mi_box_fill: the primitives touching box i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (an
+        OVERLAP array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
+        (None: hits.size) is written."""
+        return self._fill_host(self._lib.mi_box_fill, OVERLAP, self._source(boxes, BOX), offsets, hits, capacity)
+
+    def list_overlaps(self, boxes: np.ndarray):
+        """Every primitive that touches each box (a BOX array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs an
+        OVERLAP array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are box i's primitives in ascending order of (geomID,
+        primID), flags = OVERLAP_CONTAINED where the primitive's own bounds lie inside the box. Synchronous; batched by setRayBatch."""
+        return self._all_lists(self.box_offsets, self.box_fill, OVERLAP, boxes)
+
+    def first_overlaps(self, boxes: np.ndarray, k: int) -> np.ndarray:
+        """The k smallest (geomID, primID) of the primitives touching each box: an OVERLAP array [n, k]; boxes with fewer are padded
+        with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
+        return self._first_k(self.box_fill, OVERLAP, boxes, k)
+
+    def box_query_device(self, kind: int, d_boxes: int, d_out: int, n: int, stream: int = 0):
+        """mi_box_query_device on device pointers (n BOX records in, n bytes or n uint32 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_box_query_device(self._h, int(kind), C.c_void_p(d_boxes), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
+
+    def box_offsets_device(self, d_boxes: int, d_offsets: int, n: int, stream: int = 0):
+        """mi_box_offsets_device on device pointers (n BOX records in, n + 1 uint64 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_box_offsets_device(self._h, C.c_void_p(d_boxes), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
+
+    def box_fill_device(self, d_boxes: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
+        """mi_box_fill_device on device pointers (n BOX records and n + 1 uint64 in, `capacity` OVERLAP records out), asynchronous
+        on `stream`."""
+        self._check(self._lib.mi_box_fill_device(self._h, C.c_void_p(d_boxes), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
+                                                 int(n), C.c_void_p(stream)))
+
+    @staticmethod
+    def _torch_boxes(what, lo, hi):
+        import torch
+        a, b = lo.to(torch.float32), hi.to(torch.float32)
+        if a.ndim != 2 or a.shape[1] != 3 or b.shape != a.shape or not a.is_cuda or b.device != a.device:
+            raise ValueError(f"{what}: lo and hi must be [N, 3] tensors on one GPU")
+        n = a.shape[0]
+        pad = torch.zeros((n, 1), dtype=torch.float32, device=a.device)
+        return torch.cat([a, pad, b, pad], dim=1).contiguous(), n      # [N, 8] = n mi_box
+
+    def box_any(self, lo, hi):
+        """Torch convenience over mi_box_query_device (BOX_ANY): float32 device tensors lo, hi of shape [N, 3], enqueued on
+        torch.cuda.current_stream(). Returns an [N] bool device tensor: a primitive touches the box."""
+        boxes, n = self._torch_boxes("box_any", lo, hi)
+        return self._torch_flags(boxes, n, self.box_query_device, BOX_ANY)
+
+    def box_count(self, lo, hi):
+        """The same for BOX_COUNT: an [N] int32 device tensor, the number of primitives touching each box."""
+        import torch
+        boxes, n = self._torch_boxes("box_count", lo, hi)
+        out = torch.empty(n, dtype=torch.int32, device=boxes.device)
+        self.box_query_device(BOX_COUNT, boxes.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(boxes.device).cuda_stream)
+        return out
+
+    def box_list(self, lo, hi):
+        """Torch convenience over mi_box_offsets_device + mi_box_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 - the
+        words of the OVERLAP records: primID, geomID | flags << 16, box, 0), box by box in ascending (geomID, primID). It runs the
+        offsets, reads the total with one .item() (the one synchronisation), then allocates and fills."""
+        boxes, n = self._torch_boxes("box_list", lo, hi)
+        return self._torch_all_lists(self.box_offsets_device, self.box_fill_device, boxes, n, sync_when_empty=False)
+
+    def voxelize(self, origin, cell, dims, device=None):
+        """Surface voxelisation: a bool device tensor [nx, ny, nz], cell (i, j, k) set when a primitive touches the closed box
+        lo = origin + (i, j, k) cell, hi = origin + (i + 1, j + 1, k + 1) cell - each one multiply and one add in float32 as written,
+        so neighbouring cells share their faces bit for bit and a surface lying in a shared face sets the cells on both sides.
+        origin: three floats; cell: a float or three; dims: (nx, ny, nz). One BOX_ANY launch on torch.cuda.current_stream()."""
+        import torch
+        dev = torch.device("cuda", self.desc.device) if device is None else torch.device(device)
+        nx, ny, nz = (int(d) for d in dims)
+        o = torch.as_tensor(origin, dtype=torch.float32, device=dev).expand(3)
+        c = torch.as_tensor(cell, dtype=torch.float32, device=dev).expand(3)
+        axes = [torch.arange(m + 1, dtype=torch.float32, device=dev) * c[a] + o[a] for a, m in enumerate((nx, ny, nz))]      # the grid's planes
+        lo = torch.stack(torch.meshgrid(axes[0][:-1], axes[1][:-1], axes[2][:-1], indexing="ij"), dim=-1).reshape(-1, 3)
+        hi = torch.stack(torch.meshgrid(axes[0][1:], axes[1][1:], axes[2][1:], indexing="ij"), dim=-1).reshape(-1, 3)
+        return self.box_any(lo, hi).reshape(nx, ny, nz)
 
     # -- crossing counts, inside tests, signed distance (mi_count_query*, mi_point_sign*) -----------------------------------------------
     def count_crossings(self, rays: np.ndarray) -> np.ndarray:

@@ -14,19 +14,6 @@
 
 namespace mi::host {
 
-namespace {
-// What the walk reads of a node: the decoded box, where it goes on when the box is passed, and for a leaf the first 40 bytes of
-// the device's leaf record (kind, nine floats) with the ids the result reports.
-struct WalkNode {
-  float minx, maxx, miny, maxy, minz, maxz;
-  uint32_t skip;        // the node behind this node's subtree (a leaf's: i + 1)
-  uint32_t kind;        // 0 triangle, 1 sphere, 2 disc; kInterior for an interior node
-  float f[9];
-  uint32_t primID;
-  uint16_t geomID;
-};
-constexpr uint32_t kInterior = 0xFFFFFFFFu;
-
 // The walk's table of desc's nodes; fn: the entry's name, for the message of what is refused.
 std::vector<WalkNode> walkTable(const mi_scene_desc& d, const char* fn) {
   auto need = [fn](bool ok, const char* what) { if (!ok) throw std::invalid_argument(std::string(fn) + ": " + what); };
@@ -84,7 +71,6 @@ std::vector<WalkNode> walkTable(const mi_scene_desc& d, const char* fn) {
   need(N == 0 || nodes[0].skip == N, "BVH root does not span the node array");
   return nodes;
 }
-}  // namespace
 
 void pointQueryHost(const mi_scene_desc& d, int kind, const mi_point* points, void* out, size_t n, uint64_t* visits) {
   const std::vector<WalkNode> nodes = walkTable(d, "mi_point_query_host");

@@ -180,6 +180,26 @@ int mi_near_fill_host(const mi_scene_desc* desc, const mi_point* points, const u
   return guarded([&] { nearFillHost(*desc, points, offsets, hits, capacity, n, visits); });
 }
 
+// Box queries: the host twins of mi_box_query* / mi_box_offsets* / mi_box_fill* (box_query_host.cpp)
+int mi_box_query_host(const mi_scene_desc* desc, int kind, const mi_box* boxes, void* out, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_box_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (kind != MI_BOX_ANY && kind != MI_BOX_COUNT) { g_err = "mi_box_query_host: unknown box kind"; return MI_ERR_INVALID_ARG; }
+  if (n && (!boxes || !out)) { g_err = "mi_box_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { boxQueryHost(*desc, kind, boxes, out, n, visits); });
+}
+
+int mi_box_offsets_host(const mi_scene_desc* desc, const mi_box* boxes, uint64_t* offsets, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_box_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!boxes || !offsets)) { g_err = "mi_box_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { boxOffsetsHost(*desc, boxes, offsets, n, visits); });
+}
+
+int mi_box_fill_host(const mi_scene_desc* desc, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_box_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!boxes || !offsets || !hits)) { g_err = "mi_box_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { boxFillHost(*desc, boxes, offsets, hits, capacity, n, visits); });
+}
+
 // The canonical primitive table of desc's arrays: the host twin of canon_prim_kernel (canon_kernels.hpp, mi_scene_set_geometry*) -
 // the same prefix, the same search and record per canonical index (canon_prims.hpp), the same checks with mi_scene_create's words
 int mi_canonical_prims(const mi_scene_desc* desc, void* out, uint32_t capacity, uint32_t* count) {

@@ -99,11 +99,28 @@ void buildCompactBvh(const std::vector<BuildPrim>& prims, std::vector<mi_bvh_nod
 void refitCompactBvh(const mi_scene_desc& desc, mi_bvh_node* out);
 // lbvh.cpp: the host twin of mi_scene_rebuild
 void buildLbvhCompact(const mi_scene_desc& desc, std::vector<mi_bvh_node>& nodes, uint32_t& maxDepth);
+// point_query_host.cpp: what the host twins' walks read of a node - the decoded box, where the walk goes on when the box is passed,
+// and for a leaf the first 40 bytes of the device's leaf record (kind, nine floats) with the ids a result reports - and the table of
+// desc's nodes (fn: the entry's name, for the message of what is refused)
+struct WalkNode {
+  float minx, maxx, miny, maxy, minz, maxz;
+  uint32_t skip;        // the node behind this node's subtree (a leaf's: i + 1)
+  uint32_t kind;        // 0 triangle, 1 sphere, 2 disc; kInterior for an interior node
+  float f[9];
+  uint32_t primID;
+  uint16_t geomID;
+};
+constexpr uint32_t kInterior = 0xFFFFFFFFu;
+std::vector<WalkNode> walkTable(const mi_scene_desc& desc, const char* fn);
 // point_query_host.cpp: the host twin of mi_point_query (visits: {box tests, primitive evaluations}, may be null)
 void pointQueryHost(const mi_scene_desc& desc, int kind, const mi_point* points, void* out, size_t n, uint64_t* visits);
 // point_query_host.cpp: the host twins of mi_near_offsets / mi_near_fill (the same visits)
 void nearOffsetsHost(const mi_scene_desc& desc, const mi_point* points, uint64_t* offsets, size_t n, uint64_t* visits);
 void nearFillHost(const mi_scene_desc& desc, const mi_point* points, const uint64_t* offsets, mi_neighbour* hits, size_t capacity, size_t n, uint64_t* visits);
+// box_query_host.cpp: the host twins of mi_box_query / mi_box_offsets / mi_box_fill (the same visits)
+void boxQueryHost(const mi_scene_desc& desc, int kind, const mi_box* boxes, void* out, size_t n, uint64_t* visits);
+void boxOffsetsHost(const mi_scene_desc& desc, const mi_box* boxes, uint64_t* offsets, size_t n, uint64_t* visits);
+void boxFillHost(const mi_scene_desc& desc, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t* visits);
 
 // glb_reader.cpp: meshes of a glTF-binary file with node transforms baked in, file order kept
 std::vector<TriMesh> loadGlbMeshes(const std::string& path, bool loadNormals);

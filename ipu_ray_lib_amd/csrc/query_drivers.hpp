@@ -1,5 +1,5 @@
-// The host side of the five query families - ray queries (mi_query*), point queries (mi_point_query*), crossing counts and
-// signs (mi_count_query*, mi_point_sign*), crossing lists (mi_list_*) and neighbour lists (mi_near_*): one launch frame, one
+// The host side of the six query families - ray queries (mi_query*), point queries (mi_point_query*), crossing counts and
+// signs (mi_count_query*, mi_point_sign*), crossing lists (mi_list_*), neighbour lists (mi_near_*) and box queries (mi_box_*): one launch frame, one
 // build selection, one argument checker, one two-slot host pipeline, and the extern "C" entries on top of them. Included by
 // raylib.hip, in its translation unit, once mi_scene, LaunchSlot, guarded, HIP_CHECK and kMaxWorkItems are defined
 // (group_render.hpp is included the same way). A new family supplies a kernel header, a launcher body inside launchFrame, its
@@ -177,6 +177,38 @@ void launchNearFill(mi_scene& S, const mi_point* d_points, const uint64_t* d_off
   });
 }
 
+// Box queries (mi_box_query_device): whether a primitive touches each box (MI_BOX_ANY, n bytes) or how many do (MI_BOX_COUNT, n
+// uint32_t), one thread per box (box_kernels.hpp). full_stats picks the instrumented build; no other option applies.
+void launchBoxQuery(mi_scene& S, int kind, const mi_box* d_boxes, void* d_out, size_t n, hipStream_t stream) {
+  launchFrame(S, "mi_box_query", "boxes", n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
+    withFlag(kind == MI_BOX_COUNT, [&](auto count) { pickBuild<false, false>(S.opt, [&](auto b) {
+      hipLaunchKernelGGL((box_query_kernel<decltype(count)::value, decltype(b)::stats>), grid, block, 0, stream, dsv, d_boxes, d_out, cnt);
+    }); });
+  });
+}
+
+// Box lists, step 1 (mi_box_offsets_device): d_incl[i] = the primitives touching boxes 0 .. i. box_count_kernel writes the counts
+// as 64 bits, scanOffsets sums them.
+void launchBoxOffsets(mi_scene& S, const mi_box* d_boxes, uint64_t* d_incl, size_t n, hipStream_t stream) {
+  launchFrame(S, "mi_box_offsets", "boxes", n, stream, [&](LaunchSlot& slot, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
+    pickBuild<false, false>(S.opt, [&](auto b) {
+      hipLaunchKernelGGL(box_count_kernel<decltype(b)::stats>, grid, block, 0, stream, dsv, d_boxes, d_incl, cnt);
+    });
+    HIP_CHECK(hipGetLastError());
+    scanOffsets(slot, d_incl, cnt, stream);
+  });
+}
+
+// Box lists, step 2 (mi_box_fill_device): box_fill_kernel, one thread per box. boxBase: the index of the launch's first box in the
+// caller's numbering (the host entry's batches).
+void launchBoxFill(mi_scene& S, const mi_box* d_boxes, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, uint32_t boxBase, size_t n, hipStream_t stream) {
+  launchFrame(S, "mi_box_fill", "boxes", n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
+    pickBuild<false, false>(S.opt, [&](auto b) {
+      hipLaunchKernelGGL(box_fill_kernel<decltype(b)::stats>, grid, block, 0, stream, dsv, d_boxes, d_offsets, d_hits, (uint64_t)capacity, boxBase, cnt);
+    });
+  });
+}
+
 // ------------------------------------------------------------------------------------------------------
 // argument rules
 // ------------------------------------------------------------------------------------------------------
@@ -188,6 +220,7 @@ struct BufferRule { const void* p; size_t align; const char* why; };
 constexpr const char* kBuffers16 = "buffers must be 16-byte aligned";
 constexpr const char* kRays16 = "rays must be 16-byte aligned";
 constexpr const char* kPoints16 = "points must be 16-byte aligned";
+constexpr const char* kBoxes16 = "boxes must be 16-byte aligned";
 constexpr size_t kNoLimit = ~(size_t)0;      // (a host entry: its limit is per batch, hostBatch)
 
 // The argument rules of every query entry, in the order the entries have always applied them: the scene, the kind (kindBad: the
@@ -229,7 +262,11 @@ bool pointSignBad(const char* fn, const mi_scene* scene, int kind, const void* p
   return queryArgsBad(fn, scene, kind != MI_SIGN_INSIDE && kind != MI_SIGN_DISTANCE ? "unknown sign kind" : nullptr, dir, n, limit, "points",
                       {{points, 16, kBuffers16}, {out, kind == MI_SIGN_DISTANCE ? 16u : 1u, kBuffers16}});
 }
-// (the crossing lists' and the neighbour lists' entries: `in` the rays or the points; hits: only the fill's)
+bool boxQueryBad(const char* fn, const mi_scene* scene, int kind, const void* boxes, const void* out, size_t n, size_t limit) {
+  return queryArgsBad(fn, scene, kind != MI_BOX_ANY && kind != MI_BOX_COUNT ? "unknown box kind" : nullptr, nullptr, n, limit, "boxes",
+                      {{boxes, 16, kBoxes16}, {out, kind == MI_BOX_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
+}
+// (the entries of the crossing lists, the neighbour lists and the box lists: `in` the rays, the points or the boxes; hits: only the fill's)
 bool listQueryBad(const char* fn, const mi_scene* scene, const char* noun, const char* inWhy, const void* in, const void* offsets, const void* hits, bool fill, size_t n, size_t limit) {
   return queryArgsBad(fn, scene, nullptr, nullptr, n, limit, noun,
                       {{in, 16, inWhy}, {offsets, 8, "offsets must be 8-byte aligned"}, {hits, fill ? 16u : 0u, "hits must be 16-byte aligned"}});
@@ -292,7 +329,7 @@ void pipelinedQuery(mi_scene* scene, const void* in, size_t inSize, void* out, s
   } catch (...) { (void)hipDeviceSynchronize(); throw; }
 }
 
-// mi_list_offsets and mi_near_offsets on host buffers: every batch's prefix sum starts at 0 on the device; what precedes the
+// mi_list_offsets, mi_near_offsets and mi_box_offsets on host buffers: every batch's prefix sum starts at 0 on the device; what precedes the
 // batch is added here, batch by batch.
 template <class Launch>
 void offsetsHost(mi_scene* scene, const void* in, size_t inSize, uint64_t* offsets, size_t n, size_t batch, const Launch& launch) {
@@ -305,7 +342,7 @@ void offsetsHost(mi_scene* scene, const void* in, size_t inSize, uint64_t* offse
   }
 }
 
-// mi_list_fill and mi_near_fill on host buffers (in: rays or points of inSize bytes; hits: 16-byte records of either kind;
+// mi_list_fill, mi_near_fill and mi_box_fill on host buffers (in: rays, points or boxes of inSize bytes; hits: 16-byte records of any of the kinds;
 // launch(d_in, d_offsets, d_hits, capacity, base, cnt, stream) enqueues one batch's fill): the pipeline's slots - the result buffer
 // carries a batch's offsets in - plus a staging buffer of records per slot. A batch's segments are packed from 0 in the staging -
 // the device sees offsets of its own, cut at `capacity` here already - and copied to where the caller's offsets put them: in one
@@ -517,6 +554,63 @@ int mi_near_fill(mi_scene* scene, const mi_point* points, const uint64_t* offset
   return guarded([&] {
     listFillHost(scene, points, sizeof(mi_point), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_neighbour* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
       launchNearFill(*scene, static_cast<const mi_point*>(d_in), d_off, d_hits, cap, base, cnt, st);
+    });
+  });
+}
+
+int mi_box_query_device(mi_scene* scene, int kind, const void* d_boxes, void* d_out, size_t n, void* hip_stream) {
+  if (boxQueryBad("mi_box_query_device", scene, kind, d_boxes, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] { launchBoxQuery(*scene, kind, static_cast<const mi_box*>(d_boxes), d_out, n, (hipStream_t)hip_stream); });
+}
+
+int mi_box_query(mi_scene* scene, int kind, const mi_box* boxes, void* out, size_t n) {
+  if (boxQueryBad("mi_box_query", scene, kind, boxes, out, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch("mi_box_query", "boxes", scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    pipelinedQuery(scene, boxes, sizeof(mi_box), out, kind == MI_BOX_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchBoxQuery(*scene, kind, static_cast<const mi_box*>(d_in), d_out, cnt, st);
+    });
+  });
+}
+
+int mi_box_offsets_device(mi_scene* scene, const void* d_boxes, uint64_t* d_offsets, size_t n, void* hip_stream) {
+  if (listQueryBad("mi_box_offsets_device", scene, "boxes", kBoxes16, d_boxes, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] {
+    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
+    launchBoxOffsets(*scene, static_cast<const mi_box*>(d_boxes), d_offsets + 1, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_box_fill_device(mi_scene* scene, const void* d_boxes, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream) {
+  if (listQueryBad("mi_box_fill_device", scene, "boxes", kBoxes16, d_boxes, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] { launchBoxFill(*scene, static_cast<const mi_box*>(d_boxes), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
+}
+
+int mi_box_offsets(mi_scene* scene, const mi_box* boxes, uint64_t* offsets, size_t n) {
+  if (listQueryBad("mi_box_offsets", scene, "boxes", kBoxes16, boxes, offsets, nullptr, false, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch("mi_box_offsets", "boxes", scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    offsetsHost(scene, boxes, sizeof(mi_box), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchBoxOffsets(*scene, static_cast<const mi_box*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
+    });
+  });
+}
+
+int mi_box_fill(mi_scene* scene, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n) {
+  if (listQueryBad("mi_box_fill", scene, "boxes", kBoxes16, boxes, offsets, hits, true, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch("mi_box_fill", "boxes", scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    listFillHost(scene, boxes, sizeof(mi_box), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_overlap* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
+      launchBoxFill(*scene, static_cast<const mi_box*>(d_in), d_off, d_hits, cap, base, cnt, st);
     });
   });
 }

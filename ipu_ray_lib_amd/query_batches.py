@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import RAY, POINT, POINT_HIT, INVALID_PRIM      # noqa: F401  (the record dtypes of ray and point queries, side by side)
+from . import RAY, POINT, POINT_HIT, BOX, INVALID_PRIM      # noqa: F401  (the record dtypes of ray and point queries, side by side)
 
 RAY_EPSILON = np.float32(5.9604644775390625e-08 * 1500.0)       # ray_math.h kRayEpsilon (precision_utils.hpp)
 LIGHT = np.array([18.0, 257.0, -1060.0], np.float32)            # the reference's shadow-trace light (trace.cpp:247)
@@ -34,6 +34,14 @@ def make_points(positions: np.ndarray, radius=np.inf) -> np.ndarray:
         p[c] = positions[:, k]
     p["radius"] = radius
     return p
+
+
+def make_boxes(lo: np.ndarray, hi: np.ndarray) -> np.ndarray:
+    """A BOX array from [N, 3] lower and upper corners (box queries: IpuScene.touches / count_overlaps / list_overlaps)."""
+    b = np.zeros(len(lo), BOX)
+    b["lo"] = lo
+    b["hi"] = hi
+    return b
 
 
 def primary_rays(host_scene) -> np.ndarray:
