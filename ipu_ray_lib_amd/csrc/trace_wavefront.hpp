@@ -534,7 +534,9 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
             GLeaf L;
             if constexpr (ROT) {
               // the block of the cast's shear axis: the same three loads (16 + 16 + 8 bytes), the vertices arrive rotated
-              const GLeafBlock B = *reinterpret_cast<const GLeafBlock*>(reinterpret_cast<const char*>(sc.leavesRot) + (recNode << 2) + sh.kz * 40u);
+              // (the two offsets are summed in 32 bits first: added to the pointer one by one, hipcc carries `leavesRot + kz * 40` as a 64-bit
+              // pair through the whole cast and the loads lose the scalar-base form)
+              const GLeafBlock B = *reinterpret_cast<const GLeafBlock*>(reinterpret_cast<const char*>(sc.leavesRot) + ((recNode << 2) + sh.kz * 40u));
               L.type = B.type;
 #pragma unroll
               for (int q = 0; q < 9; ++q) L.f[q] = B.f[q];
@@ -571,7 +573,17 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           // so a box test follows at once (tune.leafThenNode) and the vote after it sees its outcome
           if (tune.leafThenNode) {
             if (STATS) { itN++; lnN += (uint32_t)__popcll(__ballot(ph == PH_NODE)); }
-            nodeStep();      // (from global memory in the HOT builds too: with the choice the 80-register builds spill, and the frame is no faster - profiles/r06_k1w_hot_nodes_ab.txt)
+            // (from global memory in the HOT builds too: with the choice the 80-register builds spill, and the frame is no faster - profiles/r06_k1w_hot_nodes_ab.txt;
+            // in the select form below the choice no longer spills and still loses 1.2 % - profiles/r11_k1w_leaf_turn.txt §3b)
+            if constexpr (SPEC) nodeStep();       // (the SPEC form keeps its own phase bookkeeping)
+            else if (ph == PH_NODE) {
+              // The phase is written back as behind the spelled-out runs - two selects and a compare. Test by test (nodeStep) hipcc builds it
+              // from a chain of exec regions, some fifty instructions more in every LEAF turn (profiles/r11_k1w_leaf_turn.txt).
+              if (anyExact) (void)nodeBodyT(std::true_type{}, std::true_type{}, std::false_type{});
+              else (void)nodeBody();
+              ph = (node & kLeafFlag) ? PH_LEAF : ((node >= numNodes) ? PH_SHADE : PH_NODE);
+              node &= ~kLeafFlag;
+            }
             ++steps;
           }
         }
