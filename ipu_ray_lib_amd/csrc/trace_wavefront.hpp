@@ -8,6 +8,8 @@
 //     SHADE traversal finished: hit update, BxDF, roulette   (codelets/TraceCodelets.cpp:214-257)
 //     GEN   next sample's camera ray                          (codelets/TraceCodelets.cpp:142-164)
 //     FETCH work unit finished: write it back, take another one from the global work counter
+// (the phase is no register: it is read off the lane's `node` word - kGenNode below - so no turn writes it back and every vote is a
+// compare of that word)
 // and each loop iteration the wave votes (ballot + popcount, scalar) and runs the phase most of its
 // lanes are waiting in (SHADE and GEN are served by ONE turn: template parameter MERGE). A lane that
 // finishes a path starts its next sample in the turn that ended the path, a lane that
@@ -27,6 +29,13 @@
 namespace mi {
 
 enum : uint32_t { PH_NODE = 0, PH_LEAF = 1, PH_SHADE = 2, PH_GEN = 3, PH_FETCH = 4, PH_DONE = 5 };
+// The phase of a lane is not a register of its own: it is read off `node` (every build but SPEC, whose lanes wait for a primitive
+// test while their node walks on). Between cast set-up and SHADE the walk decides it - node < numNodes: NODE; kLeafFlag set (the
+// lane stopped at a primitive; the flag stays in the register until the LEAF turn forms the record's address): LEAF; flag clear and
+// numNodes <= node < kGenNode (the walk ran off the array's end - a link of numNodes << 5): SHADE. GEN, FETCH and DONE are three
+// values with the flag clear that no byte offset reaches: a scene has fewer than 2^26 nodes, so offsets end at 0x7FFFFFE0.
+constexpr uint32_t kGenNode = 0x7FFFFFFDu, kFetchNode = 0x7FFFFFFEu, kDoneNode = 0x7FFFFFFFu;
+static_assert(kGenNode > ((kLeafFlag >> 5) - 1u) << 5 && kDoneNode < kLeafFlag && kFetchNode == kGenNode + (PH_FETCH - PH_GEN) && kDoneNode == kGenNode + (PH_DONE - PH_GEN), "the parked phases lie between the largest byte offset and the leaf flag");
 
 // Scheduling weights (quarter units, NODE/TRAVERSE weigh 4) and traversal-burst limits; the defaults
 // {8, 16, 24, 48, 3} (dbl 4, maxExtra 6) are the measured optimum over the box and the Collada scene (+-1 % plateau):
@@ -152,13 +161,22 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
   const uint32_t numNodes = sc.numNodes << 5;
   const uint32_t spp = ex.sampleCount ? ex.sampleCount : sc.samplesPerPixel;
   const bool segd = ex.segPart != nullptr || slots;          // (pixel, segment) work atoms
-  const uint32_t segShift = segment_shift(sc.samplesPerPixel), segMask = (1u << segShift) - 1u;
+  // (read back as a scalar: hipcc evaluates the clamp in vector registers and otherwise keeps shift and mask there for the whole kernel -
+  // two of the 80, one of them spilled in the barycentric builds)
+  const uint32_t segShift = (uint32_t)__builtin_amdgcn_readfirstlane((int)segment_shift(sc.samplesPerPixel)), segMask = (1u << segShift) - 1u;
   const uint32_t segs = segd ? ex.segments : 1u;
   const uint32_t items = n * segs;                 // (host checks that this fits 32 bits)
 
   // ---- lane state ----
-  uint32_t ph = PH_FETCH;
-  uint32_t sample = 0, bounce = 0, node = 0, pendLeaf = 0;
+  constexpr bool kPhInNode = !SPEC;
+  uint32_t ph = PH_FETCH;      // (SPEC only)
+  uint32_t sample = 0, bounce = 0, node = kPhInNode ? kFetchNode : 0u, pendLeaf = 0;
+  auto inNode = [&]() -> bool { return kPhInNode ? node < numNodes : ph == PH_NODE; };
+  auto inLeaf = [&]() -> bool { return kPhInNode ? (int32_t)node < 0 : ph == PH_LEAF; };
+  auto inShade = [&]() -> bool { return kPhInNode ? node - numNodes < kGenNode - numNodes : ph == PH_SHADE; };
+  auto inGen = [&]() -> bool { return kPhInNode ? node == kGenNode : ph == PH_GEN; };
+  auto inFetch = [&]() -> bool { return kPhInNode ? node == kFetchNode : ph == PH_FETCH; };
+  auto park = [&](uint32_t p) { if (kPhInNode) node = kGenNode + (p - PH_GEN); else ph = p; };      // p = PH_GEN, PH_FETCH or PH_DONE
   uint32_t pend1 = 0xFFFFFFFFu, pend1Node = 0, specNodes = 0;       // SPEC: the primitive test the lane has walked past, where it was found, box tests made since (STATS)
   float prow = 0.f, pcol = 0.f;
   Rng rng; rng.s0 = rng.s1 = 0;
@@ -251,7 +269,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
     // Work is taken from the global counter in chunks (ex.fetchChunk indices, a multiple of 64 = whole 8x8 tiles)
     // and handed out to the lanes from the wave's local range: one global atomic per chunk, not per service.
     for (;;) {
-      const unsigned long long mF = __ballot(ph == PH_FETCH);
+      const unsigned long long mF = __ballot(inFetch());
       if (!mF) break;
       if (chunkNext >= chunkEnd) {
         const uint32_t firstF = (uint32_t)__ffsll((long long)mF) - 1u;
@@ -263,7 +281,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
       const uint32_t avail = chunkEnd - chunkNext, rankF = lane_rank(mF);
       const uint32_t chunkBase = chunkNext;
       chunkNext += min((uint32_t)__popcll(mF), avail);
-      if (ph == PH_FETCH && rankF < avail) {
+      if (inFetch() && rankF < avail) {
         const uint32_t idx = chunkBase + rankF;
         if (idx < items) {
           // When the stream is made of full rows of width tileStreamW (a multiple of 8), consecutive work indices
@@ -286,16 +304,16 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           rng_seed_pixel_segment(rng, sc.rngSeed, prow, pcol, seg);
           sample = (slots ? seg - ex.segBase : seg) << segShift;      // slots are numbered within the launch
           pathStore();                 // (GEN initialises the rest)
-          ph = PH_GEN;
+          park(PH_GEN);
         } else {
-          ph = PH_DONE;
+          park(PH_DONE);
         }
       }
     }
 
     // ---------------- vote ----------------
-    uint32_t cN = (uint32_t)__popcll(__ballot(ph == PH_NODE)), cL = (uint32_t)__popcll(__ballot(ph == PH_LEAF));
-    uint32_t cS = (uint32_t)__popcll(__ballot(ph == PH_SHADE)), cG = (uint32_t)__popcll(__ballot(ph == PH_GEN));
+    uint32_t cN = (uint32_t)__popcll(__ballot(inNode())), cL = (uint32_t)__popcll(__ballot(inLeaf()));
+    uint32_t cS = (uint32_t)__popcll(__ballot(inShade())), cG = (uint32_t)__popcll(__ballot(inGen()));
     if ((cN | cL | cS | cG) == 0) break;            // every ray DONE (FETCH lanes were just served)
     // Top-level vote: TRAVERSE (the NODE and LEAF populations together) against SHADE and GEN, by weighted
     // population (a phase cannot use more than 64 lanes). Inside TRAVERSE a two-way mini-vote (two ballots)
@@ -319,10 +337,9 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
       // per-burst fact
       bool anyExact = !FAST && __ballot(exactSlab) != 0ull;
       // One box test of a lane that is in the NODE phase; returns whether the lane is still in it afterwards, so that
-      // back-to-back tests narrow the exec mask from that condition directly instead of re-reading `ph`.
-      // deferTag (the spelled-out run of box tests only): the lane's phase is not updated test by test; the phase of
-      // every lane that took part is derived once, behind the run, from the node value it stopped with.
-      auto nodeBodyT = [&](auto exactTag, auto deferTag, auto ldsTag) -> bool {
+      // back-to-back tests narrow the exec mask from that condition directly. The node the lane stops with IS its phase
+      // (the SPEC form alone keeps a phase word, test by test).
+      auto nodeBodyT = [&](auto exactTag, auto ldsTag) -> bool {
         {
           GNode nd;
           typedef uint32_t ProbeVec __attribute__((ext_vector_type(4)));
@@ -398,21 +415,34 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           // the record it waits for is leaves[node - 1], nothing is carried from this step to the LEAF turn.
           node = boxHit ? nd.hit : nd.link;
           // (an LDS run compares with the staged prefix's end instead: a cold node reads as "stop" too, and the lane stays in NODE)
-          if constexpr (decltype(deferTag)::value) {
-            return node < ((HOT && decltype(ldsTag)::value) ? hotBytes : numNodes);      // the phase is derived once, behind the run of box tests
-          } else {
-            if (node & kLeafFlag) { node &= ~kLeafFlag; ph = PH_LEAF; return false; }
-            if (node >= numNodes) { ph = PH_SHADE; return false; }
-            return true;
+          return node < ((HOT && decltype(ldsTag)::value) ? hotBytes : numNodes);
+        }
+      };
+      auto nodeBody = [&]() -> bool { return nodeBodyT(std::false_type{}, std::false_type{}); };               // the common case: no lane needs the literal test
+      auto nodeBodyH = [&]() -> bool { return nodeBodyT(std::false_type{}, std::true_type{}); };             // ... and every lane of the run stands in the staged prefix (HOT)
+      auto nodeStep = [&]() { if (inNode()) (void)(anyExact ? nodeBodyT(std::true_type{}, std::false_type{}) : nodeBodyT(std::false_type{}, std::false_type{})); };
+      // (instrumented HOT build: the same choice per step, so that the counters describe what the plain build does per run)
+      auto nodeStepH = [&]() { if (inNode() && node < hotBytes) (void)nodeBodyT(std::false_type{}, std::true_type{}); };
+      // A run of 1 + extra box tests, spelled out rather than looped: straight-line code, and each further test runs under the previous
+      // one's "still walking" condition. (94 % of the runs are full length; a ladder of their own that never asks for the length again, beside
+      // this one or beside a rolled loop for the rest, bought nothing or lost - profiles/r12_k1w_loop_control.txt.)
+      auto boxTestRun = [&](auto& body, uint32_t extra) {
+        bool go = body();
+        if (extra >= 1 && go) { go = body();
+          if (extra >= 2 && go) { go = body();
+            if (extra >= 3 && go) { go = body();
+              if (extra >= 4 && go) { go = body();
+                if (extra >= 5 && go) { go = body();
+                  if (extra >= 6 && go) { go = body();
+                    if (extra >= 7 && go) (void)body();
+                  }
+                }
+              }
+            }
           }
         }
       };
-      auto nodeBody = [&]() -> bool { return nodeBodyT(std::false_type{}, std::true_type{}, std::false_type{}); };               // the common case: no lane needs the literal test
-      auto nodeBodyH = [&]() -> bool { return nodeBodyT(std::false_type{}, std::true_type{}, std::true_type{}); };             // ... and every lane of the run stands in the staged prefix (HOT)
-      auto nodeStep = [&]() { if (ph == PH_NODE) (void)(anyExact ? nodeBodyT(std::true_type{}, std::false_type{}, std::false_type{}) : nodeBodyT(std::false_type{}, std::false_type{}, std::false_type{})); };
-      // (instrumented HOT build: the same choice per step, so that the counters describe what the plain build does per run)
-      auto nodeStepH = [&]() { if (ph == PH_NODE && node < hotBytes) (void)nodeBodyT(std::false_type{}, std::false_type{}, std::true_type{}); };
-      auto coldLanes = [&]() -> unsigned long long { return __ballot(ph == PH_NODE && node >= hotBytes); };
+      auto coldLanes = [&]() -> unsigned long long { return __ballot(kPhInNode ? node - hotBytes < numNodes - hotBytes : (ph == PH_NODE && node >= hotBytes)); };      // (hotBytes <= numNodes: one range compare)
       for (;;) {
         const uint32_t stay = cN;
         const uint32_t cP = SPEC ? (uint32_t)__popcll(__ballot(pend1 != 0xFFFFFFFFu)) : 0u;
@@ -429,14 +459,14 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
               itH++; lnH += stay;
               nodeStepH();
               for (uint32_t e = 0; e < extra; ++e) {
-                const uint32_t in = (uint32_t)__popcll(__ballot(ph == PH_NODE && node < hotBytes));
+                const uint32_t in = (uint32_t)__popcll(__ballot(inNode() && node < hotBytes));
                 itN++; lnN += in; itH++; lnH += in;
                 nodeStepH();
               }
             } else {
             if (HOT) { itC++; lnC += stay; }
             nodeStep();
-            for (uint32_t e = 0; e < extra; ++e) { const uint32_t in = (uint32_t)__popcll(__ballot(ph == PH_NODE)); itN++; lnN += in; if (HOT) { itC++; lnC += in; } nodeStep(); }
+            for (uint32_t e = 0; e < extra; ++e) { const uint32_t in = (uint32_t)__popcll(__ballot(inNode())); itN++; lnN += in; if (HOT) { itC++; lnC += in; } nodeStep(); }
             }
           } else if (anyExact) {
             // (a lane of this burst needs the literal compare/select box test: the rolled form carries it)
@@ -444,45 +474,9 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
             for (uint32_t e = 0; e < extra; ++e) nodeStep();
           } else if (HOT && coldLanes() == 0ull) {
             // the same run with every load a pair of ds_read_b128 and the prefix's end for the array's: no lane of the wave stands at a cold node
-            if (ph == PH_NODE) {
-              bool go = nodeBodyH();
-              if (extra >= 1 && go) { go = nodeBodyH();
-                if (extra >= 2 && go) { go = nodeBodyH();
-                  if (extra >= 3 && go) { go = nodeBodyH();
-                    if (extra >= 4 && go) { go = nodeBodyH();
-                      if (extra >= 5 && go) { go = nodeBodyH();
-                        if (extra >= 6 && go) { go = nodeBodyH();
-                          if (extra >= 7 && go) (void)nodeBodyH();
-                        }
-                      }
-                    }
-                  }
-                }
-              }
-              ph = (node & kLeafFlag) ? PH_LEAF : ((node >= numNodes) ? PH_SHADE : PH_NODE);      // (a lane that stopped at a cold node stays in NODE)
-              node &= ~kLeafFlag;
-            }
-          } else if (ph == PH_NODE) {
-            // spelled out rather than looped: straight-line code, and each further test runs under the previous
-            // one's "still walking" condition instead of re-reading `ph`
-            bool go = nodeBody();
-            if (extra >= 1 && go) { go = nodeBody();
-              if (extra >= 2 && go) { go = nodeBody();
-                if (extra >= 3 && go) { go = nodeBody();
-                  if (extra >= 4 && go) { go = nodeBody();
-                    if (extra >= 5 && go) { go = nodeBody();
-                      if (extra >= 6 && go) { go = nodeBody();
-                        if (extra >= 7 && go) (void)nodeBody();
-                      }
-                    }
-                  }
-                }
-              }
-            }
-            if (!SPEC) {        // (the SPEC form keeps its own phase bookkeeping, test by test)
-              ph = (node & kLeafFlag) ? PH_LEAF : ((node >= numNodes) ? PH_SHADE : PH_NODE);
-              node &= ~kLeafFlag;
-            }
+            if (inNode()) boxTestRun(nodeBodyH, extra);      // (a lane that stopped at a cold node is still in NODE)
+          } else if (inNode()) {
+            boxTestRun(nodeBody, extra);
           }
           steps += extra;
         } else {
@@ -526,10 +520,12 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
               }
             }
           } else
-          if (ph == PH_LEAF) {
+          if (inLeaf()) {
             if (STATS) cs.leaves++;
-            const uint32_t atLeaf = HOT ? (node >> 5) : (node >> 5) - 1u;   // the leaf the lane stopped at (its link is the node after it; HOT: the lane stands at the leaf itself)
-            const uint32_t recNode = HOT ? node : node - 32u;
+            const uint32_t at = node & ~kLeafFlag;      // (the flag is the lane's phase up to here; it falls out of the shifts below, no instruction of its own)
+            if (!HOT) node = at;
+            const uint32_t atLeaf = HOT ? (at >> 5) : (at >> 5) - 1u;   // the leaf the lane stopped at (its link is the node after it; HOT: the lane stands at the leaf itself)
+            const uint32_t recNode = HOT ? at : at - 32u;
             // (uniform base + 32-bit byte offset, as for the nodes: a 64-byte record per 32-byte node)
             GLeaf L;
             if constexpr (ROT) {
@@ -567,28 +563,24 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
             const bool closer = cand & (t > 0.f) & (t < hit.t);
             hit.t = closer ? t : hit.t; hit.leaf = closer ? atLeaf : hit.leaf;
             if constexpr (BARY) { hit.b0 = closer ? b0 : hit.b0; hit.b1 = closer ? b1 : hit.b1; hit.b2 = closer ? b2 : hit.b2; }
-            ph = (node >= numNodes) ? PH_SHADE : PH_NODE;
           }
           // every lane that waited for a primitive test is walking again: the next vote would pick NODE anyway,
           // so a box test follows at once (tune.leafThenNode) and the vote after it sees its outcome
           if (tune.leafThenNode) {
-            if (STATS) { itN++; lnN += (uint32_t)__popcll(__ballot(ph == PH_NODE)); }
+            if (STATS) { itN++; lnN += (uint32_t)__popcll(__ballot(inNode())); }
             // (from global memory in the HOT builds too: with the choice the 80-register builds spill, and the frame is no faster - profiles/r06_k1w_hot_nodes_ab.txt;
             // in the select form below the choice no longer spills and still loses 1.2 % - profiles/r11_k1w_leaf_turn.txt §3b)
             if constexpr (SPEC) nodeStep();       // (the SPEC form keeps its own phase bookkeeping)
-            else if (ph == PH_NODE) {
-              // The phase is written back as behind the spelled-out runs - two selects and a compare. Test by test (nodeStep) hipcc builds it
-              // from a chain of exec regions, some fifty instructions more in every LEAF turn (profiles/r11_k1w_leaf_turn.txt).
-              if (anyExact) (void)nodeBodyT(std::true_type{}, std::true_type{}, std::false_type{});
+            else if (inNode()) {
+              // (one exec region: test by test through nodeStep hipcc builds a chain of them - profiles/r11_k1w_leaf_turn.txt)
+              if (anyExact) (void)nodeBodyT(std::true_type{}, std::false_type{});
               else (void)nodeBody();
-              ph = (node & kLeafFlag) ? PH_LEAF : ((node >= numNodes) ? PH_SHADE : PH_NODE);
-              node &= ~kLeafFlag;
             }
             ++steps;
           }
         }
-        cN = (uint32_t)__popcll(__ballot(ph == PH_NODE));
-        cL = (uint32_t)__popcll(__ballot(ph == PH_LEAF));
+        cN = (uint32_t)__popcll(__ballot(inNode()));
+        cL = (uint32_t)__popcll(__ballot(inLeaf()));
         if (++steps >= tune.burst || (cN + cL) * 8u < startT * tune.keep8 || (cN + cL) == 0) break;
       }
       if (tune.prio == 1) __builtin_amdgcn_s_setprio(0); else if (tune.prio == 2) __builtin_amdgcn_s_setprio(1);
@@ -603,7 +595,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
       const unsigned long long tq1 = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
       bool envRay = false, pathEnd = false, genNow = false, setup = false;
       uint32_t envSlot = 0;
-      const bool wasShade = ph == PH_SHADE, wasGen = ph == PH_GEN;
+      const bool wasShade = inShade(), wasGen = inGen();
       if (wasShade || wasGen) pathLoad();
       if (wasShade) {
         bool terminated = false;
@@ -668,7 +660,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
               float* part = ex.segPart + 3 * ((size_t)(((sample - 1u) >> segShift) - ex.segBase) * n + pixNow);
               part[0] = coldF(3); part[1] = coldF(4); part[2] = coldF(5);
             }
-            ph = PH_FETCH;
+            park(PH_FETCH);
           } else {
             if (!slots && ex.segPart) {
               float* part = ex.segPart + 3 * ((size_t)(((sample - 1u) >> segShift) - ex.segBase) * n + pixNow);
@@ -686,7 +678,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
             hr.throughput = {tp.x, tp.y, tp.z};
             hr.geom_id = (uint16_t)oGeom; hr.flags = (uint16_t)oFlags;
             res->h = hr;
-            ph = PH_FETCH;
+            park(PH_FETCH);
           }
         } else {
           o = offset_origin(o, d, nrm);
@@ -723,7 +715,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
         if (FAST) fast_box_setup(o, inv, oi, slabPad);
         hit.t = kInf; hit.leaf = 0xFFFFFFFFu;
         { uint32_t seen; node = root_start(sc, o, seen) << 5; if (STATS) cs.nodes += seen; }
-        ph = (numNodes > 0) ? PH_NODE : PH_SHADE;
+        if (!kPhInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
         // Slot-mode launches (NIF renders), option nif_first_test: the cast's FIRST box test runs here, in the turn that set the cast up,
         // instead of in a NODE turn. In the open scenes an environment light is for, most casts miss the root's box: they take a NODE
         // turn each for that one test - next to the few lanes that walk the mesh, 11 NODE turns per 64 casts at 20 % occupancy in
@@ -732,7 +724,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
         // Measured neutral (the walking lanes sit out the SHADE turns instead: 2.1 of them per 64 casts at half occupancy against 1.2):
         // off by default.
         if constexpr (kFirstInSetup) {
-          if (slots && ex.firstInSetup && ph == PH_NODE) {
+          if (slots && ex.firstInSetup && inNode()) {
             const GNode nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + node);
             if (STATS) cs.nodes++;
             const float ax = (nd.minx - o.x) * inv.x, bx = (nd.maxx - o.x) * inv.x;
@@ -747,8 +739,6 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
               { float tmin = az, tmax = bz; if (tmin > tmax) { const float w = tmin; tmin = tmax; tmax = w; } tmax *= kSlabScale; t0 = tmin > t0 ? tmin : t0; t1 = tmax < t1 ? tmax : t1; }
             }
             node = !(t0 > t1) ? nd.hit : nd.link;
-            ph = (node & kLeafFlag) ? PH_LEAF : ((node >= numNodes) ? PH_SHADE : PH_NODE);
-            node &= ~kLeafFlag;
           }
         }
       }
@@ -763,7 +753,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
       bool envRay = false;          // this lane's path ended in this SHADE step by escaping (slot mode)
       bool pathEnd = false;
       uint32_t envSlot = 0;
-      if (ph == PH_SHADE) {
+      if (inShade()) {
         pathLoad();
         bool terminated = false;
         if (hit.leaf != 0xFFFFFFFFu) {
@@ -819,14 +809,14 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           pathEnd = true;
           ++sample;
           const bool more = segd ? ((sample & segMask) != 0u && sample < spp) : (sample < spp);
-          if (more) ph = PH_GEN;
+          if (more) park(PH_GEN);
           else if (segd && sample < spp) {
             // a segment other than the last is complete: its partial sum (or its slots) is all it leaves
             if (!slots && ex.segPart) {
               float* part = ex.segPart + 3 * ((size_t)(((sample - 1u) >> segShift) - ex.segBase) * n + pixNow);
               part[0] = coldF(3); part[1] = coldF(4); part[2] = coldF(5);
             }
-            ph = PH_FETCH;
+            park(PH_FETCH);
           } else {
             // pixel complete: rgb sum + the LAST sample's hit record
             if (!slots && ex.segPart) {
@@ -845,7 +835,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
             hr.throughput = {tp.x, tp.y, tp.z};
             hr.geom_id = (uint16_t)oGeom; hr.flags = (uint16_t)oFlags;
             res->h = hr;
-            ph = PH_FETCH;
+            park(PH_FETCH);
           }
         } else {
           // next bounce: offsetRay + cast set-up (codelets :207-211)
@@ -859,7 +849,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           if (FAST) fast_box_setup(o, inv, oi, slabPad);
           hit.t = kInf; hit.leaf = 0xFFFFFFFFu;
           { uint32_t seen; node = root_start(sc, o, seen) << 5; if (STATS) cs.nodes += seen; }
-          ph = (numNodes > 0) ? PH_NODE : PH_SHADE;
+          if (!kPhInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
         }
         pathStore();
       }
@@ -870,7 +860,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
       // ---------------- GEN: camera ray of the next sample ----------------
       if (STATS) { itG++; lnG += cG; }
       const unsigned long long tq2 = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
-      if (ph == PH_GEN) {
+      if (inGen()) {
         pathLoad();
         if constexpr (kCoordsFromStream) {
           const uint32_t e = coldU(0);
@@ -897,7 +887,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
         if (FAST) fast_box_setup(o, inv, oi, slabPad);
         hit.t = kInf; hit.leaf = 0xFFFFFFFFu;
         { uint32_t seen; node = root_start(sc, o, seen) << 5; if (STATS) cs.nodes += seen; }
-        ph = (numNodes > 0) ? PH_NODE : PH_SHADE;
+        if (!kPhInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
         pathStore();
       }
       casts += cG;
