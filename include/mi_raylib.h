@@ -713,7 +713,12 @@ int mi_scene_set_ray_batch(mi_scene* scene, size_t rays_per_batch);
  *                                   those nodes take 0.9 of the tree's expected box tests (surface-area model, decided at create). Every result byte is the same
  *                                   either way. NIF renders, renders under double_fallback or fast, and a scene whose geometry has been updated, rebuilt
  *                                   or replaced (mi_scene_update*, mi_scene_rebuild, mi_scene_set_geometry*) run on the shared arrays whatever the option says.
- *                                   The copy is made at create, whatever the option says then (it may be set later): about 260 bytes of device memory per
+ *                                   The un-instrumented builds walk a copy from which the interior nodes whose box test cannot change a result have been
+ *                                   taken (both children's stored boxes inside the node's own, and the node more than half its nearest surviving ancestor's
+ *                                   half-area: csrc/hot_order.hpp), casts on the literal box test (a zero or denormal direction component, a non-finite
+ *                                   origin) start in a region of every node behind it; the instrumented build (full_stats) walks a copy of every node and
+ *                                   counts the reference's visits.
+ *                                   The copies are made at create, whatever the option says then (it may be set later): about 750 bytes of device memory per
  *                                   BVH node beside the shared arrays' own, given back by the first update, rebuild or replacement of the geometry
  *   "coords"        0 | 1           (pixel, segment) work units read the pixel's (u, v) from a compact copy of the stream gathered once
  *                                   per launch, not from the 84-byte record (default 1: a third of the HBM traffic)

@@ -209,6 +209,12 @@ def host_lib() -> C.CDLL:
         lib.mi_hot_walk.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_uint32, C.POINTER(C.c_int)]
         lib.mi_hot_walk.restype = C.c_uint32
         lib.mi_hot_share.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.mi_hot_collapse.argtypes = [C.c_void_p, C.c_uint32, C.c_double] + [C.c_void_p] * 8 + [C.POINTER(C.c_uint32)]
+        lib.mi_hot_join.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.mi_hot_cast_is_literal.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        lib.mi_hot_walk_count.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_uint32,
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
+        lib.mi_hot_walk_count.restype = C.c_uint32
         lib.mi_bvh_cost_compact.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_compact_block.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_estimate.argtypes = [C.POINTER(C.c_double)]
@@ -619,6 +625,60 @@ def hot_walk(device_nodes: np.ndarray, origin, direction, leaf_link: np.ndarray 
     cnt = host_lib().mi_hot_walk(device_nodes.ctypes.data, device_nodes.size, None if link is None else link.ctypes.data, o, d, visits.ctypes.data, cap, C.byref(status))
     _check_host(status.value)
     return visits[:min(cnt, cap)].copy()
+
+
+def hot_collapse(nodes: np.ndarray, theta: float = -1.0) -> dict:
+    """mi_hot_collapse: the collapsed tree plain renders walk where the private copy is on (csrc/hot_order.hpp) - {"preorder", "keep"}
+    over the BVH_NODE array's nodes, and over the survivors {"from" (preorder index of survivor j), "collapsed" (the survivors as a
+    preorder array of their own), "order", "hot", "leaf_link", "share"}; "blocked": the interior nodes only the containment rule keeps.
+    theta < 0: the device library's constant."""
+    nodes = np.ascontiguousarray(nodes, dtype=BVH_NODE)
+    n = nodes.size
+    out = {"preorder": np.zeros(n, DEVICE_NODE), "keep": np.zeros(n, np.uint8), "from": np.zeros(n, np.uint32), "collapsed": np.zeros(n, DEVICE_NODE),
+           "order": np.zeros(n, np.uint32), "hot": np.zeros(n, DEVICE_NODE), "leaf_link": np.zeros(n, np.uint32), "share": np.zeros(n, np.float64)}
+    counts = (C.c_uint32 * 2)()
+    _check_host(host_lib().mi_hot_collapse(nodes.ctypes.data if n else None, n, float(theta),
+                                           *[out[k].ctypes.data if n else None for k in ("preorder", "keep", "from", "collapsed", "order", "hot", "leaf_link", "share")], counts))
+    m = int(counts[0])
+    for k in ("from", "collapsed", "order", "hot", "leaf_link", "share"):
+        out[k] = out[k][:m].copy()
+    out["blocked"] = int(counts[1])
+    return out
+
+
+def hot_join(collapse: dict, full: dict) -> dict:
+    """mi_hot_join: the node array plain renders walk where the private copy is on - hot_collapse's tree, then hot_nodes' (every node) -
+    {"nodes", "leaf_link", "exact_start" (where a cast on the literal box test starts), "place" (preorder index of the node at place k)}."""
+    m, n = collapse["hot"].size, full["hot"].size
+    out = {"nodes": np.zeros(m + n, DEVICE_NODE), "leaf_link": np.zeros(m + n, np.uint32)}
+    start = C.c_uint32(0)
+    ptr = lambda a: a.ctypes.data if a.size else None
+    _check_host(host_lib().mi_hot_join(ptr(collapse["hot"]), ptr(collapse["leaf_link"]), m, ptr(full["hot"]), ptr(full["leaf_link"]), n, ptr(out["nodes"]), ptr(out["leaf_link"]),
+                                       C.byref(start)))
+    out["exact_start"] = int(start.value)
+    out["place"] = np.concatenate([collapse["from"][collapse["order"]], full["order"]]).astype(np.uint32)
+    return out
+
+
+def hot_cast_is_literal(origin, direction) -> bool:
+    """mi_hot_cast_is_literal: whether K1w runs the literal box test for this cast (and starts it in the region of every node)."""
+    o, d = ((C.c_float * 3)(*[float(np.float32(x)) for x in v]) for v in (origin, direction))
+    return bool(host_lib().mi_hot_cast_is_literal(o, d))
+
+
+def hot_walk_count(device_nodes: np.ndarray, origin, direction, leaf_link: np.ndarray | None = None, t_max: float = float("inf"), start: int = 0):
+    """mi_hot_walk_count: hot_walk from node `start` for the segment [0, t_max] with the far slab product scaled as the kernels scale it -
+    (entries, number of box tests)."""
+    assert device_nodes.dtype == DEVICE_NODE and device_nodes.flags.c_contiguous
+    o, d = ((C.c_float * 3)(*[float(np.float32(x)) for x in v]) for v in (origin, direction))
+    link = None if leaf_link is None else np.ascontiguousarray(leaf_link, np.uint32)
+    cap = 4 * device_nodes.size + 4
+    visits = np.zeros(cap, np.uint32)
+    status, tests = C.c_int(0), C.c_uint32(0)
+    cnt = host_lib().mi_hot_walk_count(device_nodes.ctypes.data, device_nodes.size, None if link is None else link.ctypes.data, int(start), o, d, C.c_float(float(np.float32(t_max))),
+                                       visits.ctypes.data, cap, C.byref(tests), C.byref(status))
+    _check_host(status.value)
+    return visits[:min(cnt, cap)].copy(), int(tests.value)
 
 
 def sphere_crossings_host(centre, radius2, origin, direction, t_min=0.0, t_max=float("inf")) -> int:

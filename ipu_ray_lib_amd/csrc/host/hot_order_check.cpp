@@ -1,7 +1,9 @@
 // hot_order_check.cpp — a stand-alone check of csrc/hot_order.hpp and host/hot_order.cpp (its own main; built and run by
 // tests/test_hot_order.py with the address and undefined-behaviour sanitizers, never part of a library): random depth-first BVH2s
 // of compact nodes, their hot-first order, the private node array, and walks of both arrays for random rays, which must visit the
-// same nodes and primitives in the same order. Exit status 0 = every check held.
+// same nodes and primitives in the same order; and the collapsed tree (mi_hot_collapse), whose walks must test the same primitives in the same
+// order. Exit status 0 = every check held.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -59,6 +61,20 @@ int main() {
     std::vector<unsigned char> seen(n, 0);
     for (uint32_t k = 0; k < n; ++k) { if (order[k] >= n || seen[order[k]]) return fail("the order is not a bijection", prims, 0); seen[order[k]] = 1; }
     if (n && order[0] != 0) return fail("the root does not stand first", prims, 0);
+    // the collapsed tree (hot_collapse_keep / hot_collapse_nodes): survivors in preorder, then the same order and permutation over them
+    std::vector<unsigned char> pre2(32 * (size_t)n), thin(32 * (size_t)n), hot2(32 * (size_t)n), keep(n);
+    std::vector<uint32_t> from(n), order2(n), link2(n);
+    std::vector<double> share2(n);
+    uint32_t counts[2] = {0, 0};
+    if (mi_hot_collapse(compact.data(), n, -1.0, pre2.data(), keep.data(), from.data(), thin.data(), order2.data(), hot2.data(), link2.data(), share2.data(), counts) != MI_OK)
+      return fail("mi_hot_collapse refused a depth-first BVH2", prims, 0);
+    const uint32_t m = counts[0];
+    if (m > n || (n && (m == 0 || !keep[0] || from[0] != 0 || order2[0] != 0))) return fail("the collapsed tree lost its root", prims, 0);
+    if (n && memcmp(pre.data(), pre2.data(), pre.size()) != 0) return fail("mi_hot_collapse and mi_hot_nodes disagree on the preorder array", prims, 0);
+    std::vector<unsigned char> joined(32 * ((size_t)m + n));
+    std::vector<uint32_t> jlink((size_t)m + n);
+    uint32_t exact = 0;
+    if (mi_hot_join(hot2.data(), link2.data(), m, hot.data(), link.data(), n, joined.data(), jlink.data(), &exact) != MI_OK || exact != m) return fail("mi_hot_join failed", prims, 0);
     const uint32_t cap = 4 * n + 4;
     std::vector<uint32_t> a(cap), b(cap);
     for (uint32_t r = 0; r < 2000; ++r) {
@@ -73,6 +89,22 @@ int main() {
       if (ca != cb || ca > cap) return fail("the two walks differ in length", prims, r);
       for (uint32_t k = 0; k < ca; ++k)
         if (((b[k] & 0x80000000u) | order[b[k] & 0x7FFFFFFFu]) != a[k]) return fail("the two walks visit different nodes", prims, r);
+      // the collapsed walk: the same leaves in the same order, with the ray's far end open and given
+      const float far = (r % 3 == 0) ? uni(0.f, 60.f) : INFINITY;
+      uint32_t ta = 0, tb = 0;
+      const uint32_t wa = mi_hot_walk_count(pre.data(), n, nullptr, 0, o, d, far, a.data(), cap, &ta, &sa);
+      // (as the device walks it: the joined array, a cast on the literal box test from the region of every node)
+      const uint32_t wb = mi_hot_walk_count(joined.data(), m + n, jlink.data(), mi_hot_cast_is_literal(o, d) ? exact : 0u, o, d, far, b.data(), cap, &tb, &sb);
+      if (sa != MI_OK || sb != MI_OK || wa > cap || wb > cap) return fail("a counted walk left the array", prims, r);
+      uint32_t ka = 0, kb = 0;
+      for (;; ++ka, ++kb) {
+        while (ka < wa && !(a[ka] & 0x80000000u)) ++ka;
+        while (kb < wb && !(b[kb] & 0x80000000u)) ++kb;
+        if (ka >= wa || kb >= wb) break;
+        const uint32_t at = b[kb] & 0x7FFFFFFFu;
+        if ((at < m ? from[order2[at]] : order[at - m]) != (a[ka] & 0x7FFFFFFFu)) return fail("the collapsed walk tests another primitive", prims, r);
+      }
+      if ((ka < wa) != (kb < wb)) return fail("the collapsed walk tests more or fewer primitives", prims, r);
     }
   }
   // what is refused: a second child that is not behind the first child's subtree

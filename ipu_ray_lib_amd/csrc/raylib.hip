@@ -361,15 +361,22 @@ struct mi_scene {
   // arrays as uploaded. Everything that changes the shared arrays on the device - a refit, a rebuild, new contents - takes its
   // mutable reference to them from touchArrays(), which retires the copies: from then on the scene launches today's kernel on
   // the shared arrays (the copies are not regenerated on the device).
+  // Two of them: `hot` holds every node - the instrumented build walks it and counts the reference's visits -, `thin` the collapsed tree
+  // (hot_order.hpp: interior nodes whose box test decides nothing taken out of the walk), which the plain HOT builds walk, and behind it,
+  // in the same arrays, every node once more: the region a cast on the literal box test starts in (exactBase; thinNodes = the collapsed
+  // tree's own count, what the staged prefix and option auto go by).
   struct HotCopy { const GNode* nodes = nullptr; const GLeaf* leaves = nullptr; const GLeafRot* rot = nullptr; const float* leafNormals = nullptr; bool valid = false;
-                   std::vector<double> share; } hot;      // share[k - 1]: what the first k nodes take of the tree's expected box tests (hot_prefix_share)
-  DeviceScene hotView() const { DeviceScene v = view(); v.nodes = hot.nodes; v.leaves = hot.leaves; v.leavesRot = hot.rot; v.leafNormals = hot.leafNormals; return v; }
-  DeviceScene& touchArrays() { hot.valid = false; return ds; }
+                   uint32_t numNodes = 0, thinNodes = 0, exactBase = 0;
+                   std::vector<double> share; } hot, thin;      // share[k - 1]: what the first k nodes take of the tree's expected box tests (hot_prefix_share)
+  DeviceScene hotView(const HotCopy& c) const { DeviceScene v = view(); v.nodes = c.nodes; v.numNodes = c.numNodes; v.exactBase = c.exactBase; v.leaves = c.leaves; v.leavesRot = c.rot; v.leafNormals = c.leafNormals; return v; }
+  DeviceScene& touchArrays() { hot.valid = false; thin.valid = false; return ds; }
   // gives a retired copy's buffers back (hipFree waits for the work that may still read them); called where an update has been applied
   void freeRetiredHot() {
-    if (hot.valid) return;
-    for (const void* p : {(const void*)hot.nodes, (const void*)hot.leaves, (const void*)hot.rot, (const void*)hot.leafNormals}) release(p);
+    if (hot.valid || thin.valid) return;
+    for (const HotCopy* c : {&hot, &thin})
+      for (const void* p : {(const void*)c->nodes, (const void*)c->leaves, (const void*)c->rot, (const void*)c->leafNormals}) release(p);
     hot = HotCopy{};
+    thin = HotCopy{};
   }
   bool hotRoomSaid = false;
   // the dynamic LDS (bytes, a multiple of a node) a HOT build may take per workgroup without losing a resident workgroup per compute unit
@@ -661,22 +668,51 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
   ds.nodes = S.keep(upload(nodes)); ds.numNodes = N;
   ds.leaves = S.keep(upload(leaves)); ds.numLeaves = (uint32_t)leaves.size();
   // K1w's private copies (mi_scene::hot): the nodes in hot-first order with their successors renumbered, the records moved along
-  std::vector<uint32_t> hotOrder(N), hotLink(N);
+  // - once over every node (hot), once over the survivors of the collapse (thin). at[k] = the preorder index of the node at place k.
+  struct Private { mi_scene::HotCopy* copy; std::vector<uint32_t> at, link; std::vector<GNode> nodes; } priv[2] = {{&S.hot, {}, {}, {}}, {&S.thin, {}, {}, {}}};
   {
-    std::vector<GNode> hotNodes(N);
-    if (N) {
-      hot_first_order(reinterpret_cast<const HotNode*>(nodes.data()), N, hotOrder.data());
-      hot_permute_nodes(reinterpret_cast<const HotNode*>(nodes.data()), N, hotOrder.data(), reinterpret_cast<HotNode*>(hotNodes.data()), hotLink.data());
-      S.hot.share.resize(N);
-      hot_prefix_share(reinterpret_cast<const HotNode*>(nodes.data()), N, hotOrder.data(), S.hot.share.data());
+    const HotNode* pre = reinterpret_cast<const HotNode*>(nodes.data());
+    std::vector<uint8_t> keepNode(N);
+    const uint32_t M = hot_collapse_keep(pre, N, kHotCollapseTheta, keepNode.data(), nullptr);
+    std::vector<HotNode> thinPre(M);
+    std::vector<uint32_t> thinFrom(M);
+    hot_collapse_nodes(pre, N, keepNode.data(), thinPre.data(), thinFrom.data());
+    need(M == 0 || (thinFrom[0] == 0 && (M == 1 || (thinPre[0].hit == 32u) == !node_is_leaf(nodes[0]))), "the collapsed tree lost its root");      // (root_start: an interior root's first surviving descendant is node 1)
+    for (int c = 0; c < 2; ++c) {
+      const HotNode* src = c ? thinPre.data() : pre;
+      const uint32_t n = c ? M : N;
+      std::vector<uint32_t> order(n);
+      priv[c].nodes.resize(n);
+      priv[c].link.resize(n);
+      hot_first_order(src, n, order.data());
+      hot_permute_nodes(src, n, order.data(), reinterpret_cast<HotNode*>(priv[c].nodes.data()), priv[c].link.data());
+      priv[c].copy->share.resize(n);
+      if (c) hot_prefix_share_any(src, n, order.data(), S.thin.share.data()); else hot_prefix_share(src, n, order.data(), S.hot.share.data());
+      priv[c].at.resize(n);
+      for (uint32_t k = 0; k < n; ++k) priv[c].at[k] = c ? thinFrom[order[k]] : order[k];
+      priv[c].copy->numNodes = priv[c].copy->thinNodes = n;
     }
+    {
+      // the plain builds' arrays: the collapsed tree, then every node (hot_join_regions); the records below follow `at` and `link`
+      std::vector<GNode> joined(M + N);
+      std::vector<uint32_t> joinedLink(M + N);
+      hot_join_regions(reinterpret_cast<const HotNode*>(priv[1].nodes.data()), priv[1].link.data(), M, reinterpret_cast<const HotNode*>(priv[0].nodes.data()), priv[0].link.data(), N,
+                       reinterpret_cast<HotNode*>(joined.data()), joinedLink.data());
+      priv[1].nodes.swap(joined);
+      priv[1].link.swap(joinedLink);
+      priv[1].at.insert(priv[1].at.end(), priv[0].at.begin(), priv[0].at.end());
+      S.thin.numNodes = M + N;
+      S.thin.exactBase = M << 5;
+    }
+    for (Private& p : priv) p.copy->nodes = S.keep(upload(p.nodes));
     // (a leaf's record carries the node that follows it: a plain record in triBase - the walk reads it with primID's 16 bytes, nothing
     // on the device reads the triangle's index base -, a pre-rotated block in its first word, above the kind: that word loses the geomID
     // bits the shared blocks carry, which no walk reads - the hit's geomID and primID come from the plain record, whose type word stays)
-    std::vector<GLeaf> hotLeaves(N);
-    for (uint32_t k = 0; k < N; ++k) { hotLeaves[k] = leaves[hotOrder[k]]; if (isLeafNode[hotOrder[k]]) hotLeaves[k].triBase = hotLink[k]; }
-    S.hot.nodes = S.keep(upload(hotNodes));
-    S.hot.leaves = S.keep(upload(hotLeaves));
+    for (Private& p : priv) {
+      std::vector<GLeaf> hotLeaves(p.at.size());
+      for (uint32_t k = 0; k < p.at.size(); ++k) { hotLeaves[k] = leaves[p.at[k]]; if (isLeafNode[p.at[k]]) hotLeaves[k].triBase = p.link[k]; }
+      p.copy->leaves = S.keep(upload(hotLeaves));
+    }
   }
   {
     // the primitive-test part of every record once per shear axis (GLeafRot, trace_kernels.hpp): a triangle's vertices with their
@@ -694,20 +730,22 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
         }
       }
     ds.leavesRot = S.keep(upload(rot));
-    std::vector<GLeafRot> hotRot(rot.size());
-    for (uint32_t k = 0; k < N; ++k) {
-      hotRot[k] = rot[hotOrder[k]];
-      if (isLeafNode[hotOrder[k]]) for (uint32_t kz = 0; kz < 3; ++kz) hotRot[k].b[kz].type = hotLink[k] | leaf_kind(leaves[hotOrder[k]]);
+    for (Private& p : priv) {
+      std::vector<GLeafRot> hotRot(p.at.size());
+      for (uint32_t k = 0; k < p.at.size(); ++k) {
+        hotRot[k] = rot[p.at[k]];
+        if (isLeafNode[p.at[k]]) for (uint32_t kz = 0; kz < 3; ++kz) hotRot[k].b[kz].type = p.link[k] | leaf_kind(leaves[p.at[k]]);
+      }
+      p.copy->rot = S.keep(upload(hotRot));
     }
-    S.hot.rot = S.keep(upload(hotRot));
   }
   ds.matIDs = S.keep(upload(std::vector<uint32_t>(d.mat_ids, d.mat_ids + d.num_mat_ids)));
   ds.materials = S.keep(upload(std::vector<mi_material>(d.materials, d.materials + d.num_materials)));
   ds.numMaterials = d.num_materials;
   ds.hasNormals = d.num_normals ? 1u : 0u;
   ds.leafNormals = nullptr;
-  S.hot.leafNormals = nullptr;
-  S.hot.valid = true;
+  S.hot.leafNormals = S.thin.leafNormals = nullptr;
+  S.hot.valid = S.thin.valid = true;
   if (ds.hasNormals) {
     std::vector<float> ln(9 * leaves.size(), 0.f);
     for (size_t k = 0; k < leaves.size(); ++k) {
@@ -722,9 +760,11 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
       }
     }
     ds.leafNormals = S.keep(upload(ln));
-    std::vector<float> hotLn(ln.size());
-    for (uint32_t k = 0; k < N; ++k) memcpy(&hotLn[9 * (size_t)k], &ln[9 * (size_t)hotOrder[k]], 9 * sizeof(float));
-    S.hot.leafNormals = S.keep(upload(hotLn));
+    for (Private& p : priv) {
+      std::vector<float> hotLn(9 * p.at.size());
+      for (uint32_t k = 0; k < p.at.size(); ++k) memcpy(&hotLn[9 * (size_t)k], &ln[9 * (size_t)p.at[k]], 9 * sizeof(float));
+      p.copy->leafNormals = S.keep(upload(hotLn));
+    }
     ds.meshTris = S.keep(upload(std::vector<uint16_t>(d.mesh_tris, d.mesh_tris + 3 * (size_t)d.num_tris)));
     ds.meshNormals = S.keep(upload(std::vector<mi_vec3>(d.mesh_normals, d.mesh_normals + d.num_normals)));
     ds.geomFirstVertex = S.keep(upload(geomFirstVertex));
@@ -1295,10 +1335,12 @@ uint32_t setGeometry(mi_scene& S, const mi_scene_geometry& g, hipStream_t stream
   std::vector<const void*> old = {o.nodes, o.leaves, o.leavesRot, o.matIDs, o.materials, o.leafNormals, o.meshTris, o.meshNormals, o.geomFirstVertex,
                                   oR.d_prims, oR.d_order, oR.d_boxes, oR.d_cnodes[0], oR.d_cnodes[1], oR.d_levelStart, oR.d_verts, oR.d_spheres, oR.d_discs,
                                   S.rebuild.d_canon, S.live.d_cost,
-                                  S.hot.nodes, S.hot.leaves, S.hot.rot, S.hot.leafNormals};      // (the private copies were the old contents')
+                                  S.hot.nodes, S.hot.leaves, S.hot.rot, S.hot.leafNormals,
+                                  S.thin.nodes, S.thin.leaves, S.thin.rot, S.thin.leafNormals};      // (the private copies were the old contents')
   if (B.d_primBoxes != S.rebuild.d_primBoxes) for (void* p : rebuildScratchBuffers(S.rebuild)) old.push_back(p);
   for (const void* p : old) S.release(p);
   S.hot = mi_scene::HotCopy{};
+  S.thin = mi_scene::HotCopy{};
   S.touchArrays() = ds;
   S.refit = std::move(R);
   S.rebuild = B;
@@ -1454,21 +1496,23 @@ void launchWavefront(mi_scene& S, mi_trace_result* d_rays, uint32_t cnt, hipStre
     // Option "hot_nodes": the HOT builds (trace_wavefront.hpp) walk the scene's private, hot-first copies and stage their first nodes in
     // dynamic LDS - as many as asked for, as the copy has, and as fit without costing a resident workgroup. Plain renders only, while the
     // copies stand for the shared arrays (mi_scene::touchArrays); false = nothing launched: the caller goes on to today's kernel.
-    const bool hotOn = plain && S.opt.hotNodes != 0 && S.hot.valid && S.ds.numNodes > 0;
+    // The plain builds walk the collapsed copy (mi_scene::thin), the instrumented one the copy of every node: its counters are the reference's visits.
+    const bool hotOn = plain && S.opt.hotNodes != 0 && (STATS ? S.hot.valid : S.thin.valid) && S.ds.numNodes > 0;
     auto goHot = [&](auto kern, uint32_t threads) -> bool {
+      const mi_scene::HotCopy& copy = STATS ? S.hot : S.thin;
       const uint32_t room = S.hotRoom(reinterpret_cast<const void*>(kern), (int)threads);
-      const uint32_t count = std::min(std::min(S.opt.hotNodes < 0 ? ~0u : (uint32_t)S.opt.hotNodes, S.ds.numNodes), room / (uint32_t)sizeof(GNode));
+      const uint32_t count = std::min(std::min(S.opt.hotNodes < 0 ? ~0u : (uint32_t)S.opt.hotNodes, copy.thinNodes), room / (uint32_t)sizeof(GNode));
       if (!count) return false;
       if (S.opt.hotNodes < 0) {
         // auto: decided from the prefix the plain build of this scene's kind stages, whichever build is being launched (the instrumented one has room for more)
         const uint32_t plainRoom = S.ds.hasNormals ? S.hotRoom(reinterpret_cast<const void*>(MI_K1W_HOT(kHotThreads, true, false)), (int)kHotThreads)
                                                    : S.hotRoom(reinterpret_cast<const void*>(MI_K1W_HOT(kHotThreads, false, true)), (int)kHotThreads);
-        const uint32_t ref = std::min(S.ds.numNodes, plainRoom / (uint32_t)sizeof(GNode));
-        if (!ref || S.hot.share[ref - 1] < kHotAutoShare) return false;
+        const uint32_t ref = std::min(S.thin.thinNodes, plainRoom / (uint32_t)sizeof(GNode));
+        if (!ref || S.thin.share[ref - 1] < kHotAutoShare) return false;
       }
       const uint32_t wgs = grid(kern, threads, room);
       if (S.opt.sayGrid) fprintf(stderr, "mi_raylib: grid %u workgroups of %u threads, %u hot nodes of %u that fit\n", wgs, threads, count, room / (uint32_t)sizeof(GNode));
-      hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), (size_t)count * sizeof(GNode), stream, S.hotView(), d_rays, cnt, workCounter, count, S.opt.tune, tileW, exs);
+      hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), (size_t)count * sizeof(GNode), stream, S.hotView(copy), d_rays, cnt, workCounter, count, S.opt.tune, tileW, exs);
       return true;
     };
     if (S.opt.doubleFallback) {

@@ -82,6 +82,9 @@ struct DeviceScene {
   // it hits it, so the walk can start at node 1 (root_start below). rootInterior = 0 switches the shortcut off.
   float rootLoX, rootLoY, rootLoZ, rootHiX, rootHiY, rootHiZ;
   uint32_t rootInterior;
+  // K1w's HOT builds on the collapsed private copy (hot_order.hpp): the byte offset, in that copy's node array, of the root of the region that
+  // holds every node - where a cast on the literal box test (exactSlab) starts. 0 everywhere else.
+  uint32_t exactBase;
 };
 
 // First node of a closest-hit walk with tMin = 0 and tMax = +inf (every cast of the path-trace loop). The reference

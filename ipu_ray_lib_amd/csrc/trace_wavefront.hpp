@@ -714,7 +714,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
         }
         if (FAST) fast_box_setup(o, inv, oi, slabPad);
         hit.t = kInf; hit.leaf = 0xFFFFFFFFu;
-        { uint32_t seen; node = root_start(sc, o, seen) << 5; if (STATS) cs.nodes += seen; }
+        { uint32_t seen; node = (root_start(sc, o, seen) << 5) + ((HOT && exactSlab) ? sc.exactBase : 0u); if (STATS) cs.nodes += seen; }      // (HOT: a literal-box-test cast walks the region of every node, hot_order.hpp)
         if (!kPhInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
         // Slot-mode launches (NIF renders), option nif_first_test: the cast's FIRST box test runs here, in the turn that set the cast up,
         // instead of in a NODE turn. In the open scenes an environment light is for, most casts miss the root's box: they take a NODE
@@ -848,7 +848,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           }
           if (FAST) fast_box_setup(o, inv, oi, slabPad);
           hit.t = kInf; hit.leaf = 0xFFFFFFFFu;
-          { uint32_t seen; node = root_start(sc, o, seen) << 5; if (STATS) cs.nodes += seen; }
+          { uint32_t seen; node = (root_start(sc, o, seen) << 5) + ((HOT && exactSlab) ? sc.exactBase : 0u); if (STATS) cs.nodes += seen; }      // (HOT: a literal-box-test cast walks the region of every node, hot_order.hpp)
           if (!kPhInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
         }
         pathStore();
@@ -886,7 +886,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
         }
         if (FAST) fast_box_setup(o, inv, oi, slabPad);
         hit.t = kInf; hit.leaf = 0xFFFFFFFFu;
-        { uint32_t seen; node = root_start(sc, o, seen) << 5; if (STATS) cs.nodes += seen; }
+        { uint32_t seen; node = (root_start(sc, o, seen) << 5) + ((HOT && exactSlab) ? sc.exactBase : 0u); if (STATS) cs.nodes += seen; }      // (HOT: a literal-box-test cast walks the region of every node, hot_order.hpp)
         if (!kPhInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
         pathStore();
       }
