@@ -707,6 +707,8 @@ int mi_scene_set_ray_batch(mi_scene* scene, size_t rays_per_batch);
  *   "rebuild_timing" 0 | 1          bracket the passes of mi_scene_rebuild with HIP events (mi_get_rebuild_timing)
  *   "leaf_rot"      0 | 1           scenes without vertex normals: the default kernel reads primitive records pre-rotated for the cast's shear axis (default 1)
  *   "lean_hit"      0 | 1           scenes without vertex normals run the build of the default kernel that carries no barycentrics (default 1)
+ *   "leaf_frame"    0 | 1           scenes without vertex normals: the default kernel loads the tangent frame of a diffuse bounce off a triangle or disc from a
+ *                                   per-leaf record instead of computing it per hit (default 1; every byte the same either way)
  *   "hot_nodes"     auto | 0..65535 plain renders of the default kernel walk a private, hot-first copy of the BVH arrays and run the box-test runs whose lanes
  *                                   all stand in its first nodes from LDS: that many nodes, clamped to the tree and to what fits beside the kernel's other LDS
  *                                   (316 on an MI355X). 0 = off: the shared arrays and the launch of before. auto (the default): on, with as many as fit, where

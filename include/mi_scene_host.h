@@ -198,6 +198,15 @@ int mi_hot_cast_is_literal(const float origin[3], const float direction[3]);
 uint32_t mi_hot_walk_count(const void* nodes, uint32_t num_nodes, const uint32_t* leaf_link, uint32_t start, const float origin[3], const float direction[3], float t_max,
                            uint32_t* visits, uint32_t capacity, uint32_t* box_tests, int* status);
 
+/* The tangent frame a diffuse bounce builds about `normal` (ipu_ray_lib_amd/csrc/ray_math.h diffuse_frame), and the per-leaf records a
+ * scene WITHOUT vertex normals keeps of it (scene option "leaf_frame", mi_raylib.h; ipu_ray_lib_amd/csrc/leaf_frame.hpp, from the function
+ * the device library's upload runs): frames receives, for each of `count` places, the eight floats {xb, 0, yb, 0} of the node at[k]
+ * (at = NULL: node k; count <= num_nodes then) - the frame about a triangle leaf's face normal or a disc leaf's plane normal, zeros
+ * for sphere leaves and interior nodes. normals (may be NULL) receives three floats per NODE: the normal the frame was built about
+ * (zeros where there is none). `at` = the "place" list of a private copy gives that copy's records. */
+void mi_diffuse_frame(const float normal[3], float xb[3], float yb[3]);
+int mi_leaf_frames(const mi_scene_desc* desc, const uint32_t* at, uint32_t count, float* frames, float* normals);
+
 /* initPerspectiveRayStream(rayStream, image, data, nullptr) + zeroRgb: window_w*window_h rays in
  * row-major window order, origin 0, un-jittered pinhole directions, u=row, v=col. */
 int mi_init_ray_stream(const mi_scene_desc* desc, mi_trace_result* rays, size_t capacity);

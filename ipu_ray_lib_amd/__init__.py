@@ -215,6 +215,9 @@ def host_lib() -> C.CDLL:
         lib.mi_hot_walk_count.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_void_p, C.c_uint32,
                                           C.POINTER(C.c_uint32), C.POINTER(C.c_int)]
         lib.mi_hot_walk_count.restype = C.c_uint32
+        lib.mi_diffuse_frame.argtypes = [C.POINTER(C.c_float)] * 3
+        lib.mi_diffuse_frame.restype = None
+        lib.mi_leaf_frames.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
         lib.mi_bvh_cost_compact.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_compact_block.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)]
         lib.mi_bvh_cost_estimate.argtypes = [C.POINTER(C.c_double)]
@@ -658,6 +661,27 @@ def hot_join(collapse: dict, full: dict) -> dict:
     out["exact_start"] = int(start.value)
     out["place"] = np.concatenate([collapse["from"][collapse["order"]], full["order"]]).astype(np.uint32)
     return out
+
+
+def diffuse_frame(normal) -> np.ndarray:
+    """mi_diffuse_frame: the tangent frame (xb, yb) a diffuse bounce builds about `normal`, as a (2, 3) float32 array."""
+    n = (C.c_float * 3)(*[float(np.float32(x)) for x in normal])
+    xb, yb = (C.c_float * 3)(), (C.c_float * 3)()
+    host_lib().mi_diffuse_frame(n, xb, yb)
+    return np.array([list(xb), list(yb)], np.float32)
+
+
+def leaf_frames(desc: SceneDesc, place: np.ndarray | None = None):
+    """mi_leaf_frames: the per-leaf frame records of a scene without vertex normals (option leaf_frame) - (frames, normals): frames[k] =
+    the eight floats {xb, 0, yb, 0} of the node at place[k] (None: the shared, preorder array), normals[i] = the normal node i's frame
+    is built about (zeros for sphere leaves and interior nodes). place = hot_nodes(...)["order"] or hot_join(...)["place"]: the records
+    of a private copy."""
+    n = int(desc.num_nodes)
+    at = None if place is None else np.ascontiguousarray(place, np.uint32)
+    count = n if at is None else at.size
+    frames, normals = np.zeros((count, 8), np.float32), np.zeros((n, 3), np.float32)
+    _check_host(host_lib().mi_leaf_frames(C.byref(desc), None if at is None or not count else at.ctypes.data, count, frames.ctypes.data if count else None, normals.ctypes.data if n else None))
+    return frames, normals
 
 
 def hot_cast_is_literal(origin, direction) -> bool:

@@ -407,9 +407,12 @@ MI_HD void sample_disc_concentric(float u1, float u2, const float* sinTbl, float
   if (ux == 0.f && uy == 0.f) { ox = ux; oy = uy; return; }
   const float piby4 = (float)(3.14159265358979323846264338327950288 / 4.0);
   const float piby2 = (float)(3.14159265358979323846264338327950288 / 2.0);
-  float r, th;
-  if (fabsf(ux) > fabsf(uy)) { r = ux; th = piby4 * (uy / ux); }
-  else { r = uy; th = piby2 - piby4 * (ux / uy); }
+  // (one division behind selects: as `if (wide) uy / ux else ux / uy` the device compiles two exec regions with a division each, and
+  // the outcome is random per lane, so a wave runs both - the same operations on the same operands either way)
+  const bool wide = fabsf(ux) > fabsf(uy);
+  const float r = wide ? ux : uy;
+  const float q = piby4 * ((wide ? uy : ux) / (wide ? ux : uy));
+  const float th = wide ? q : piby2 - q;
   float s, c;
   sincos_deg_table(th, sinTbl, s, c);
   ox = r * c; oy = r * s;
@@ -420,14 +423,28 @@ MI_HD f3 cosine_sample_hemisphere(float u1, float u2, const float* sinTbl) {
   const float z = sqrtf(fmaxf(0.f, 1.f - x * x - y * y));
   return mk(x, y, z);
 }
-MI_HD f3 sample_diffuse(f3 n, float u1, float u2, const float* sinTbl) {
-  f3 xb;
+// The tangent frame of a diffuse bounce (the reference's orthonormal system about n): |n.x| > |n.y| ? xb = (-n.z, 0, n.x) / sqrt(n.x^2 + n.z^2)
+// : xb = (0, n.z, -n.y) / sqrt(n.y^2 + n.z^2), yb = n x xb. ONE sqrt and ONE division behind selects - as two branches the device runs
+// both, each with its own, in every wave whose lanes hold different normals. The operations and their operands are the branch form's:
+// (-n.z) * il is not -(n.z * il) for a NaN, the zero component is a literal. A function of the normal alone: K1w reads it per leaf
+// where the normal is the leaf's (leaf_frame.hpp).
+MI_HD void diffuse_frame(f3 n, f3& xb, f3& yb) {
   const f3 a = abs3(n), sq = n * n;
-  if (a.x > a.y) { const float il = 1.f / sqrtf(sq.x + sq.z); xb = mk(-n.z * il, 0.f, n.x * il); }
-  else { const float il = 1.f / sqrtf(sq.y + sq.z); xb = mk(0.f, n.z * il, -n.y * il); }
-  const f3 yb = cross(n, xb);
+  const bool wide = a.x > a.y;
+  const float il = 1.f / sqrtf((wide ? sq.x : sq.y) + sq.z);
+  const float m = (wide ? -n.z : n.z) * il;
+  const float z = (wide ? n.x : -n.y) * il;
+  xb = mk(wide ? m : 0.f, wide ? 0.f : m, z);
+  yb = cross(n, xb);
+}
+MI_HD f3 diffuse_in_frame(f3 n, f3 xb, f3 yb, float u1, float u2, const float* sinTbl) {
   const f3 wi = cosine_sample_hemisphere(u1, u2, sinTbl);
   return mk(dot(mk(xb.x, yb.x, n.x), wi), dot(mk(xb.y, yb.y, n.y), wi), dot(mk(xb.z, yb.z, n.z), wi));
+}
+MI_HD f3 sample_diffuse(f3 n, float u1, float u2, const float* sinTbl) {
+  f3 xb, yb;
+  diffuse_frame(n, xb, yb);
+  return diffuse_in_frame(n, xb, yb, u1, u2, sinTbl);
 }
 MI_HD f3 reflect_dir(f3 d, f3 n) {
   const float cosTheta = dot(d, n);

@@ -143,6 +143,7 @@ struct SceneOptions {
                                    // 0 = w6, 1 = t6, 2 = t4 (nif_mlp_kernel's workgroup shapes); 4 = r8, 5 = r8s (K3r, nif_regs_kernel.hpp: measured slower, selectable in the variants build)
   bool leafRot = true;             // "leaf_rot": scenes without vertex normals read primitive records pre-rotated for the cast's shear axis (GLeafRot: 18 selects per triangle test become 6; -2.4 %, profiles/r05_k1w_leaf_ab.txt)
   bool leanHit = true;             // "lean_hit": scenes without vertex normals run the default kernel's build that carries no barycentrics (BARY = false)
+  bool leafFrame = true;           // "leaf_frame": scenes without vertex normals: a diffuse bounce off a triangle or disc loads its tangent frame from the leaf's record (GLeafFrame, leaf_frame.hpp); 0 = computed per hit
   bool coords = true;              // "coords": (pixel, segment) atoms read the pixel coordinates from a compact copy of the stream's (u, v)
   int nifOverlap = -1;             // "nif_overlap": NIF renders trace sample batch b + 1 beside the MLP of batch b (two slot sets, second stream): 1 | 0 | auto
                                    // (-1, the default: only beside nif_mlp_kernel, whose workgroups come and go - K3a / K3b hold every register of their
@@ -271,6 +272,7 @@ struct SceneOptions {
     if (key == "lean_hit") return flag01(v, leanHit);
     if (key == "auto_rebuild") { if (!autoRebuildValue(v, autoRebuild)) { why = "auto_rebuild takes 0 (off) or a decimal ratio above 1"; return false; } return true; }
     if (key == "leaf_rot") return flag01(v, leafRot);
+    if (key == "leaf_frame") return flag01(v, leafFrame);
     if (key == "hot_nodes") { if (!strcmp(v, "auto")) { hotNodes = kHotNodesAuto; return true; } if (!number(v, 0, 65535, q)) return false; hotNodes = (int)q; return true; }
     if (key == "double_fallback") {
       bool b = doubleFallback;
@@ -316,7 +318,7 @@ struct SceneOptions {
                                          {"MI_RAYLIB_POOL_TUNE", "pool_tune"}, {"MI_RAYLIB_POOL_WAVES", "pool_waves"}, {"MI_RAYLIB_CUS", "cus"},
                                          {"MI_RAYLIB_NIF_OVERLAP", "nif_overlap"}, {"MI_RAYLIB_COORDS", "coords"},
                                          {"MI_RAYLIB_NIF_TRACE_WGS", "nif_trace_wgs"}, {"MI_RAYLIB_NIF_SPLIT", "nif_split"}, {"MI_RAYLIB_NIF_GENERATIONS", "nif_generations"},
-                                         {"MI_RAYLIB_HOT_NODES", "hot_nodes"}};
+                                         {"MI_RAYLIB_HOT_NODES", "hot_nodes"}, {"MI_RAYLIB_LEAF_FRAME", "leaf_frame"}};
     // (an unparsable environment value is ignored: the option keeps its default. The two options that select ARITHMETIC,
     // double_fallback and fast, are deliberately not in this list: a process that says "bit-exact" must not change tier
     // because of a variable somebody exported)
@@ -356,7 +358,8 @@ struct mi_scene {
   // (auto: beside nif_mlp_kernel, and whenever the trace launches are given compute units of their own - option nif_split)
   bool nifOverlapOn() const { return opt.nifOverlap < 0 ? (opt.nifSplit > 0 || !((opt.nifShape >= 6 && opt.nifShape <= 8) && nif_asm_covers(nif.regs))) : opt.nifOverlap != 0; }
   // the scene as one launch sees it: option "root_start" decides whether the walk may start below the root
-  DeviceScene view() const { DeviceScene v = ds; if (!opt.rootStart) v.rootInterior = 0; return v; }
+  // ... and option "leaf_frame" whether a scene without vertex normals shows its per-leaf frame records (null: every frame is computed)
+  DeviceScene view() const { DeviceScene v = ds; if (!opt.rootStart) v.rootInterior = 0; if (!opt.leafFrame && !v.hasNormals) v.leafNormalsOrFrames = nullptr; return v; }
   // K1w's private copies of the walk's arrays in hot-first order (option "hot_nodes"; hot_order.hpp), made at create from the
   // arrays as uploaded. Everything that changes the shared arrays on the device - a refit, a rebuild, new contents - takes its
   // mutable reference to them from touchArrays(), which retires the copies: from then on the scene launches today's kernel on
@@ -368,7 +371,7 @@ struct mi_scene {
   struct HotCopy { const GNode* nodes = nullptr; const GLeaf* leaves = nullptr; const GLeafRot* rot = nullptr; const float* leafNormals = nullptr; bool valid = false;
                    uint32_t numNodes = 0, thinNodes = 0, exactBase = 0;
                    std::vector<double> share; } hot, thin;      // share[k - 1]: what the first k nodes take of the tree's expected box tests (hot_prefix_share)
-  DeviceScene hotView(const HotCopy& c) const { DeviceScene v = view(); v.nodes = c.nodes; v.numNodes = c.numNodes; v.exactBase = c.exactBase; v.leaves = c.leaves; v.leavesRot = c.rot; v.leafNormals = c.leafNormals; return v; }
+  DeviceScene hotView(const HotCopy& c) const { DeviceScene v = view(); v.nodes = c.nodes; v.numNodes = c.numNodes; v.exactBase = c.exactBase; v.leaves = c.leaves; v.leavesRot = c.rot; if (v.hasNormals || opt.leafFrame) v.leafNormalsOrFrames = c.leafNormals; return v; }
   DeviceScene& touchArrays() { hot.valid = false; thin.valid = false; return ds; }
   // gives a retired copy's buffers back (hipFree waits for the work that may still read them); called where an update has been applied
   void freeRetiredHot() {
@@ -743,7 +746,7 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
   ds.materials = S.keep(upload(std::vector<mi_material>(d.materials, d.materials + d.num_materials)));
   ds.numMaterials = d.num_materials;
   ds.hasNormals = d.num_normals ? 1u : 0u;
-  ds.leafNormals = nullptr;
+  ds.leafNormalsOrFrames = nullptr;
   S.hot.leafNormals = S.thin.leafNormals = nullptr;
   S.hot.valid = S.thin.valid = true;
   if (ds.hasNormals) {
@@ -759,7 +762,7 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
         ln[9 * k + 3 * c] = nn.x; ln[9 * k + 3 * c + 1] = nn.y; ln[9 * k + 3 * c + 2] = nn.z;
       }
     }
-    ds.leafNormals = S.keep(upload(ln));
+    ds.leafNormalsOrFrames = S.keep(upload(ln));
     for (Private& p : priv) {
       std::vector<float> hotLn(9 * p.at.size());
       for (uint32_t k = 0; k < p.at.size(); ++k) memcpy(&hotLn[9 * (size_t)k], &ln[9 * (size_t)p.at[k]], 9 * sizeof(float));
@@ -768,6 +771,24 @@ void buildDeviceScene(mi_scene& S, const mi_scene_desc& d) {
     ds.meshTris = S.keep(upload(std::vector<uint16_t>(d.mesh_tris, d.mesh_tris + 3 * (size_t)d.num_tris)));
     ds.meshNormals = S.keep(upload(std::vector<mi_vec3>(d.mesh_normals, d.mesh_normals + d.num_normals)));
     ds.geomFirstVertex = S.keep(upload(geomFirstVertex));
+  } else if (N) {
+    // no vertex normals: the pointer carries the per-leaf tangent frames instead (leaf_frame.hpp) - diffuse_frame of the normal SHADE reads
+    // for a triangle (GLeaf::n) or disc leaf, zeros elsewhere -, in the shared order and in the private copies' (both regions of `thin`)
+    std::vector<uint8_t> framed(N);
+    std::vector<float> normal(3 * (size_t)N, 0.f);
+    for (uint32_t i = 0; i < N; ++i) {
+      const GLeaf& L = leaves[i];
+      framed[i] = isLeafNode[i] && leaf_kind(L) != LEAF_SPHERE;
+      if (framed[i]) memcpy(&normal[3 * (size_t)i], leaf_kind(L) == LEAF_TRI ? L.n : L.f, 3 * sizeof(float));
+    }
+    std::vector<GLeafFrame> fr(N);
+    fill_leaf_frames(framed.data(), normal.data(), nullptr, N, fr.data());
+    ds.leafNormalsOrFrames = reinterpret_cast<const float*>(S.keep(upload(fr)));
+    for (Private& p : priv) {
+      std::vector<GLeafFrame> hotFr(p.at.size());
+      fill_leaf_frames(framed.data(), normal.data(), p.at.data(), (uint32_t)p.at.size(), hotFr.data());
+      p.copy->leafNormals = reinterpret_cast<const float*>(S.keep(upload(hotFr)));
+    }
   }
   ds.rootInterior = 0;
   if (N > 1) {      // (N > 1: the root is an interior node - checked above: a leaf root spans one node; option "root_start" = 0 clears the flag per launch)
@@ -936,6 +957,9 @@ void updateArgs(const char* fn, const mi_scene* S, const mi_geometry_update* u) 
 // then - behind everything already enqueued on the scene - pass 4 and the copies into the current geometry. Returns when it is
 // all in place; on a refused box nothing of the scene has changed.
 uint32_t rebuildScene(mi_scene& S, hipStream_t stream);
+// DeviceScene::leafNormalsOrFrames as the kernels that rewrite leaves[] take it: one of the two is null
+float* leafNormalsOf(const DeviceScene& ds) { return ds.hasNormals ? const_cast<float*>(ds.leafNormalsOrFrames) : nullptr; }
+GLeafFrame* leafFramesOf(const DeviceScene& ds) { return ds.hasNormals ? nullptr : reinterpret_cast<GLeafFrame*>(const_cast<float*>(ds.leafNormalsOrFrames)); }
 void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
   refitTables(S);
   mi_scene::Refit& R = S.refit;
@@ -993,7 +1017,7 @@ void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
   if (N) {
     if (timing) HIP_CHECK(hipEventRecord(R.ev[3], stream));
     hipLaunchKernelGGL(refit_write_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, N, R.d_prims, cn, g, const_cast<GNode*>(ds.nodes),
-                       const_cast<GLeaf*>(ds.leaves), const_cast<GLeafRot*>(ds.leavesRot), const_cast<float*>(ds.leafNormals));
+                       const_cast<GLeaf*>(ds.leaves), const_cast<GLeafRot*>(ds.leavesRot), leafNormalsOf(ds), leafFramesOf(ds));
     HIP_CHECK(hipGetLastError());
   }
   if (u.mesh_verts && R.numVerts) HIP_CHECK(hipMemcpyAsync(R.d_verts, u.mesh_verts, (size_t)R.numVerts * sizeof(mi_vec3), hipMemcpyDeviceToDevice, stream));
@@ -1186,7 +1210,7 @@ uint32_t rebuildPasses(mi_scene& S, mi_scene::Refit& R, mi_scene::Rebuild& B, De
   // from here on the scene changes: after everything already enqueued on it, on any stream (records built aside are nobody's yet)
   if (inPlace) for (LaunchSlot& l : S.slots) if (l.stream != stream) HIP_CHECK(hipStreamWaitEvent(stream, l.lastWork, 0));
   hipLaunchKernelGGL(rebuild_scatter_kernel, blocks(N), dim3(256), 0, stream, t, B.d_canon, g, R.d_cnodes[scratch], const_cast<GNode*>(ds.nodes),
-                     const_cast<GLeaf*>(ds.leaves), const_cast<GLeafRot*>(ds.leavesRot), const_cast<float*>(ds.leafNormals), R.d_prims);
+                     const_cast<GLeaf*>(ds.leaves), const_cast<GLeafRot*>(ds.leavesRot), leafNormalsOf(ds), leafFramesOf(ds), R.d_prims);
   HIP_CHECK(hipGetLastError());
   // both compact arrays carry the topology (a refit keeps the links and geomIDs of the array it writes)
   HIP_CHECK(hipMemcpyAsync(R.d_cnodes[1 - scratch], R.d_cnodes[scratch], (size_t)N * sizeof(mi_bvh_node), hipMemcpyDeviceToDevice, stream));
@@ -1286,12 +1310,12 @@ uint32_t setGeometry(mi_scene& S, const mi_scene_geometry& g, hipStream_t stream
     for (int k = 0; k < 3; ++k) R.ms[k] = S.refit.ms[k];
     R.ready = true;
     // the records and the refit's tables, one entry per node
-    GNode* nodes; GLeaf* leaves; GLeafRot* rot; float* leafNormals;
-    alloc(nodes, N); alloc(leaves, N); alloc(rot, N); alloc(leafNormals, g.num_normals ? 9 * (size_t)N : 0);
+    GNode* nodes; GLeaf* leaves; GLeafRot* rot; float* leafNormals;      // (the last: nine floats of vertex normals per node, or a GLeafFrame - eight - where there are none)
+    alloc(nodes, N); alloc(leaves, N); alloc(rot, N); alloc(leafNormals, (g.num_normals ? 9 : sizeof(GLeafFrame) / sizeof(float)) * (size_t)N);
     alloc(R.d_prims, N); alloc(R.d_order, N); alloc(R.d_boxes, N); alloc(R.d_cnodes[0], N); alloc(R.d_cnodes[1], N);
     ds.nodes = nodes; ds.numNodes = N; ds.leaves = leaves; ds.numLeaves = N; ds.leavesRot = rot;
     ds.matIDs = matIDs; ds.materials = materials; ds.numMaterials = g.num_materials;
-    ds.hasNormals = g.num_normals ? 1u : 0u; ds.leafNormals = leafNormals;
+    ds.hasNormals = g.num_normals ? 1u : 0u; ds.leafNormalsOrFrames = leafNormals;
     ds.meshTris = tris; ds.meshNormals = normals; ds.geomFirstVertex = firstVertex;
     ds.rootInterior = 0;
     ds.rootLoX = ds.rootHiX = ds.rootLoY = ds.rootHiY = ds.rootLoZ = ds.rootHiZ = 0.f;
@@ -1332,7 +1356,7 @@ uint32_t setGeometry(mi_scene& S, const mi_scene_geometry& g, hipStream_t stream
   // the swap: the old set's buffers, then the scene's pointers
   const DeviceScene& o = S.ds;
   const mi_scene::Refit& oR = S.refit;
-  std::vector<const void*> old = {o.nodes, o.leaves, o.leavesRot, o.matIDs, o.materials, o.leafNormals, o.meshTris, o.meshNormals, o.geomFirstVertex,
+  std::vector<const void*> old = {o.nodes, o.leaves, o.leavesRot, o.matIDs, o.materials, o.leafNormalsOrFrames, o.meshTris, o.meshNormals, o.geomFirstVertex,
                                   oR.d_prims, oR.d_order, oR.d_boxes, oR.d_cnodes[0], oR.d_cnodes[1], oR.d_levelStart, oR.d_verts, oR.d_spheres, oR.d_discs,
                                   S.rebuild.d_canon, S.live.d_cost,
                                   S.hot.nodes, S.hot.leaves, S.hot.rot, S.hot.leafNormals,

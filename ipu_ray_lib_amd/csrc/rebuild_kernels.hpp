@@ -225,7 +225,7 @@ __global__ void __launch_bounds__(256) rebuild_heights_kernel(uint32_t N, const 
 // pass 10: node n's records at its preorder index, as buildDeviceScene (raylib.hip) derives them at create from the compact nodes
 // and the geometry; interior nodes leave zero records behind, as at create. prims[i]: what a later refit computes node i's box from.
 __global__ void __launch_bounds__(256) rebuild_scatter_kernel(RebuildTree t, const RebuildPrim* canon, RefitGeom g, mi_bvh_node* cnodes,
-                                                              GNode* nodes, GLeaf* leaves, GLeafRot* rot, float* leafNormals, RefitPrim* prims) {
+                                                              GNode* nodes, GLeaf* leaves, GLeafRot* rot, float* leafNormals, GLeafFrame* leafFrames, RefitPrim* prims) {
   const uint32_t n = blockIdx.x * blockDim.x + threadIdx.x;
   const uint32_t P = t.numPrims, I = P - 1;
   if (n >= 2 * P - 1) return;
@@ -243,6 +243,7 @@ __global__ void __launch_bounds__(256) rebuild_scatter_kernel(RebuildTree t, con
   __builtin_memset(&L, 0, sizeof L);
   __builtin_memset(&R, 0, sizeof R);
   float vn[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  GLeafFrame F = leaf_frame_zero();      // (scenes without vertex normals: the tangent frame about a triangle's or disc's normal, leaf_frame.hpp)
   RefitPrim rp;
   if (n < I) {
     const uint2 ch = t.child[n];
@@ -267,6 +268,7 @@ __global__ void __launch_bounds__(256) rebuild_scatter_kernel(RebuildTree t, con
         const uint32_t v[3] = {p.a, p.b, p.c};
         for (int k = 0; k < 3; ++k) { const mi_vec3 q = g.normals[v[k]]; vn[3 * k] = q.x; vn[3 * k + 1] = q.y; vn[3 * k + 2] = q.z; }
       }
+      if (leafFrames) F = leaf_frame_of(fn);
     } else if (p.kind == REFIT_SPHERE) {
       const mi_sphere s = g.spheres[p.a];
       L.f[0] = s.x; L.f[1] = s.y; L.f[2] = s.z; L.f[3] = s.radius; L.f[4] = s.radius * s.radius;   // Primitives.hpp:44
@@ -275,6 +277,7 @@ __global__ void __launch_bounds__(256) rebuild_scatter_kernel(RebuildTree t, con
       const mi_disc d = g.discs[p.a];
       L.f[0] = d.nx; L.f[1] = d.ny; L.f[2] = d.nz; L.f[3] = d.cx; L.f[4] = d.cy; L.f[5] = d.cz; L.f[6] = d.r * d.r;
       L.type = LEAF_DISC | (p.geomID << 16);
+      if (leafFrames) F = leaf_frame_of(mk(L.f[0], L.f[1], L.f[2]));
     }
     // GLeafRot: block kz = the record's floats, a triangle's vertex components rotated so that component kz comes last
     for (uint32_t kz = 0; kz < 3; ++kz) {
@@ -293,6 +296,7 @@ __global__ void __launch_bounds__(256) rebuild_scatter_kernel(RebuildTree t, con
   leaves[i] = L;
   rot[i] = R;
   if (leafNormals) for (int k = 0; k < 9; ++k) leafNormals[9 * (size_t)i + k] = vn[k];
+  if (leafFrames) leafFrames[i] = F;
 }
 
 }  // namespace mi

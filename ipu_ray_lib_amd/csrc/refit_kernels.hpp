@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(kRefitTopThreads) refit_top_kernel(const uint3
 // pass 4: node i's device records from its new compact node and its primitive, as buildDeviceScene (raylib.hip) derives them
 // at create. Links, types, primIDs, triBase and material indices do not change.
 __global__ void __launch_bounds__(256) refit_write_kernel(uint32_t n, const RefitPrim* prims, const mi_bvh_node* cnodes, RefitGeom g,
-                                                          GNode* nodes, GLeaf* leaves, GLeafRot* rot, float* leafNormals) {
+                                                          GNode* nodes, GLeaf* leaves, GLeafRot* rot, float* leafNormals, GLeafFrame* leafFrames) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const mi_bvh_node c = cnodes[i];
@@ -139,6 +139,8 @@ __global__ void __launch_bounds__(256) refit_write_kernel(uint32_t n, const Refi
     L.f[0] = d.nx; L.f[1] = d.ny; L.f[2] = d.nz; L.f[3] = d.cx; L.f[4] = d.cy; L.f[5] = d.cz; L.f[6] = d.r * d.r;
   }
   leaves[i] = L;
+  // (scenes without vertex normals: the tangent frame about the normal just stored, leaf_frame.hpp; a sphere's stays zero)
+  if (leafFrames && p.kind != REFIT_SPHERE) leafFrames[i] = leaf_frame_of(p.kind == REFIT_TRI ? mk(L.n[0], L.n[1], L.n[2]) : mk(L.f[0], L.f[1], L.f[2]));
   // GLeafRot: block kz = the record's floats, a triangle's vertex components rotated so that component kz comes last
   for (uint32_t kz = 0; kz < 3; ++kz) {
     GLeafBlock B;

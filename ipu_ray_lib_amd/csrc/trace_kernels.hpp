@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ray_math.h"
+#include "leaf_frame.hpp"
 #include "../../include/mi_raylib.h"
 
 namespace mi {
@@ -49,7 +50,9 @@ struct __attribute__((aligned(16))) GLeaf {       // 64 B pre-resolved primitive
   uint32_t triBase;  // tri: index of the triangle's first u16 in meshTris (for vertex normals)
   float n[3];        // tri: the face normal normalise(cross(p1-p0, p2-p0)) (Mesh.hpp:112-114), evaluated once at
                      // upload with the same binary32 operations the reference performs per hit (no contraction,
-                     // correctly rounded sqrt and divide on both sides), so SHADE just reads it
+                     // correctly rounded sqrt and divide on both sides), so SHADE just reads it. The tangent frame a diffuse
+                     // bounce builds about it is a constant of the leaf in the same way: GLeafFrame (leaf_frame.hpp), a record
+                     // of its own per node, written wherever this is
   uint32_t matIndex; // matIDs[geomID], resolved at upload (one dependent load less when a hit is shaded)
 };
 static_assert(sizeof(GLeaf) == 64, "GLeaf must stay 64 bytes");
@@ -73,7 +76,11 @@ struct DeviceScene {
   const mi_material* materials; uint32_t numMaterials;
   // vertex normals (only when the scene was loaded with normals)
   const uint16_t* meshTris; const mi_vec3* meshNormals; const uint32_t* geomFirstVertex; uint32_t hasNormals;
-  const float* leafNormals;  // [numLeaves][9]: a triangle leaf's three vertex normals, gathered at upload (zeros for other leaves)
+  // One pointer, two uses (the default instantiations are at their scalar-register limit; a scene is one kind or the other):
+  //   hasNormals != 0: [numLeaves][9], a triangle leaf's three vertex normals, gathered at upload (zeros for other leaves);
+  //   hasNormals == 0: [numLeaves] GLeafFrame records (leaf_frame.hpp: [numLeaves][8] floats, 16-byte aligned), the tangent frame of a
+  //                    diffuse bounce off a triangle or disc leaf; null = compute it per hit (scene option "leaf_frame" 0).
+  const float* leafNormalsOrFrames;
   float imageWidth, imageHeight, tanTheta, antiAliasScale;
   uint32_t maxPathLength, rouletteStartDepth, samplesPerPixel;
   uint64_t rngSeed;
@@ -455,7 +462,7 @@ __device__ __forceinline__ f3 hit_normal(const DeviceScene& sc, const Hit& h, f3
     if (!sc.hasNormals) return mk(L.n[0], L.n[1], L.n[2]);
     // normals[firstVertex + tris[triBase + k]], k = 0..2 (Mesh.hpp:115-120), gathered per leaf at upload: one load
     // that depends on the leaf's index alone instead of three hops (first vertex, vertex indices, normals)
-    const float* q = sc.leafNormals + 9 * (size_t)h.leaf;
+    const float* q = sc.leafNormalsOrFrames + 9 * (size_t)h.leaf;
     return normalized((mk(q[0], q[1], q[2]) * h.b0) + (mk(q[3], q[4], q[5]) * h.b1) + (mk(q[6], q[7], q[8]) * h.b2));
   }
   if (leaf_kind(L) == LEAF_SPHERE) return normalized(hp - mk(L.f[0], L.f[1], L.f[2]));

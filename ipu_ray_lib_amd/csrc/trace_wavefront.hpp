@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char dynLds[];
   load_sin_table(sinTbl);
-  // HOT (scene option "hot_nodes"): sc.nodes / leaves / leavesRot / leafNormals are K1w's private, hot-first copies (hot_order.hpp)
+  // HOT (scene option "hot_nodes"): sc.nodes / leaves / leavesRot / leafNormalsOrFrames are K1w's private, hot-first copies (hot_order.hpp)
   // and the walk is layout-free: a lane that stops at a primitive stands AT its node, and takes the node that follows from the
   // record's load. Every workgroup stages the first ldsNodeCount nodes of the copy; a run of box tests whose lanes all stand
   // inside that prefix runs from LDS (the choice is wave-uniform, made once per run: no step ever pays for both paths).
@@ -601,6 +601,24 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
         bool terminated = false;
         if (hit.leaf != 0xFFFFFFFFu) {
           const GLeaf L = sc.leaves[hit.leaf];
+          // BARY == false (a scene without vertex normals): the tangent frame of a diffuse bounce off a triangle or a disc is a constant of
+          // the leaf (leaf_frame.hpp) - two 16-byte loads off the same index, issued with the record's own, take the place of a sqrt, a
+          // division and the cross product between the normal's arrival and the new direction. A sphere's record holds zeros, and zeros
+          // stand in where the scene shows no records (option leaf_frame 0; wave-uniform): a lane whose xb is zero computes its frame, so
+          // nothing but the record itself is carried from here to the bounce (a frame about any normal has a component that is not zero,
+          // and were there one that has none, computing it is what gives it).
+          // Plain renders only: the NIF-slot builds of this turn have no registers left for the record (with it the 256-thread build on plain
+          // records spills eight vector registers to scratch, the pre-rotated one two more scalars - profiles/r14_k1w_leaf_frame.txt); they
+          // keep the computed frame.
+          constexpr bool kLeafFrame = !BARY && SLOTS == 0;
+          f3 frX = mk(0.f, 0.f, 0.f), frY = frX;
+          if constexpr (kLeafFrame) {
+            if (sc.leafNormalsOrFrames != nullptr) {
+              // (uniform base + 32-bit byte offset, as for the nodes: an array of fewer than 2^26 records of 32 bytes)
+              const GLeafFrame* fr = reinterpret_cast<const GLeafFrame*>(reinterpret_cast<const char*>(sc.leafNormalsOrFrames) + (hit.leaf << 5));
+              frX = mk(fr->xb[0], fr->xb[1], fr->xb[2]); frY = mk(fr->yb[0], fr->yb[1], fr->yb[2]);
+            }
+          }
           hit.geomID = leaf_geom(L);
           coldU(6) = hit.leaf; coldF(7) = hit.t;
           o = o + d * hit.t;
@@ -614,6 +632,11 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           if (mat.type == 0) {
             const float u1 = rng_uniform01(rng);
             const float u2 = rng_uniform01(rng);
+            if constexpr (kLeafFrame) {
+              f3 xb = frX, yb = frY;
+              if ((frX.x == 0.f) & (frX.y == 0.f) & (frX.z == 0.f)) diffuse_frame(nrm, xb, yb);
+              d = diffuse_in_frame(nrm, xb, yb, u1, u2, sinTbl);
+            } else
             d = sample_diffuse(nrm, u1, u2, sinTbl);
             tp = tp * albedo;
           } else if (mat.type == 1) {
