@@ -288,6 +288,42 @@ MI_HD void sincos_deg_table(float x, const float* tbl, float& s, float& c) {
   s = y;
   c = cx * cz - sx * sz;
 }
+// sincos_deg_table behind its range reduction: x in degrees, 0 <= x < 360, `neg` the sign taken off the angle.
+MI_HD void sincos_deg_reduced(float x, bool neg, const float* tbl, float& s, float& c) {
+  int ix = (int)(x + .5f);
+  const float z = x - (float)ix;
+  bool sneg = false, cneg = false;
+  if (ix > 180) { sneg = true; cneg = true; ix -= 180; }
+  if (ix > 90) { cneg = !cneg; ix = 180 - ix; }
+  float sx = tbl[ix];
+  if (sneg) sx = -sx;
+  float cx = tbl[90 - ix];
+  if (cneg) cx = -cx;
+  const float sz = 1.74531263774940077459e-2f * z;
+  const float cz = 1.f - 1.52307909153324666207e-4f * z * z;
+  float y = sx * cz + cx * sz;
+  if (neg) y = -y;
+  s = y;
+  c = cx * cz - sx * sz;
+}
+// Two callers know their angle's range, and there the correctly rounded x / 360 of the general form (a dozen instructions on the
+// device, on the chain to a new direction) can only give one or two quotients. Both return sincos_deg_table's bits for every binary32
+// angle of their domain (host/shade_consts_check.cpp runs through all of them).
+// |th| <= 2.4 (the concentric map: |th| <= 3 pi / 4): |x| < 138, floorf(x / 360) is 0 and x - 360 * 0 is x. But for th = -0 (uy = +0
+// over a negative ux), which is not `neg`: the general form goes on with -0 - (-0) = +0, this one with -0. The zero only reaches
+// z = x - 0 and sz = k z, and both sums that take sz give the same bits for either: s = 0 * 1 + 1 * sz = +0, c = 1 * 1 - 0 * sz = 1.
+MI_HD void sincos_deg_table_small(float th, const float* tbl, float& s, float& c) {
+  float x = th * (float)(180.0 / 3.14159265358979323846264338327950288);
+  const bool neg = x < 0.f;
+  if (neg) x = -x;
+  sincos_deg_reduced(x, neg, tbl, s, c);
+}
+// 0 <= th <= 6.2831855f (the Box-Muller angle 2 pi u, u in [0, 1]; +0, not -0): 0 <= x <= 360.00003, the quotient's floor is 1 from
+// x = 360 on (360 / 360 is 1) and 0 below (the largest binary32 below 360 divides to 1 - 2^-24), and x - 360 * 1 is exact.
+MI_HD void sincos_deg_table_turn(float th, const float* tbl, float& s, float& c) {
+  const float x = th * (float)(180.0 / 3.14159265358979323846264338327950288);
+  sincos_deg_reduced(x >= 360.f ? x - 360.f : x, false, tbl, s, c);
+}
 
 // ---- xoroshiro128** / splitmix64: include/xoshiro.hpp:18-80 ------------------------------------------
 struct Rng { uint64_t s0, s1; };
@@ -299,10 +335,19 @@ MI_HD uint64_t splitmix64(uint64_t z) {
   return z ^ (z >> 31);
 }
 MI_HD void rng_seed(Rng& r, uint64_t seed) { r.s0 = splitmix64(seed); r.s1 = splitmix64(r.s0); }
+// a * 5 and a * 9 modulo 2^64 as (a << 2) + a and (a << 3) + a: one v_lshl_add_u64 each on the device. hipcc lowers the 64-bit
+// multiply to two v_mad_u64_u32 and two moves, and turns the shift-add written in C++ back into that multiply.
+#if defined(__HIP_DEVICE_COMPILE__)
+MI_HD uint64_t mul5_u64(uint64_t a) { uint64_t r; asm("v_lshl_add_u64 %0, %1, 2, %1" : "=v"(r) : "v"(a)); return r; }
+MI_HD uint64_t mul9_u64(uint64_t a) { uint64_t r; asm("v_lshl_add_u64 %0, %1, 3, %1" : "=v"(r) : "v"(a)); return r; }
+#else
+MI_HD uint64_t mul5_u64(uint64_t a) { return a * 5; }
+MI_HD uint64_t mul9_u64(uint64_t a) { return a * 9; }
+#endif
 MI_HD uint64_t rng_next(Rng& r) {
   const uint64_t a = r.s0;
   uint64_t b = r.s1;
-  const uint64_t out = rotl64(a * 5, 7) * 9;
+  const uint64_t out = mul9_u64(rotl64(mul5_u64(a), 7));
   b ^= a;
   r.s0 = rotl64(a, 24) ^ b ^ (b << 16);
   r.s1 = rotl64(b, 37);
@@ -382,7 +427,7 @@ MI_HD void rng_gauss2(Rng& r, const float* sinTbl, float& g0, float& g1) {
   if (w < 2.98023223876953125e-08f) w = 2.98023223876953125e-08f;
   const float rad = sqrtf(-2.f * log_det(w));
   float sn, cs;
-  sincos_deg_table(6.283185307179586f * ub, sinTbl, sn, cs);
+  sincos_deg_table_turn(6.283185307179586f * ub, sinTbl, sn, cs);      // (ub in [0, 1])
   g0 = rad * cs;
   g1 = rad * sn;
 }
@@ -414,7 +459,7 @@ MI_HD void sample_disc_concentric(float u1, float u2, const float* sinTbl, float
   const float q = piby4 * ((wide ? uy : ux) / (wide ? ux : uy));
   const float th = wide ? q : piby2 - q;
   float s, c;
-  sincos_deg_table(th, sinTbl, s, c);
+  sincos_deg_table_small(th, sinTbl, s, c);      // (|q| <= pi / 4: |th| <= 3 pi / 4)
   ox = r * c; oy = r * s;
 }
 MI_HD f3 cosine_sample_hemisphere(float u1, float u2, const float* sinTbl) {
@@ -450,14 +495,18 @@ MI_HD f3 reflect_dir(f3 d, f3 n) {
   const float cosTheta = dot(d, n);
   return normalized(d - n * (cosTheta * 2.f));
 }
-MI_HD float schlick(float cosTheta, float ri) {
-  float r0 = (1.f - ri) / (1.f + ri);
-  r0 = r0 * r0;
+// Schlick's approximation in its two halves: the reflectance at normal incidence, a function of the index ratio alone, and the rest
+MI_HD float schlick_r0(float ri) {
+  const float r0 = (1.f - ri) / (1.f + ri);
+  return r0 * r0;
+}
+MI_HD float schlick_from_r0(float cosTheta, float r0) {
   const float base = 1.f - cosTheta;
   const float base2 = base * base;
   const float base5 = base2 * base * base2;
   return r0 + (1.f - r0) * base5;
 }
+MI_HD float schlick(float cosTheta, float ri) { return schlick_from_r0(cosTheta, schlick_r0(ri)); }
 MI_HD f3 refract_dir(f3 dir, f3 n, float ndotr, float ri) {
   const float cosTheta = -ndotr;
   const f3 rPerp = (dir + n * cosTheta) * ri;
@@ -473,6 +522,46 @@ MI_HD bool dielectric(f3 dir, f3 n, float ri, float u1, f3& out) {
   out = reflect_dir(dir, n);
   return false;
 }
+// What a dielectric bounce takes from its material alone: the index ratio of a ray that enters, and the reflectance at normal incidence
+// of a ray that leaves (ratio ior) and of one that enters (ratio 1 / ior) - the binary32 operations dielectric() and schlick() run at
+// every bounce, in their order. K1w computes them once per material, where a workgroup stages the materials (trace_wavefront.hpp).
+struct DielectricConsts { float invIor, r0In, r0Out; };
+MI_HD DielectricConsts dielectric_consts(float ior) {
+  DielectricConsts k;
+  k.invIor = 1.f / ior;
+  k.r0In = schlick_r0(ior);
+  k.r0Out = schlick_r0(k.invIor);
+  return k;
+}
+// The index ratio and its r0 for a ray on either side (`inside`: dot(n, dir) > 0, it leaves the medium) - computed at the bounce as
+// dielectric() and schlick() do, or selected from the material's constants: the same values.
+struct DielectricComputed {};
+MI_HD void dielectric_ratio(float ior, const DielectricComputed&, bool inside, float& ri, float& r0) {
+  ri = inside ? ior : 1.f / ior;
+  r0 = schlick_r0(ri);
+}
+MI_HD void dielectric_ratio(float ior, const DielectricConsts& k, bool inside, float& ri, float& r0) {
+  ri = inside ? ior : k.invIor;
+  r0 = inside ? k.r0In : k.r0Out;
+}
+// dielectric() over either source of the ratio; everything else is dielectric()'s, on the same operands (K1w's form of the bounce:
+// trace_wavefront.hpp shade_specular).
+template <class K>
+MI_HD bool dielectric_with(f3 dir, f3 n, float ior, const K& k, float u1, f3& out) {
+  const bool inside = dot(n, dir) > 0.f;
+  if (inside) n = -n;
+  float ri, r0;
+  dielectric_ratio(ior, k, inside, ri, r0);
+  const float ndotr = dot(n, dir);
+  const float cost1 = -ndotr;
+  const float cost2 = 1.f - ri * ri * (1.f - cost1 * cost1);
+  const bool refracts = cost2 > 0.f && u1 > schlick_from_r0(cost1, r0);
+  if (refracts) out = refract_dir(dir, n, ndotr, ri);
+  else out = reflect_dir(dir, n);
+  return refracts;
+}
+// dielectric() with its two divisions taken from the material's constants
+MI_HD bool dielectric(f3 dir, f3 n, float ior, const DielectricConsts& k, float u1, f3& out) { return dielectric_with(dir, n, ior, k, u1, out); }
 // geometric_sampling.hpp:56-63 — survival probability is the smallest throughput channel
 MI_HD bool roulette_stop(float u1, f3& tp) {
   const float p = min_comp(tp);

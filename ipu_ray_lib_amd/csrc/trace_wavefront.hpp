@@ -110,6 +110,23 @@ constexpr uint32_t kEnvBlock = 256;      // what a wave has left of its last res
                                          // before, every further whole block is filled with kEnvHole - entries no MLP kernel evaluates (nif_kernels.hpp kNifHole)
 constexpr uint32_t kEnvHole = 0xFFFFFFFFu;
 
+// The bounce off a mirror (material type 1) or a dielectric (type 2: glass) of both SHADE copies, over either source of the dielectric's
+// index ratio (ray_math.h dielectric_with). With the uniform choice of the source inside the glass branch alone - dielectric() on the
+// constants or dielectric() as it was - the headline build and two more spill a vector register; in this form none does.
+template <class K>
+__device__ __forceinline__ void shade_specular(bool glass, float ior, const K& k, f3 albedo, Rng& rng, f3 nrm, f3& d, f3& tp) {
+  if (!glass) {
+    d = reflect_dir(d, nrm);
+    tp = tp * albedo;
+  } else {
+    const float u1 = rng_uniform01(rng);
+    f3 nd;
+    const bool refracted = dielectric_with(d, nrm, ior, k, u1, nd);
+    d = nd;
+    if (refracted) tp = tp * albedo;
+  }
+}
+
 constexpr WaveTune kDefaultTune = {8, 16, 24, 48, 3, 4, 6, 1, 1, 40, 0};      // re-swept on the round-3 kernel on two scenes (profiles/r03_kernel_ab.txt): a cheaper box test favours one more of them per vote
 // DF: the reference's ALLOW_DOUBLE_FALLBACK=1 build of the triangle test (trace_kernels.hpp). FAST: the tolerance tier
 // (scene option "fast"): the box test as three pairs of FMAs on (plane, 1/d, -o/d), the triangle test contracted, no
@@ -130,12 +147,18 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
   // the materials a hit is shaded with, when the scene has few (the built-in scenes have 8, test_scene.dae 9): SHADE
   // otherwise waits for two dependent global loads, leaf record then material
   constexpr uint32_t kMatCache = 16;
-  struct __attribute__((aligned(16))) CachedMaterial { mi_material m; uint32_t pad[3]; };
+  // (behind the 36 bytes of a material, in what was padding: the divisions a dielectric bounce would make from its ior - ray_math.h
+  // dielectric_consts -, filled by the thread that stages the ior)
+  struct __attribute__((aligned(16))) CachedMaterial { mi_material m; DielectricConsts k; };
+  static_assert(sizeof(CachedMaterial) == 48 && sizeof(mi_material) == 36, "a staged material is three 16-byte reads");
   __shared__ CachedMaterial matS[kMatCache];
   const bool matsInLds = sc.numMaterials <= kMatCache;
   if (matsInLds) {
-    for (uint32_t k = threadIdx.x; k < sc.numMaterials * 9u; k += blockDim.x)
-      reinterpret_cast<uint32_t*>(&matS[k / 9u].m)[k % 9u] = reinterpret_cast<const uint32_t*>(sc.materials)[k];
+    for (uint32_t k = threadIdx.x; k < sc.numMaterials * 9u; k += blockDim.x) {
+      const uint32_t w = reinterpret_cast<const uint32_t*>(sc.materials)[k];
+      reinterpret_cast<uint32_t*>(&matS[k / 9u].m)[k % 9u] = w;
+      if (k % 9u == offsetof(mi_material, ior) / 4u) matS[k / 9u].k = dielectric_consts(__uint_as_float(w));
+    }
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char dynLds[];
   load_sin_table(sinTbl);
@@ -626,7 +649,8 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           // (two loads under a wave-uniform branch: as a select of the two addresses hipcc made FLAT loads of it, which go through the
           // texture addresser as well as the LDS and wait on both counters)
           mi_material mat;
-          if (matsInLds) { mat = matS[L.matIndex].m; asm volatile("" ::: "memory"); } else mat = sc.materials[L.matIndex];      // (the empty asm keeps the two loads apart)
+          DielectricConsts matK = {0.f, 0.f, 0.f};      // (read only where the materials are in LDS)
+          if (matsInLds) { mat = matS[L.matIndex].m; matK = matS[L.matIndex].k; asm volatile("" ::: "memory"); } else mat = sc.materials[L.matIndex];      // (the empty asm keeps the two loads apart)
           const f3 albedo = mk(mat.albedo.x, mat.albedo.y, mat.albedo.z);
           if (mat.emissive) color = color + tp * mk(mat.emission.x, mat.emission.y, mat.emission.z);
           if (mat.type == 0) {
@@ -639,15 +663,10 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
             } else
             d = sample_diffuse(nrm, u1, u2, sinTbl);
             tp = tp * albedo;
-          } else if (mat.type == 1) {
-            d = reflect_dir(d, nrm);
-            tp = tp * albedo;
-          } else if (mat.type == 2) {
-            const float u1 = rng_uniform01(rng);
-            f3 nd2;
-            const bool refracted = dielectric(d, nrm, mat.ior, u1, nd2);
-            d = nd2;
-            if (refracted) tp = tp * albedo;
+          } else if (mat.type == 1 || mat.type == 2) {
+            // (the staged constants where the materials are in LDS, the computing form for a scene of more than kMatCache: wave-uniform)
+            if (matsInLds) shade_specular(mat.type == 2, mat.ior, matK, albedo, rng, nrm, d, tp);
+            else shade_specular(mat.type == 2, mat.ior, DielectricComputed{}, albedo, rng, nrm, d, tp);
           } else {
             const float qn = __builtin_nanf("");
             coldF(3) = coldF(3) * qn; coldF(4) = coldF(4) * qn; coldF(5) = coldF(5) * qn;
@@ -786,7 +805,8 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           o = o + d * hit.t;                                          // updateHit, Render.hpp:15-23
           nrm = hit_normal(sc, hit, o);
           mi_material mat;                                                                              // = materials[matIDs[geomID]]
-          if (matsInLds) { mat = matS[L.matIndex].m; asm volatile("" ::: "memory"); } else mat = sc.materials[L.matIndex];      // (the empty asm keeps the two loads apart)
+          DielectricConsts matK = {0.f, 0.f, 0.f};      // (read only where the materials are in LDS)
+          if (matsInLds) { mat = matS[L.matIndex].m; matK = matS[L.matIndex].k; asm volatile("" ::: "memory"); } else mat = sc.materials[L.matIndex];      // (the empty asm keeps the two loads apart)
           const f3 albedo = mk(mat.albedo.x, mat.albedo.y, mat.albedo.z);
           if (mat.emissive) color = color + tp * mk(mat.emission.x, mat.emission.y, mat.emission.z);
           if (mat.type == 0) {
@@ -794,15 +814,10 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
             const float u2 = rng_uniform01(rng);
             d = sample_diffuse(nrm, u1, u2, sinTbl);
             tp = tp * albedo;
-          } else if (mat.type == 1) {
-            d = reflect_dir(d, nrm);
-            tp = tp * albedo;
-          } else if (mat.type == 2) {
-            const float u1 = rng_uniform01(rng);
-            f3 nd2;
-            const bool refracted = dielectric(d, nrm, mat.ior, u1, nd2);
-            d = nd2;
-            if (refracted) tp = tp * albedo;
+          } else if (mat.type == 1 || mat.type == 2) {
+            // (the staged constants where the materials are in LDS, the computing form for a scene of more than kMatCache: wave-uniform)
+            if (matsInLds) shade_specular(mat.type == 2, mat.ior, matK, albedo, rng, nrm, d, tp);
+            else shade_specular(mat.type == 2, mat.ior, DielectricComputed{}, albedo, rng, nrm, d, tp);
           } else {
             const float qn = __builtin_nanf("");
             coldF(3) = coldF(3) * qn; coldF(4) = coldF(4) * qn; coldF(5) = coldF(5) * qn;
