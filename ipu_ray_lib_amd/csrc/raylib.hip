@@ -120,7 +120,6 @@ const float* hostSinTable() {
 constexpr uint32_t kNifSplDefault = 512, kNifSplMax = 1024;
 constexpr int kHotNodesAuto = -1;                 // option "hot_nodes" = auto: on, with as many nodes as fit, where the staged prefix takes kHotAutoShare of the tree's expected box tests
 constexpr double kHotAutoShare = 0.9;             // (hot_order.hpp hot_prefix_share; the box scene: 0.96 and -2.4 % frame time, test_scene.dae: 0.76 and +2 % - profiles/r06_k1w_hot_nodes_ab.txt)
-constexpr uint32_t kHotThreads = 768;             // the HOT builds' workgroup: two per compute unit, six waves per SIMD - the larger the workgroup, the larger the prefix its copies of the cold state leave room for (256 x 6: 68 nodes, 512 x 3: 172, 768 x 2: 316)
 constexpr uint32_t kLdsPerCU = 160 * 1024, kLdsGranule = 1280;      // gfx950 hands LDS out in 320-dword granules; the occupancy query does not round
 struct SceneOptions {
   bool fullStats = false;          // MI_RAYLIB_FULL_STATS / "full_stats": instrumented kernel variants (node/leaf counters, phase occupancy)
@@ -154,7 +153,7 @@ struct SceneOptions {
   uint32_t nifSplit = 0;           // "nif_split": compute units a NIF render's trace launches of batches 1.. get for themselves (CU-masked streams: the MLP's
                                    // workgroups take every register of their unit, so a trace launch beside them otherwise only runs in their ramps and tails;
                                    // the MLP is power-limited and loses less than the units it gives up: DESIGN.md §6). 0 = no partition
-  bool nifFirstTest = false;       // "nif_first_test": a NIF render's casts take their first box test in the turn that sets them up (trace_wavefront.hpp kFirstInSetup) instead of
+  bool nifFirstTest = false;       // "nif_first_test": a NIF render's casts take their first box test in the turn that sets them up (k1w_builds.hpp firstInSetup) instead of
                                    // in a NODE turn. Measured neutral (config 5: NODE turns 11.0 -> 3.4 per 64 casts, SHADE turns 1.2 -> 2.1 at lower occupancy, frame +-0.05 %,
                                    // profiles/r05_config5_launch_ab.txt): off by default, kept for A/B; results are the same either way
   bool nifTiming = false;          // "nif_timing": HIP events round every MLP launch of a NIF render (mi_get_nif_timing)
@@ -199,6 +198,8 @@ struct SceneOptions {
     out = r;
     return true;
   }
+  // what option fast has a build for: kernel 1, 6 waves, one SHADE / GEN turn, default weights, no spec
+  bool defaultKernelOnly() const { return kernelChoice == 1 && !specLeaf && wavesPerSimd == 6 && mergeTurns && tune == kDefaultTune; }
   bool set(const std::string& key, const char* v) {
     why = "unknown option or bad value";
     if (!v) return false;
@@ -217,7 +218,7 @@ struct SceneOptions {
     if (fast && (key == "kernel" || key == "waves" || key == "spec" || key == "merge" || key == "tune")) {
       SceneOptions probe = *this; probe.fast = false;
       if (!probe.set(key, v)) { why = probe.why; return false; }
-      if (probe.kernelChoice != 1 || probe.specLeaf || probe.wavesPerSimd != 6 || !probe.mergeTurns || !(probe.tune == kDefaultTune)) {
+      if (!probe.defaultKernelOnly()) {
         why = "fast is a build of the default kernel only (kernel 1, 6 waves, one SHADE / GEN turn, default weights, no spec): clear fast first"; return false;
       }
       return true;      // (a default value: nothing to change)
@@ -285,7 +286,7 @@ struct SceneOptions {
       if (!flag01(v, b)) return false;
       if (b && (fullStats || doubleFallback)) { why = "fast cannot be combined with full_stats or double_fallback"; return false; }
 #if MI_RAYLIB_VARIANTS
-      if (b && (kernelChoice != 1 || specLeaf || wavesPerSimd != 6 || !mergeTurns || !(tune == kDefaultTune))) { why = "fast is a build of the default kernel only (kernel 1, 6 waves, one SHADE / GEN turn, default weights, no spec)"; return false; }
+      if (b && !defaultKernelOnly()) { why = "fast is a build of the default kernel only (kernel 1, 6 waves, one SHADE / GEN turn, default weights, no spec)"; return false; }
 #endif
       fast = b; return true;
     }
@@ -1495,6 +1496,21 @@ void launchWavefront(mi_scene& S, mi_trace_result* d_rays, uint32_t cnt, hipStre
     hipLaunchKernelGGL(pixel_coords_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream, d_rays, cnt, slot.d_coords);
     coords = slot.d_coords;
   }
+  // Which build of K1w (k1w_builds.hpp select_k1w), from the launch, the scene and its options. The HOT builds take plain renders while the scene's private
+  // copies stand for the shared arrays (mi_scene::touchArrays): the plain ones walk the collapsed copy (mi_scene::thin), the instrumented one the copy of every node.
+  K1wChoice choice{};
+  choice.variants = MI_RAYLIB_VARIANTS != 0; choice.stats = STATS; choice.slots = !plain;
+  choice.hasNormals = S.ds.hasNormals != 0; choice.rotLeaves = S.ds.leavesRot != nullptr; choice.hasNodes = S.ds.numNodes > 0;
+  choice.hotOn = S.opt.hotNodes != 0 && (STATS ? S.hot.valid : S.thin.valid) && S.ds.numNodes > 0;
+  choice.doubleFallback = S.opt.doubleFallback; choice.fast = S.opt.fast; choice.specLeaf = S.opt.specLeaf; choice.mergeTurns = S.opt.mergeTurns;
+  choice.leanHit = S.opt.leanHit; choice.leafRot = S.opt.leafRot; choice.kernelChoice = S.opt.kernelChoice; choice.wavesPerSimd = S.opt.wavesPerSimd;
+  choice.defaultWeights = S.opt.tune == kDefaultTune;
+#if MI_RAYLIB_VARIANTS
+  choice.poolFits = S.ds.samplesPerPixel <= kPoolMaxSamples && S.ds.maxPathLength <= kPoolMaxBounces;
+#endif
+  const K1wId picked = select_k1w(choice);
+  // (the tolerance tier - never the default - has plain, un-instrumented launches only; mi_scene_set_option refuses the other combinations it has no build for)
+  if (picked == K1wId::RefusedFast) throw ArgError("mi_render: the tolerance tier (option fast) has no NIF / instrumented build; clear the option for this render");
   for (uint32_t l = 0; l < launches; ++l) {
     const uint32_t segBase = l * perLaunch;
     WaveExtras exs = ex;
@@ -1512,43 +1528,51 @@ void launchWavefront(mi_scene& S, mi_trace_result* d_rays, uint32_t cnt, hipStre
       if (!plain) wgs = std::min<uint64_t>(wgs, kMaxSlotWorkgroups);      // (the escaped-slot list has padding for that many)
       return (uint32_t)wgs;
     };
-    auto go = [&](auto kern) {
-      if (S.opt.sayGrid) fprintf(stderr, "mi_raylib: grid %u workgroups = %u units x %u resident\n", grid(kern, 256, 0), units, S.residentBlocks(reinterpret_cast<const void*>(kern), 256, 0));
+    auto go = [&](auto kern, const char* name) {
+      if (S.opt.sayGrid) fprintf(stderr, "mi_raylib: grid %u workgroups = %u units x %u resident, build %s\n", grid(kern, 256, 0), units, S.residentBlocks(reinterpret_cast<const void*>(kern), 256, 0), name);
       hipLaunchKernelGGL(kern, dim3(grid(kern, 256, 0)), dim3(256), 0, stream, dsv, d_rays, cnt, workCounter, 0u, S.opt.tune, tileW, exs);
     };
-#define MI_K1W_HOT(BL, BA, RO) path_trace_wavefront_kernel<false, false, BL, 6, false, 0, true, false, false, true, BA, RO, true>
-    // Option "hot_nodes": the HOT builds (trace_wavefront.hpp) walk the scene's private, hot-first copies and stage their first nodes in
-    // dynamic LDS - as many as asked for, as the copy has, and as fit without costing a resident workgroup. Plain renders only, while the
-    // copies stand for the shared arrays (mi_scene::touchArrays); false = nothing launched: the caller goes on to today's kernel.
-    // The plain builds walk the collapsed copy (mi_scene::thin), the instrumented one the copy of every node: its counters are the reference's visits.
-    const bool hotOn = plain && S.opt.hotNodes != 0 && (STATS ? S.hot.valid : S.thin.valid) && S.ds.numNodes > 0;
-    auto goHot = [&](auto kern, uint32_t threads) -> bool {
+    // Option "hot_nodes": the HOT builds stage the first nodes of the private copy they walk in dynamic LDS - as many as asked for, as the copy
+    // has, and as fit without costing a resident workgroup. false = nothing launched (no node fits, or `auto` declines).
+    auto goHot = [&](auto kern, uint32_t threads, const char* name) -> bool {
       const mi_scene::HotCopy& copy = STATS ? S.hot : S.thin;
       const uint32_t room = S.hotRoom(reinterpret_cast<const void*>(kern), (int)threads);
       const uint32_t count = std::min(std::min(S.opt.hotNodes < 0 ? ~0u : (uint32_t)S.opt.hotNodes, copy.thinNodes), room / (uint32_t)sizeof(GNode));
       if (!count) return false;
       if (S.opt.hotNodes < 0) {
         // auto: decided from the prefix the plain build of this scene's kind stages, whichever build is being launched (the instrumented one has room for more)
-        const uint32_t plainRoom = S.ds.hasNormals ? S.hotRoom(reinterpret_cast<const void*>(MI_K1W_HOT(kHotThreads, true, false)), (int)kHotThreads)
-                                                   : S.hotRoom(reinterpret_cast<const void*>(MI_K1W_HOT(kHotThreads, false, true)), (int)kHotThreads);
+        const uint32_t plainRoom = S.ds.hasNormals ? S.hotRoom(reinterpret_cast<const void*>(path_trace_wavefront_kernel<K1wHotBary>), K1wHotBary::block)
+                                                   : S.hotRoom(reinterpret_cast<const void*>(path_trace_wavefront_kernel<K1wHotRot>), K1wHotRot::block);
         const uint32_t ref = std::min(S.thin.thinNodes, plainRoom / (uint32_t)sizeof(GNode));
         if (!ref || S.thin.share[ref - 1] < kHotAutoShare) return false;
       }
       const uint32_t wgs = grid(kern, threads, room);
-      if (S.opt.sayGrid) fprintf(stderr, "mi_raylib: grid %u workgroups of %u threads, %u hot nodes of %u that fit\n", wgs, threads, count, room / (uint32_t)sizeof(GNode));
+      if (S.opt.sayGrid) fprintf(stderr, "mi_raylib: grid %u workgroups of %u threads, %u hot nodes of %u that fit, build %s\n", wgs, threads, count, room / (uint32_t)sizeof(GNode), name);
       hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), (size_t)count * sizeof(GNode), stream, S.hotView(copy), d_rays, cnt, workCounter, count, S.opt.tune, tileW, exs);
       return true;
     };
-    if (S.opt.doubleFallback) {
-      // the ALLOW_DOUBLE_FALLBACK=1 variant: the phase-scheduled kernel's 4-wave build with the binary64 edge functions compiled in
-      go(path_trace_wavefront_kernel<STATS, false, 256, 4, false, 2, false, true>);
-    } else if (S.opt.fast) {
-      // the tolerance tier (never the default): FMA box and triangle tests. Plain, un-instrumented launches of the default kernel only;
-      // mi_scene_set_option refuses the combinations it has no build for, a NIF render is refused here.
-      if (!plain || STATS) throw ArgError("mi_render: the tolerance tier (option fast) has no NIF / instrumented build; clear the option for this render");
-      go(path_trace_wavefront_kernel<false, false, 256, 6, false, 0, true, false, true>);
+    auto launch = [&](K1wId id) -> bool {      // false: a HOT build that launched nothing
+      bool launched = true;
+      const bool has = with_k1w<MI_RAYLIB_VARIANTS != 0>(id, [&](auto build) {
+        using B = decltype(build);
+        auto kern = path_trace_wavefront_kernel<B>;
+        if constexpr (B::hot) launched = goHot(kern, B::block, k1w_name(id));
+        else if constexpr (B::ldsNodes) {
+          // kernel 2: one 1024-thread workgroup per CU shares one LDS copy of the first nodes of the (preorder) array
+          const uint32_t ldsNodes = std::min<uint32_t>(S.ds.numNodes, kLdsBudgetBytes / (uint32_t)sizeof(GNode));
+          if (!S.ldsAttrSet[B::stats ? 1 : 0]) {
+            HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudgetBytes));
+            S.ldsAttrSet[B::stats ? 1 : 0] = true;
+          }
+          const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + 1023) / 1024, S.cus());
+          hipLaunchKernelGGL(kern, dim3(blocks), dim3(B::block), (size_t)ldsNodes * sizeof(GNode), stream, S.view(), d_rays, cnt, workCounter, ldsNodes, S.opt.tune, tileW, exs);
+        } else go(kern, k1w_name(id));
+      });
+      if (!has) throw std::logic_error(std::string("mi_render: this library has no build ") + k1w_name(id));      // (nothing select_k1w returns for it: tests/test_k1w_builds.py)
+      return launched;
+    };
+    if (picked == K1wId::PathPool) {
 #if MI_RAYLIB_VARIANTS
-    } else if (S.opt.kernelChoice == 3 && S.ds.samplesPerPixel <= kPoolMaxSamples && S.ds.maxPathLength <= kPoolMaxBounces) {
       // path pool (trace_pool.hpp): persistent, exactly as many workgroups as stay resident; a workgroup of W waves
       // owns 100 W path slots
       const uint32_t W = (uint32_t)S.opt.poolWaves, pwg = 100u * W;
@@ -1572,57 +1596,11 @@ void launchWavefront(mi_scene& S, mi_trace_result* d_rays, uint32_t cnt, hipStre
       if (W == 4) goPool(path_trace_pool_kernel<STATS, 4, 400, 4>, 0);
       else if (W == 8) goPool(path_trace_pool_kernel<STATS, 8, 800, 4>, 1);
       else goPool(path_trace_pool_kernel<STATS, 16, 1600, 4>, 2);
-    } else if (plain && S.opt.kernelChoice == 2 && S.ds.numNodes > 0) {
-      // one 1024-thread workgroup per CU shares one LDS copy of the first nodes of the (preorder) array
-      const uint32_t ldsNodes = std::min<uint32_t>(S.ds.numNodes, kLdsBudgetBytes / (uint32_t)sizeof(GNode));
-      const size_t ldsBytes = (size_t)ldsNodes * sizeof(GNode);
-      auto kern = path_trace_wavefront_kernel<STATS, true, 1024>;
-      if (!S.ldsAttrSet[STATS ? 1 : 0]) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBudgetBytes));
-        S.ldsAttrSet[STATS ? 1 : 0] = true;
-      }
-      const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + 1023) / 1024, S.cus());
-      hipLaunchKernelGGL(kern, dim3(blocks), dim3(1024), ldsBytes, stream, S.view(), d_rays, cnt, workCounter, ldsNodes, S.opt.tune, tileW, exs);
-    } else if (S.opt.specLeaf) {
-      if (!STATS) go(path_trace_wavefront_kernel<false, false, 256, 5, true>);
-      else go(path_trace_wavefront_kernel<STATS, false, 256, 4, true>);
-    } else if (!STATS && !(S.opt.tune == kDefaultTune)) {
-      // runtime weights (tune sweeps, knock-in probes): scalar spills, a few per cent slower than the compiled-in weights
-      if (S.opt.wavesPerSimd == 6) go(path_trace_wavefront_kernel<false, false, 256, 6>);
-      else go(path_trace_wavefront_kernel<false, false, 256, 5>);
-    } else if (!STATS && !S.opt.mergeTurns) {
-      // SHADE and GEN as two turns, five waves per SIMD: the default kernel up to round 3, kept for A/B and parity
-      if (plain) go(path_trace_wavefront_kernel<false, false, 256, 5, false, 0, true, false, false, false>);
-      else go(path_trace_wavefront_kernel<false, false, 256, 5, false, 1, true, false, false, false>);
-    } else if (!STATS && S.opt.wavesPerSimd == 7 && plain) {
-      go(path_trace_wavefront_kernel<false, false, 256, 7, false, 0, true>);                   // 72 VGPRs, 21 words of LDS per lane: seven waves per SIMD
-    } else if (!STATS && S.opt.wavesPerSimd == 5) {
-      if (plain) go(path_trace_wavefront_kernel<false, false, 256, 5, false, 0, true>);        // the 96-VGPR build of today's form
-      else go(path_trace_wavefront_kernel<false, false, 256, 5, false, 1, true>);
 #endif
-    } else if (!STATS && S.opt.wavesPerSimd == 6) {
-      // the default path: SHADE and GEN in one turn, 80 VGPRs without a spill, six waves per SIMD (profiles/r04_k1w_merged_turn_ab.txt);
-      // the default scheduling weights are compiled into the two instantiations (plain renders / NIF slots)
-      // the builds of the default form: a scene WITHOUT vertex normals takes the one that carries no barycentrics (option "lean_hit")
-      // and reads the primitive records pre-rotated for the cast's shear axis (option "leaf_rot"); both default on, both exact (every
-      // byte the oracle's either way), the other settings kept for A/B. With vertex normals the pre-rotated form spills seven
-      // registers at 80 and loses 8 % (test_scene.dae: 292 against 271 ms per 1000 spp, profiles/r05_k1w_leaf_ab.txt): not built.
-      const bool lean = S.opt.leanHit && !S.ds.hasNormals;
-      const bool rot = lean && S.opt.leafRot && S.ds.leavesRot != nullptr;
-      bool launched = false;
-      if (hotOn && rot) launched = goHot(MI_K1W_HOT(kHotThreads, false, true), kHotThreads);
-      else if (hotOn && !lean) launched = goHot(MI_K1W_HOT(kHotThreads, true, false), kHotThreads);
-#define MI_K1W(SL, BA, RO) path_trace_wavefront_kernel<false, false, 256, 6, false, SL, true, false, false, true, BA, RO>
-      if (launched) {}
-      else if (plain) { if (rot) go(MI_K1W(0, false, true)); else if (lean) go(MI_K1W(0, false, false)); else go(MI_K1W(0, true, false)); }
-      else { if (rot) go(MI_K1W(1, false, true)); else if (lean) go(MI_K1W(1, false, false)); else go(MI_K1W(1, true, false)); }
-#undef MI_K1W
-    } else if (STATS && hotOn && goHot(path_trace_wavefront_kernel<true, false, 256, 4, false, 2, false, false, false, true, true, false, true>, 256)) {
-      // (the instrumented HOT build: the same walk of the private copies, its runs counted - mi_get_hot_stats)
-    } else {
-      go(path_trace_wavefront_kernel<STATS, false, 256>);               // the instrumented build (and, in the variants build, option waves = 4)
+    } else if (!launch(picked)) {      // a HOT build that launched nothing: what the selection says without hot nodes
+      choice.hotOn = false;
+      launch(select_k1w(choice));
     }
-#undef MI_K1W_HOT
     if (segmented) hipLaunchKernelGGL(segment_combine_kernel, dim3((cnt + 255) / 256), dim3(256), 0, stream, d_rays, cnt, exs.segments, slot.d_segPart, segBase ? 1u : 0u);
   }
 }

@@ -11,7 +11,7 @@
 // (the phase is no register: it is read off the lane's `node` word - kGenNode below - so no turn writes it back and every vote is a
 // compare of that word)
 // and each loop iteration the wave votes (ballot + popcount, scalar) and runs the phase most of its
-// lanes are waiting in (SHADE and GEN are served by ONE turn: template parameter MERGE). A lane that
+// lanes are waiting in (SHADE and GEN are served by ONE turn: field merge of the build, k1w_builds.hpp). A lane that
 // finishes a path starts its next sample in the turn that ended the path, a lane that
 // finishes a work unit - a 4- to 64-sample segment of a pixel (ray_math.h) - pulls a new one, so no lane
 // idles until the frame runs out of work; units are small on purpose, the drain at the end of a frame is paid
@@ -24,6 +24,7 @@
 // bit-identical to the nested-loop kernel and to the CPU oracle.
 #pragma once
 
+#include "k1w_builds.hpp"
 #include "trace_kernels.hpp"
 
 namespace mi {
@@ -87,18 +88,6 @@ struct WaveExtras {
   uint32_t firstInSetup = 0;     // slot-mode launches: 1 = a cast's first box test runs in the turn that sets the cast up (scene option "nif_first_test") instead of in a NODE turn
 };
 
-// SPEC: a lane whose walk reaches a primitive whose box it hits does not wait for the LEAF turn: it notes the primitive
-// (pend1, found at node pend1Node) and walks on as if the test were going to leave the closest hit unchanged - which
-// is what the reference's walk does in that case. When the LEAF turn has run the test, either the guess was right
-// (no closer hit: the box tests made meanwhile used the right hit distance and stand) or the lane goes back to node
-// pend1Node + 1 with the new, closer hit and repeats the walk from there, exactly as the reference continues. A second
-// primitive found while the first is still pending makes the lane wait as before. Nothing is ever skipped or reordered
-// in what a path finally takes from the walk: only work that turns out to be unnecessary is added, in lanes that
-// would have idled.
-// SLOTS: 0 = plain launches only (rgb in registers / partial sums), 1 = NIF launches only (slots), 2 = decided at run time
-// from ex.slotColor. FIXED_TUNE: the scheduling weights are the compile-time defaults (kDefaultTune) instead of the
-// `tune` argument. The two default-path instantiations (<.., 0, true> and <.., 1, true>) carry neither the other mode's
-// code nor the ten weights in scalar registers: no scalar spills (33 before), -2.5 % frame time.
 // How many lanes below this one are set in `mask` (v_mbcnt: no per-lane bit mask held in registers across the kernel).
 __device__ __forceinline__ uint32_t lane_rank(unsigned long long mask) {
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
@@ -128,21 +117,14 @@ __device__ __forceinline__ void shade_specular(bool glass, float ior, const K& k
 }
 
 constexpr WaveTune kDefaultTune = {8, 16, 24, 48, 3, 4, 6, 1, 1, 40, 0};      // re-swept on the round-3 kernel on two scenes (profiles/r03_kernel_ab.txt): a cheaper box test favours one more of them per vote
-// DF: the reference's ALLOW_DOUBLE_FALLBACK=1 build of the triangle test (trace_kernels.hpp). FAST: the tolerance tier
-// (scene option "fast"): the box test as three pairs of FMAs on (plane, 1/d, -o/d), the triangle test contracted, no
-// literal NaN-exact fallback - results within a stated tolerance of the exact tier's, not bit-identical.
-// BARY = false (round 5): for scenes WITHOUT vertex normals. The barycentrics of the closest hit only ever feed the interpolated
-// normal (Mesh.hpp:115-120); a scene without vertex normals shades with the face normal, so the three products per primitive test,
-// the three selects of the closest-hit update and three registers of the walk are dead weight there. Bit-identical by construction
-// (nothing reads them); launchWavefront picks it by the scene's hasNormals.
-template <bool STATS, bool LDS_NODES, int BLOCK, int WAVES_PER_SIMD = 4, bool SPEC = false, int SLOTS = 2, bool FIXED_TUNE = false, bool DF = false, bool FAST = false, bool MERGE = true,
-          bool BARY = true, bool ROT = false, bool HOT = false>
-__global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIMD > 4) ? WAVES_PER_SIMD : 1) path_trace_wavefront_kernel(DeviceScene sc, mi_trace_result* rays, uint32_t n,
+// Build: one of the builds of k1w_builds.hpp, which says what each field means and what follows from it.
+template <class Build>
+__global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_trace_wavefront_kernel(DeviceScene sc, mi_trace_result* rays, uint32_t n,
                                                                    uint32_t* workCounter, uint32_t ldsNodeCount, WaveTune tuneArg, uint32_t tileStreamW, WaveExtras ex) {
+  constexpr bool STATS = Build::stats, LDS_NODES = Build::ldsNodes, SPEC = Build::spec, FIXED_TUNE = Build::fixedTune, DF = Build::df, FAST = Build::fast, MERGE = Build::merge, BARY = Build::bary, ROT = Build::rot, HOT = Build::hot;
+  constexpr int BLOCK = Build::block, SLOTS = Build::slots;
   const WaveTune tune = FIXED_TUNE ? kDefaultTune : tuneArg;
-  static_assert(!HOT || (MERGE && !SPEC && !FAST && !LDS_NODES && !DF), "HOT is a form of the default kernel's plain-render builds");
   const bool slots = (SLOTS == 2) ? (ex.slotColor != nullptr) : (SLOTS == 1);
-  constexpr bool kFirstInSetup = SLOTS != 0 && MERGE && !SPEC && !FAST && !LDS_NODES && !DF && !HOT;      // (see the cast set-up of the merged SHADE / GEN turn)
   __shared__ float sinTbl[92];
   // the materials a hit is shaded with, when the scene has few (the built-in scenes have 8, test_scene.dae 9): SHADE
   // otherwise waits for two dependent global loads, leaf record then material
@@ -191,15 +173,14 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
   const uint32_t items = n * segs;                 // (host checks that this fits 32 bits)
 
   // ---- lane state ----
-  constexpr bool kPhInNode = !SPEC;
   uint32_t ph = PH_FETCH;      // (SPEC only)
-  uint32_t sample = 0, bounce = 0, node = kPhInNode ? kFetchNode : 0u, pendLeaf = 0;
-  auto inNode = [&]() -> bool { return kPhInNode ? node < numNodes : ph == PH_NODE; };
-  auto inLeaf = [&]() -> bool { return kPhInNode ? (int32_t)node < 0 : ph == PH_LEAF; };
-  auto inShade = [&]() -> bool { return kPhInNode ? node - numNodes < kGenNode - numNodes : ph == PH_SHADE; };
-  auto inGen = [&]() -> bool { return kPhInNode ? node == kGenNode : ph == PH_GEN; };
-  auto inFetch = [&]() -> bool { return kPhInNode ? node == kFetchNode : ph == PH_FETCH; };
-  auto park = [&](uint32_t p) { if (kPhInNode) node = kGenNode + (p - PH_GEN); else ph = p; };      // p = PH_GEN, PH_FETCH or PH_DONE
+  uint32_t sample = 0, bounce = 0, node = Build::phInNode ? kFetchNode : 0u, pendLeaf = 0;
+  auto inNode = [&]() -> bool { return Build::phInNode ? node < numNodes : ph == PH_NODE; };
+  auto inLeaf = [&]() -> bool { return Build::phInNode ? (int32_t)node < 0 : ph == PH_LEAF; };
+  auto inShade = [&]() -> bool { return Build::phInNode ? node - numNodes < kGenNode - numNodes : ph == PH_SHADE; };
+  auto inGen = [&]() -> bool { return Build::phInNode ? node == kGenNode : ph == PH_GEN; };
+  auto inFetch = [&]() -> bool { return Build::phInNode ? node == kFetchNode : ph == PH_FETCH; };
+  auto park = [&](uint32_t p) { if (Build::phInNode) node = kGenNode + (p - PH_GEN); else ph = p; };      // p = PH_GEN, PH_FETCH or PH_DONE
   uint32_t pend1 = 0xFFFFFFFFu, pend1Node = 0, specNodes = 0;       // SPEC: the primitive test the lane has walked past, where it was found, box tests made since (STATS)
   float prow = 0.f, pcol = 0.f;
   Rng rng; rng.s0 = rng.s1 = 0;
@@ -217,11 +198,9 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
   // A build for seven waves per SIMD must fit seven workgroups' LDS into a compute unit: it keeps 21 words, not 23 - the pixel's
   // (row, col) (1, 2) are fetched again from the stream's compact copy by every GEN instead (8 bytes, an L2 hit: the lane's 64
   // samples of one (pixel, segment) unit read the same address).
-  constexpr bool kCoordsFromStream = WAVES_PER_SIMD >= 7;
-  constexpr uint32_t kColdWords = kCoordsFromStream ? 21u : 23u;
-  __shared__ uint32_t coldLds[kColdWords * BLOCK];   // + the last hit's leaf and distance (6, 7) + the path state (8..22)
-  auto coldU = [&](uint32_t w) -> uint32_t& { return coldLds[((kCoordsFromStream && w > 2u) ? w - 2u : w) * BLOCK + threadIdx.x]; };
-  auto coldF = [&](uint32_t w) -> float& { return reinterpret_cast<float*>(coldLds)[((kCoordsFromStream && w > 2u) ? w - 2u : w) * BLOCK + threadIdx.x]; };
+  __shared__ uint32_t coldLds[Build::coldWords * BLOCK];   // + the last hit's leaf and distance (6, 7) + the path state (8..22)
+  auto coldU = [&](uint32_t w) -> uint32_t& { return coldLds[((Build::coordsFromStream && w > 2u) ? w - 2u : w) * BLOCK + threadIdx.x]; };
+  auto coldF = [&](uint32_t w) -> float& { return reinterpret_cast<float*>(coldLds)[((Build::coordsFromStream && w > 2u) ? w - 2u : w) * BLOCK + threadIdx.x]; };
 
   auto getPix = [&]() -> uint32_t { return coldU(0); };
   // Path state that only SHADE / GEN / FETCH touch - the RNG, radiance, throughput, normal, bounce and sample
@@ -321,7 +300,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           const mi_trace_result* res = rays + entry;
           if (ex.coords) { const float2 pc = ex.coords[entry]; prow = pc.x; pcol = pc.y; }
           else { prow = res->u; pcol = res->v; }
-          coldU(0) = entry; if (!kCoordsFromStream) { coldF(1) = prow; coldF(2) = pcol; }
+          coldU(0) = entry; if (!Build::coordsFromStream) { coldF(1) = prow; coldF(2) = pcol; }
           if (seg == 0) { coldF(3) = res->rgb.x; coldF(4) = res->rgb.y; coldF(5) = res->rgb.z; }
           else { coldF(3) = 0.f; coldF(4) = 0.f; coldF(5) = 0.f; }           // a later segment's own partial sum
           rng_seed_pixel_segment(rng, sc.rngSeed, prow, pcol, seg);
@@ -465,7 +444,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           }
         }
       };
-      auto coldLanes = [&]() -> unsigned long long { return __ballot(kPhInNode ? node - hotBytes < numNodes - hotBytes : (ph == PH_NODE && node >= hotBytes)); };      // (hotBytes <= numNodes: one range compare)
+      auto coldLanes = [&]() -> unsigned long long { return __ballot(Build::phInNode ? node - hotBytes < numNodes - hotBytes : (ph == PH_NODE && node >= hotBytes)); };      // (hotBytes <= numNodes: one range compare)
       for (;;) {
         const uint32_t stay = cN;
         const uint32_t cP = SPEC ? (uint32_t)__popcll(__ballot(pend1 != 0xFFFFFFFFu)) : 0u;
@@ -633,9 +612,8 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           // Plain renders only: the NIF-slot builds of this turn have no registers left for the record (with it the 256-thread build on plain
           // records spills eight vector registers to scratch, the pre-rotated one two more scalars - profiles/r14_k1w_leaf_frame.txt); they
           // keep the computed frame.
-          constexpr bool kLeafFrame = !BARY && SLOTS == 0;
           f3 frX = mk(0.f, 0.f, 0.f), frY = frX;
-          if constexpr (kLeafFrame) {
+          if constexpr (Build::leafFrame) {
             if (sc.leafNormalsOrFrames != nullptr) {
               // (uniform base + 32-bit byte offset, as for the nodes: an array of fewer than 2^26 records of 32 bytes)
               const GLeafFrame* fr = reinterpret_cast<const GLeafFrame*>(reinterpret_cast<const char*>(sc.leafNormalsOrFrames) + (hit.leaf << 5));
@@ -656,7 +634,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           if (mat.type == 0) {
             const float u1 = rng_uniform01(rng);
             const float u2 = rng_uniform01(rng);
-            if constexpr (kLeafFrame) {
+            if constexpr (Build::leafFrame) {
               f3 xb = frX, yb = frY;
               if ((frX.x == 0.f) & (frX.y == 0.f) & (frX.z == 0.f)) diffuse_frame(nrm, xb, yb);
               d = diffuse_in_frame(nrm, xb, yb, u1, u2, sinTbl);
@@ -729,7 +707,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
       }
       if (slots) pushEscaped(envRay, envSlot);
       if (genNow || wasGen) {
-        if constexpr (kCoordsFromStream) {
+        if constexpr (Build::coordsFromStream) {
           const uint32_t e = coldU(0);
           if (ex.coords) { const float2 pc = ex.coords[e]; prow = pc.x; pcol = pc.y; } else { prow = rays[e].u; pcol = rays[e].v; }
         } else { prow = coldF(1); pcol = coldF(2); }
@@ -757,7 +735,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
         if (FAST) fast_box_setup(o, inv, oi, slabPad);
         hit.t = kInf; hit.leaf = 0xFFFFFFFFu;
         { uint32_t seen; node = (root_start(sc, o, seen) << 5) + ((HOT && exactSlab) ? sc.exactBase : 0u); if (STATS) cs.nodes += seen; }      // (HOT: a literal-box-test cast walks the region of every node, hot_order.hpp)
-        if (!kPhInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
+        if (!Build::phInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
         // Slot-mode launches (NIF renders), option nif_first_test: the cast's FIRST box test runs here, in the turn that set the cast up,
         // instead of in a NODE turn. In the open scenes an environment light is for, most casts miss the root's box: they take a NODE
         // turn each for that one test - next to the few lanes that walk the mesh, 11 NODE turns per 64 casts at 20 % occupancy in
@@ -765,7 +743,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
         // The same test on the same values as nodeBodyT below, the walk continues from its outcome: nothing a path computes changes.
         // Measured neutral (the walking lanes sit out the SHADE turns instead: 2.1 of them per 64 casts at half occupancy against 1.2):
         // off by default.
-        if constexpr (kFirstInSetup) {
+        if constexpr (Build::firstInSetup) {
           if (slots && ex.firstInSetup && inNode()) {
             const GNode nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + node);
             if (STATS) cs.nodes++;
@@ -887,7 +865,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
           if (FAST) fast_box_setup(o, inv, oi, slabPad);
           hit.t = kInf; hit.leaf = 0xFFFFFFFFu;
           { uint32_t seen; node = (root_start(sc, o, seen) << 5) + ((HOT && exactSlab) ? sc.exactBase : 0u); if (STATS) cs.nodes += seen; }      // (HOT: a literal-box-test cast walks the region of every node, hot_order.hpp)
-          if (!kPhInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
+          if (!Build::phInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
         }
         pathStore();
       }
@@ -900,7 +878,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
       const unsigned long long tq2 = STATS ? __builtin_amdgcn_s_memtime() : 0ull;
       if (inGen()) {
         pathLoad();
-        if constexpr (kCoordsFromStream) {
+        if constexpr (Build::coordsFromStream) {
           const uint32_t e = coldU(0);
           if (ex.coords) { const float2 pc = ex.coords[e]; prow = pc.x; pcol = pc.y; } else { prow = rays[e].u; pcol = rays[e].v; }
         } else { prow = coldF(1); pcol = coldF(2); }
@@ -925,7 +903,7 @@ __global__ void __launch_bounds__(BLOCK, ((BLOCK == 256 || HOT) && WAVES_PER_SIM
         if (FAST) fast_box_setup(o, inv, oi, slabPad);
         hit.t = kInf; hit.leaf = 0xFFFFFFFFu;
         { uint32_t seen; node = (root_start(sc, o, seen) << 5) + ((HOT && exactSlab) ? sc.exactBase : 0u); if (STATS) cs.nodes += seen; }      // (HOT: a literal-box-test cast walks the region of every node, hot_order.hpp)
-        if (!kPhInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
+        if (!Build::phInNode) ph = (numNodes > 0) ? PH_NODE : PH_SHADE;      // (node = 0 of an empty tree is its end)
         pathStore();
       }
       casts += cG;

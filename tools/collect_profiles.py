@@ -80,12 +80,14 @@ if PROBE:
 bench = json.loads((SRC / "bench.json").read_text())
 (DST / f"{TAG}_bench.json").write_text(json.dumps(bench, indent=1))
 report = list(probe_lines)
-for tag, kern in (("c2", "path_trace_wavefront_kernel<false"), ("c3", "path_trace_wavefront_kernel<false"), ("spp16", "path_trace_wavefront_kernel<false"), ("nif", "nif_asm_kernel" if TAG >= "r05" else "nif_mlp_kernel"), ("nif_w6", "nif_mlp_kernel")):
+# (K1w's builds are named, csrc/k1w_builds.hpp: these three sets render a scene without vertex normals with the default options - K1wPlainRot, or K1wHotRot where hot_nodes = auto stages a prefix)
+K1W = "path_trace_wavefront_kernel<mi::K1w"
+for tag, kern in (("c2", K1W), ("c3", K1W), ("spp16", K1W), ("nif", "nif_asm_kernel" if TAG >= "r05" else "nif_mlp_kernel"), ("nif_w6", "nif_mlp_kernel")):
     if tag == "nif_w6" and not (SRC / tag).exists():
         continue
     c = pmc(tag, kern)
     st = stats(tag)
-    k = next((r for r in st if kern.split("<")[0] in r["Name"] and ("<false" in r["Name"] or "nif" in r["Name"])), None)
+    k = next((r for r in st if kern.split("<")[0] in r["Name"] and "Stats" not in r["Name"]), None)
     line = f"{tag}: "
     if k:
         line += f"{kern.split('<')[0]} avg {float(k['AverageNs']) / 1e6:.3f} ms over {k['Calls']} launches ({k['Percentage']} % of GPU time); "
@@ -111,7 +113,7 @@ for tag, kern in (("c2", "path_trace_wavefront_kernel<false"), ("c3", "path_trac
         casts = bench["value"] * bench["ms_per_step"] * 1e-3
         summary = {
             "workload": ["box", 1440, 1440, 1000, 1],
-            "kernel": "path_trace_wavefront_kernel<false,false,256,6,false,0,true> (SHADE and GEN in one turn; + segment_combine_kernel, not included)",
+            "kernel": (k["Name"] if k else K1W + "...>") + " (SHADE and GEN in one turn; + segment_combine_kernel, not included)",
             "source": f"rocprofv3 --pmc, one group per pass (tools/prof_{TAG}.sh: python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras; profiles/{TAG}_c2_pmc.csv), mean over the timed launches of a pass",
             "source_commit": COMMIT,
             "l1_accesses_per_clk_per_cu": c["TCP_TOTAL_CACHE_ACCESSES_sum"] / CUS / cycles,
