@@ -48,6 +48,11 @@ MI_HD float min_comp(f3 v) {
   const float m = (v.x < v.y) ? v.x : v.y;
   return (m < v.z) ? m : v.z;
 }
+// The smallest of three absolute values as fminf (one v_min3_f32 |a|, |b|, |c| on the device, where min_comp(abs3(..)) is two compare /
+// select pairs serialised on VCC). The same bits as min_comp(abs3(mk(a, b, c))) when no operand is NaN - the operands are absolute values, so
+// a tie is one bit pattern; with a NaN operand fminf returns the other operand where the select chain returns the second. Only for a caller
+// whose result does not depend on the value then: the triangle test's error bound (tri_math.hpp), not offset_origin or roulette_stop.
+MI_HD float min_abs3(float a, float b, float c) { return fminf(fminf(fabsf(a), fabsf(b)), fabsf(c)); }
 
 // precision_utils.hpp:18-25
 constexpr float kMachineEps = 5.9604644775390625e-08f;   // 2^-24

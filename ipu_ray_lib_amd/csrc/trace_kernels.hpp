@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ray_math.h"
+#include "tri_math.hpp"
 #include "leaf_frame.hpp"
 #include "../../include/mi_raylib.h"
 
@@ -107,21 +108,7 @@ __device__ __forceinline__ uint32_t root_start(const DeviceScene& sc, f3 o, uint
   return inside ? 1u : 0u;
 }
 
-struct Shear { uint32_t kz; float sx, sy, sz; };
-
-// Primitives.cpp:5-22. Pure function of the ray, so it is evaluated once per cast instead of once
-// per leaf (Mesh.hpp:89); identical values.
-__device__ __forceinline__ Shear make_shear(f3 d) {
-  Shear s;
-  s.kz = min_index(d);
-  uint32_t kx = s.kz + 1; if (kx == 3) kx = 0;
-  uint32_t ky = kx + 1; if (ky == 3) ky = 0;
-  const float dx = comp(d, kx), dy = comp(d, ky), dz = comp(d, s.kz);
-  s.sx = -dx / dz;
-  s.sy = -dy / dz;
-  s.sz = 1.f / dz;
-  return s;
-}
+// (Shear, make_shear(d), permute_kz and the exact tiers' intersect_triangle: tri_math.hpp, one text for hipcc and g++)
 // The same with the ray's reciprocal direction at hand: 1 / d[kz] is one of its components (the same IEEE division).
 __device__ __forceinline__ Shear make_shear(f3 d, f3 inv) {
   Shear s;
@@ -163,74 +150,6 @@ __device__ __forceinline__ void fast_box_setup(f3 o, f3& inv, f3& oi, float& sla
   slabPad = 4.8e-7f * fmaxf(fmaxf(px ? 0.f : fabsf(oi.x), py ? 0.f : fabsf(oi.y)), pz ? 0.f : fabsf(oi.z));
 }
 
-__device__ __forceinline__ f3 permute_kz(f3 p, uint32_t kz) {
-  // (kx,ky,kz) is the cyclic rotation that puts component kz last. Written as selects: as three early returns
-  // hipcc built divergent regions (exec-mask juggling, ~50 scalar instructions in dependent chains per
-  // primitive test) out of what is six v_cndmask per vector.
-  const bool r1 = kz == 0;   // (1, 2, 0)
-  const bool r2 = kz == 1;   // (2, 0, 1)
-  return mk(r1 ? p.y : (r2 ? p.z : p.x), r1 ? p.z : (r2 ? p.x : p.y), r1 ? p.x : (r2 ? p.y : p.z));
-}
-
-// Mesh.cpp:6-104, tFar = inf as passed by Mesh.hpp:92. Returns t (0 = miss). DF = the reference's compile-time variant
-// ALLOW_DOUBLE_FALLBACK=1 (CMakeLists.txt:13,34-41; Mesh.cpp:38-51): when an edge function is exactly zero all three are
-// recomputed from products and differences in binary64 and narrowed to binary32 (v_mul_f64 / v_add_f64 / v_cvt_f32_f64
-// are IEEE operations: the same bits as the host's doubles). DF = false is the reference default.
-// Written without the reference's early returns: every lane runs every operation and the verdicts are combined at the
-// end. Identical values for every input, NaNs included: each early return of Mesh.cpp is a predicate that is evaluated
-// here on the same operands (a lane that would have returned early computes on - with whatever its operands give, an
-// infinite or NaN 1/det included - and is then told 0). With tFar = +inf (Mesh.hpp:90-92) tFar*det is -inf (det<0) or
-// +inf (det>0), and "tScaled < -inf" / "tScaled > +inf" are false for every float including NaN, so those two
-// comparisons of Mesh.cpp:62-66 drop out exactly. Measured against the early-return form: -1.4 % frame time (hipcc
-// turns early returns into nested exec regions whose merges cost 45 register moves per test).
-// PRE: p0, p1, p2 and o arrive with their components already rotated for sh.kz (GLeafRot)
-template <bool DF = false, bool PRE = false>
-__device__ __forceinline__ float intersect_triangle(f3 p0, f3 p1, f3 p2, f3 o, const Shear& sh, float& b0, float& b1, float& b2) {
-  f3 p0t = PRE ? p0 - o : permute_kz(p0 - o, sh.kz), p1t = PRE ? p1 - o : permute_kz(p1 - o, sh.kz), p2t = PRE ? p2 - o : permute_kz(p2 - o, sh.kz);
-  p0t.x += sh.sx * p0t.z; p0t.y += sh.sy * p0t.z;
-  p1t.x += sh.sx * p1t.z; p1t.y += sh.sy * p1t.z;
-  p2t.x += sh.sx * p2t.z; p2t.y += sh.sy * p2t.z;
-  float e0 = p1t.x * p2t.y - p1t.y * p2t.x;
-  float e1 = p2t.x * p0t.y - p2t.y * p0t.x;
-  float e2 = p0t.x * p1t.y - p0t.y * p1t.x;
-  if constexpr (DF) {
-    if (e0 == 0.0f || e1 == 0.0f || e2 == 0.0f) {             // Mesh.cpp:40-50, operation for operation
-      const double p2txp1ty = (double)p2t.x * (double)p1t.y;
-      const double p2typ1tx = (double)p2t.y * (double)p1t.x;
-      e0 = (float)(p2typ1tx - p2txp1ty);
-      const double p0txp2ty = (double)p0t.x * (double)p2t.y;
-      const double p0typ2tx = (double)p0t.y * (double)p2t.x;
-      e1 = (float)(p0typ2tx - p0txp2ty);
-      const double p1txp0ty = (double)p1t.x * (double)p0t.y;
-      const double p1typ0tx = (double)p1t.y * (double)p0t.x;
-      e2 = (float)(p1typ0tx - p1txp0ty);
-    }
-  }
-  // (bitwise, not short-circuit: with || hipcc rebuilds the early returns as nested exec regions; -0.4 % frame time)
-#define MI_OR |
-#define MI_AND &
-  bool miss = ((e0 < 0) MI_OR (e1 < 0) MI_OR (e2 < 0)) MI_AND ((e0 > 0) MI_OR (e1 > 0) MI_OR (e2 > 0));
-  const float det = e0 + e1 + e2;
-  miss = miss MI_OR (det == 0);
-  p0t.z *= sh.sz; p1t.z *= sh.sz; p2t.z *= sh.sz;
-  const float tScaled = e0 * p0t.z + e1 * p1t.z + e2 * p2t.z;
-  miss = miss MI_OR ((det < 0.f) MI_AND (tScaled >= 0.f)) MI_OR ((det > 0.f) MI_AND (tScaled <= 0.f));
-  const float invDet = 1 / det;
-  b0 = e0 * invDet; b1 = e1 * invDet; b2 = e2 * invDet;
-  const float t = tScaled * invDet;
-  const float maxZt = min_comp(abs3(mk(p0t.z, p1t.z, p2t.z)));
-  const float deltaZ = gamma_n(3) * maxZt;
-  const float maxXt = min_comp(abs3(mk(p0t.x, p1t.x, p2t.x)));
-  const float maxYt = min_comp(abs3(mk(p0t.y, p1t.y, p2t.y)));
-  const float deltaX = gamma_n(5) * (maxXt + maxZt);
-  const float deltaY = gamma_n(5) * (maxYt + maxZt);
-  const float deltaE = 2 * (gamma_n(2) * maxXt * maxYt + deltaY * maxXt + deltaX * maxYt);
-  const float maxE = min_comp(abs3(mk(e0, e1, e2)));
-  const float deltaT = 3 * (gamma_n(3) * maxE * maxZt + deltaE * maxZt + deltaZ * maxE) * fabsf(invDet);
-  miss = miss MI_OR (t <= deltaT);
-  return miss ? 0.f : t;
-}
-
 // The TOLERANCE tier's triangle test (scene option "fast" = 1; never the default, never the headline): the same test
 // with floating-point contraction allowed (the shear, the edge functions, tScaled and the error bound fuse into FMAs)
 // and the determinant's reciprocal taken with v_rcp_f32 (1 ulp) instead of the correctly rounded division. t, the
@@ -238,6 +157,8 @@ __device__ __forceinline__ float intersect_triangle(f3 p0, f3 p1, f3 p2, f3 o, c
 // tested as a tolerance (tests/test_gpu_parity.py, test_fast_tier_*), not as parity.
 __device__ __forceinline__ float intersect_triangle_fast(f3 p0, f3 p1, f3 p2, f3 o, const Shear& sh, float& b0, float& b1, float& b2) {
 #pragma clang fp contract(fast)
+#define MI_OR |
+#define MI_AND &
   f3 p0t = permute_kz(p0 - o, sh.kz), p1t = permute_kz(p1 - o, sh.kz), p2t = permute_kz(p2 - o, sh.kz);
   p0t.x = __builtin_fmaf(sh.sx, p0t.z, p0t.x); p0t.y = __builtin_fmaf(sh.sy, p0t.z, p0t.y);
   p1t.x = __builtin_fmaf(sh.sx, p1t.z, p1t.x); p1t.y = __builtin_fmaf(sh.sy, p1t.z, p1t.y);
@@ -254,14 +175,14 @@ __device__ __forceinline__ float intersect_triangle_fast(f3 p0, f3 p1, f3 p2, f3
   const float invDet = __builtin_amdgcn_rcpf(det);
   b0 = e0 * invDet; b1 = e1 * invDet; b2 = e2 * invDet;
   const float t = tScaled * invDet;
-  const float maxZt = min_comp(abs3(mk(p0t.z, p1t.z, p2t.z)));
+  const float maxZt = min_abs3(p0t.z, p1t.z, p2t.z);
   const float deltaZ = gamma_n(3) * maxZt;
-  const float maxXt = min_comp(abs3(mk(p0t.x, p1t.x, p2t.x)));
-  const float maxYt = min_comp(abs3(mk(p0t.y, p1t.y, p2t.y)));
+  const float maxXt = min_abs3(p0t.x, p1t.x, p2t.x);
+  const float maxYt = min_abs3(p0t.y, p1t.y, p2t.y);
   const float deltaX = gamma_n(5) * (maxXt + maxZt);
   const float deltaY = gamma_n(5) * (maxYt + maxZt);
   const float deltaE = 2 * __builtin_fmaf(gamma_n(2) * maxXt, maxYt, __builtin_fmaf(deltaY, maxXt, deltaX * maxYt));
-  const float maxE = min_comp(abs3(mk(e0, e1, e2)));
+  const float maxE = min_abs3(e0, e1, e2);
   const float deltaT = 3 * __builtin_fmaf(gamma_n(3) * maxE, maxZt, __builtin_fmaf(deltaE, maxZt, deltaZ * maxE)) * fabsf(invDet);
   miss = miss MI_OR (t <= deltaT);
 #undef MI_OR
@@ -392,10 +313,11 @@ __device__ __forceinline__ bool prim_hit(const Rec& L, f3 o, const Dir& d, const
   bool cand;
   if (leaf_kind(L) == LEAF_TRI) {
     const f3 p0 = mk(L.f[0], L.f[1], L.f[2]), p1 = mk(L.f[3], L.f[4], L.f[5]), p2 = mk(L.f[6], L.f[7], L.f[8]);
-    if constexpr (ROT) t = intersect_triangle<DF, true>(p0, p1, p2, permute_kz(o, sh.kz), sh, b0, b1, b2);
+    // (POS: the acceptance below holds t > 0 and t < tCur <= +inf for every caller - include/mi_raylib.h says so of every query family)
+    if constexpr (ROT) t = intersect_triangle<DF, true, true>(p0, p1, p2, permute_kz(o, sh.kz), sh, b0, b1, b2);
     else if constexpr (FAST) t = intersect_triangle_fast(p0, p1, p2, o, sh, b0, b1, b2);
-    else t = intersect_triangle<DF>(p0, p1, p2, o, sh, b0, b1, b2);
-    cand = t > 0.f && t < kInf;                 // Mesh.hpp:93
+    else t = intersect_triangle<DF, false, true>(p0, p1, p2, o, sh, b0, b1, b2);
+    cand = t > 0.f;                             // Mesh.hpp:93 (its t < inf is t < tCur below: tCur is at most +inf, and a NaN tCur fails both)
   } else {
     const f3 dir = ray_dir(d);
     if (leaf_kind(L) == LEAF_SPHERE) t = intersect_sphere(L, o, dir, tMin);    // Failed() carries t = 0, rejected by t > tMin

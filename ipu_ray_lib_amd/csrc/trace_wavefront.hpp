@@ -489,20 +489,17 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
               if (STATS) cs.leaves++;
               const GLeaf L = sc.leaves[pend1];
               float t, b0 = 0.f, b1 = 0.f, b2 = 0.f;
-              bool cand;
               const uint32_t kind = leaf_kind(L);
               if (kind == LEAF_TRI) {
+                // (POS, and no candidate test of its own: Mesh.hpp:93's t > 0 && t < inf is the acceptance below - hit.t is +inf or an accepted finite t)
                 t = FAST ? intersect_triangle_fast(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), o, sh, b0, b1, b2)
-                       : intersect_triangle<DF>(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), o, sh, b0, b1, b2);
-                cand = t > 0.f && t < kInf;
+                       : intersect_triangle<DF, false, true>(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), o, sh, b0, b1, b2);
               } else if (kind == LEAF_SPHERE) {
                 t = intersect_sphere(L, o, d, 0.f);
-                cand = true;
               } else {
                 t = intersect_disc(L, o, d);
-                cand = true;
               }
-              if (cand && t > 0.f && t < hit.t) {
+              if (t > 0.f && t < hit.t) {
                 // a closer hit: everything walked since is void, the walk resumes behind the primitive's node with it
                 hit.t = t; hit.leaf = pend1; hit.b0 = b0; hit.b1 = b1; hit.b2 = b2;
                 node = pend1Node;
@@ -542,27 +539,25 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
               L = *reinterpret_cast<const GLeaf*>(reinterpret_cast<const char*>(sc.leaves) + (recNode << 1));
             }
             float t, b0 = 0.f, b1 = 0.f, b2 = 0.f;
-            bool cand;
             // HOT: the private records carry the node that follows the leaf - a pre-rotated block in its first word (kind in the low five
             // bits, the successor's byte offset above), a plain record where the walk never reads (triBase: the same 16-byte load as primID)
             const uint32_t kind = (HOT && ROT) ? (L.type & 31u) : leaf_kind(L);
             if constexpr (HOT) node = ROT ? (L.type & ~31u) : L.triBase;
             if (STATS) { const unsigned long long qm = __ballot(kind != LEAF_TRI); itQ += qm ? 1u : 0u; lnQ += (uint32_t)__popcll(qm); }
             if (kind == LEAF_TRI) {
-              if constexpr (ROT) t = intersect_triangle<DF, true>(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), permute_kz(o, sh.kz), sh, b0, b1, b2);
+              // (POS: `closer` below accepts t only when t > 0 && t < hit.t, and hit.t is +inf or an accepted finite t - tri_math.hpp;
+              // Mesh.hpp:93's t > 0 && t < inf is that same acceptance, so the triangle has no candidate test of its own)
+              if constexpr (ROT) t = intersect_triangle<DF, true, true>(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), permute_kz(o, sh.kz), sh, b0, b1, b2);
               else
               t = FAST ? intersect_triangle_fast(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), o, sh, b0, b1, b2)
-                       : intersect_triangle<DF>(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), o, sh, b0, b1, b2);
-              cand = t > 0.f && t < kInf;
+                       : intersect_triangle<DF, false, true>(mk(L.f[0], L.f[1], L.f[2]), mk(L.f[3], L.f[4], L.f[5]), mk(L.f[6], L.f[7], L.f[8]), o, sh, b0, b1, b2);
             } else if (kind == LEAF_SPHERE) {
               t = intersect_sphere(L, o, d, 0.f);
-              cand = true;
             } else {
               t = intersect_disc(L, o, d);
-              cand = true;
             }
             // (five selects on one mask: as an if-block hipcc copies the five values out, branches, and copies them back)
-            const bool closer = cand & (t > 0.f) & (t < hit.t);
+            const bool closer = (t > 0.f) & (t < hit.t);
             hit.t = closer ? t : hit.t; hit.leaf = closer ? atLeaf : hit.leaf;
             if constexpr (BARY) { hit.b0 = closer ? b0 : hit.b0; hit.b1 = closer ? b1 : hit.b1; hit.b2 = closer ? b2 : hit.b2; }
           }
