@@ -464,6 +464,71 @@ int mi_box_fill_device(mi_scene* scene, const void* d_boxes, const uint64_t* d_o
 int mi_box_offsets(mi_scene* scene, const mi_box* boxes, uint64_t* offsets /* n + 1 */, size_t n);
 int mi_box_fill(mi_scene* scene, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n);
 
+/* Triangle queries: the primitives of the scene's CURRENT BVH that TOUCH each of n caller-supplied triangles (q0, q1, q2) - a face of
+ * another mesh (Embree's rtcCollide, trimesh / FCL's collision manager, libigl's intersection tests), a facet of a cutting surface.
+ * A caller with a triangle had to ask mi_box_* about its bounding box and filter with a triangle-triangle test of their own; a
+ * diagonal triangle's box lists many times what the triangle touches. Whether there is one (MI_TRI_ANY), how many (MI_TRI_COUNT), or
+ * which: two steps as for the box lists - the offsets of the triangles' segments, then the fill of a buffer the caller sized from them.
+ * Touching is CLOSED everywhere: contact counts. Queries see SURFACES, as everywhere in this library: a triangle wholly inside a
+ * sphere, away from its shell, touches nothing.
+ * The triangle: a[3], b[3], c[3] = q0, q1, q2, 36 bytes at a 4-byte aligned address: a float32 [n, 3, 3] array (vertices[faces]) IS a
+ * batch. The record has the layout of mi_overlap: the ids as mi_point_hit carries them, flags = 0, tri = the index of the query the
+ * record belongs to, reserved = 0. The empty record is {MI_INVALID_PRIM, MI_INVALID_GEOM, MI_FLAG_ESCAPED, tri, 0}.
+ * Arithmetic: binary32, one rounding per operation in the order written below, no contraction, correctly rounded divide and sqrt;
+ * a dot product is (x x' + y y') + z z', cross(a, v) = (a.y v.z - a.z v.y, a.z v.x - a.x v.z, a.x v.y - a.y v.x); min and max are
+ * compare / select pairs (a < b ? a : b, a > b ? a : b). Every separation is a strict compare that a NaN fails: a NaN never separates,
+ * and a query so large that its products overflow errs towards listing. One definition (ipu_ray_lib_amd/csrc/contact_math.hpp) serves
+ * the kernels and the host twins (mi_scene_host.h), which return the same bytes.
+ * Validity: a triangle with a coordinate that is NaN or infinite is not walked and finds nothing; so does an empty scene. A collapsed
+ * query (a segment, a point) is legal.
+ * The walk is the stackless preorder walk of the box queries. qmn, qmx = the per-axis select-min and select-max of the query's
+ * vertices ((q0 ? q1) ? q2). A node nd is entered when nd.min <= qmx && nd.max >= qmn on all three axes (compares, no arithmetic),
+ * else passed: the visited set is a function of the query's bounds alone (no plane test at the nodes). At a leaf so reached the
+ * primitive is tested; MI_TRI_ANY stops at the first one that touches.
+ * Every primitive test starts with the primitive's OWN bounds [mn, mx] - those mi_box_* defines for that kind of primitive - against
+ * [qmn, qmx], in the same compares: not touching unless mn <= qmx && mx >= qmn on all axes.
+ * Scene triangle (a, b, c): a separating-axis test of 17 axes, relative to q0. u0 = a - q0, u1 = b - q0, u2 = c - q0; v0 = (0, 0, 0),
+ *   v1 = q1 - q0, v2 = q2 - q0. e0 = u1 - u0, e1 = u2 - u1, e2 = u0 - u2; f0 = v1, f1 = v2 - v1, f2 = -v2. nT = cross(e0, e1),
+ *   nQ = cross(f0, f1). The axes, in this order: nQ; nT; cross(e_i, f_j) for i = 0..2 (outer), j = 0..2 (inner); cross(nT, e_i) for
+ *   i = 0..2; cross(nQ, f_j) for j = 0..2. For an axis x: pT_i = dot(x, u_i), pQ_0 = 0.f, pQ_j = dot(x, v_j); x separates exactly
+ *   when pT_i > pQ_j for all nine pairs or pT_i < pQ_j for all nine pairs. The triangles touch when no axis separates. The last six
+ *   axes are what decides coplanar pairs. A zero axis has all projections 0 and separates nothing, so a collapsed triangle errs
+ *   towards listing: nothing is special-cased.
+ * Sphere (centre c, radius, r2 = radius radius as the scene holds it): dmin2 = dot(d, d), d = c - q, q = mi_point_query's closest
+ *   point of the triangle (q0, q1, q2) to c; dmax2 = the select-max ((d_0 ? d_1) ? d_2) of d_i = dot(q_i - c, q_i - c). Touching when
+ *   !(dmin2 > r2) && !(dmax2 < r2): the shell is reached from outside and from inside.
+ * Disc (centre c, normal n as given, r2): CONSERVATIVE, as for boxes - three necessary conditions that must all hold. The disc's
+ *   tight bounds (mi_box_*'s) meet [qmn, qmx]. The triangle meets the plane: s_i = dot(n, q_i - c), not all three > 0 and not all
+ *   three < 0. The triangle meets the ball: !(dmin2 of c > r2). No touching disc is missed, up to the rounding of these operations; a
+ *   triangle that passes the rim may be listed without touching it. An exact disc test is not offered.
+ * Order: records are sorted by the key (geom_id, prim_id), ascending; keys are unique within a query. This IS the definition: a
+ * segment shorter than the triangle's count holds the len smallest keys, and a list is the same bytes after a refit, a rebuild or
+ * mi_scene_set_geometry of the same contents.
+ * mi_tri_query_device: d_tris = n mi_tri, d_out = n uint8_t, 1 = a primitive touches the triangle (MI_TRI_ANY; the bytes need no
+ *   alignment) or n uint32_t counts (MI_TRI_COUNT), DEVICE memory.
+ * mi_tri_offsets_device / mi_tri_fill_device: offsets, segments, the cut at capacity (NO record at an index >= capacity is ever
+ *   written and none outside the segment), a decreasing pair = an empty segment, which is not walked, caller-made offsets (K i = the K
+ *   smallest keys of every triangle, padded), overlapping segments (unspecified records inside them) and the form (a max-heap inside
+ *   the segment, heap-sorted in place) are mi_box_offsets_device's and mi_box_fill_device's, with d_hits = `capacity` mi_contact.
+ * Host entries: the same on HOST buffers, synchronous, in batches of mi_scene_set_ray_batch triangles; offsets and the `tri` field are
+ *   global across batches (`tri` is the index modulo 2^32). The fill shares mi_list_fill's device staging.
+ * Asynchrony, ordering against update / rebuild / set-geometry, destruction, groups, batches and stream rules: those of mi_box_*.
+ * n == 0 is a no-op. MI_ERR_INVALID_ARG, before any device work and without reading the scene: a null scene or buffer, an unknown kind
+ * ("unknown triangle kind"), triangles that are not 4-byte aligned ("triangles must be 4-byte aligned"), counts that are not 4-byte
+ * aligned, offsets that are not 8-byte aligned, hits that are not 16-byte aligned, or more triangles in one launch (host entries: in
+ * one batch) than the 32-bit work index allows (0xFFBFFFFF).
+ * Options: none apply (one kernel, one arithmetic). Counters: nothing is added to casts or paths; under full_stats the box tests are
+ * added to "nodes visited" and the primitive tests to "leaf tests". */
+typedef struct { float a[3], b[3], c[3]; } mi_tri;   /* 36 B, 4-byte aligned: a float32 [n,3,3] array IS a batch */
+typedef struct { uint32_t primID; uint16_t geomID; uint16_t flags; uint32_t tri; uint32_t reserved; } mi_contact;  /* 16 B, layout of mi_overlap */
+enum { MI_TRI_ANY = 0, MI_TRI_COUNT = 1 };
+int mi_tri_query_device(mi_scene* scene, int kind, const void* d_tris, void* d_out, size_t n, void* hip_stream);
+int mi_tri_query(mi_scene* scene, int kind, const mi_tri* tris, void* out, size_t n);
+int mi_tri_offsets_device(mi_scene* scene, const void* d_tris, uint64_t* d_offsets /* n + 1 */, size_t n, void* hip_stream);
+int mi_tri_fill_device(mi_scene* scene, const void* d_tris, const uint64_t* d_offsets, mi_contact* d_hits, size_t capacity, size_t n, void* hip_stream);
+int mi_tri_offsets(mi_scene* scene, const mi_tri* tris, uint64_t* offsets /* n + 1 */, size_t n);
+int mi_tri_fill(mi_scene* scene, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity, size_t n);
+
 /* Geometry updates: new positions for the primitives of a live scene, the topology kept - triangles, geometry list, materials and
  * the BVH's shape - and every BVH box recomputed on the device (a refit: Embree's RTC_BUILD_QUALITY_REFIT commit, OptiX's
  * OPTIX_BUILD_OPERATION_UPDATE). Any pointer may be NULL = keep; a non-NULL array must have exactly the scene's count (a NULL array

@@ -137,6 +137,21 @@ int mi_box_offsets_host(const mi_scene_desc* desc, const mi_box* boxes, uint64_t
 int mi_box_fill_host(const mi_scene_desc* desc, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity,
                      size_t n, uint64_t visits[2]);
 
+/* Triangle queries on the host: the twins of mi_tri_query* / mi_tri_offsets* / mi_tri_fill* (mi_raylib.h, where the contract is
+ * written), over desc->bvh_nodes and desc's arrays as mi_point_query_host reads them, boxes and primitives tested through the code the
+ * kernels run (ipu_ray_lib_amd/csrc/contact_math.hpp). out: n uint8_t (MI_TRI_ANY) or n uint32_t (MI_TRI_COUNT); offsets: n + 1
+ * uint64_t, written by mi_tri_offsets_host (0, then the running total of the triangles' counts) and read by mi_tri_fill_host, which
+ * writes `hits` as the device writes it - the len smallest keys (geom_id, prim_id) of each triangle ascending, then the empty record;
+ * nothing at or past `capacity`, nothing outside a segment, a triangle with an empty segment not walked. No alignment asked. They
+ * return the bytes the device returns; visits (may be NULL) receives {box tests, primitive tests} summed over the n triangles, what the
+ * device adds to "nodes visited" and "leaf tests" under option full_stats. MI_ERR_INVALID_ARG, with the function's name in
+ * mi_host_last_error: a null desc, an unknown kind, a null buffer with n > 0, nodes that are not a depth-first BVH2, a leaf whose
+ * geometry, primitive or vertex index is out of range. */
+int mi_tri_query_host(const mi_scene_desc* desc, int kind, const mi_tri* tris, void* out, size_t n, uint64_t visits[2]);
+int mi_tri_offsets_host(const mi_scene_desc* desc, const mi_tri* tris, uint64_t* offsets /* n + 1 */, size_t n, uint64_t visits[2]);
+int mi_tri_fill_host(const mi_scene_desc* desc, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity,
+                     size_t n, uint64_t visits[2]);
+
 /* Sphere crossings on the host: how often the ray origin + t direction, t_min < t < t_max, crosses the shell of the sphere (centre,
  * radius2 = the squared radius) - 0, 1 or 2 -, from the definition the crossing-count kernels run (mi_count_query / mi_point_sign,
  * mi_raylib.h, where the formula is written; ipu_ray_lib_amd/csrc/cross_math.hpp). The triangle and disc tests of a crossing count

@@ -58,7 +58,13 @@ NEIGHBOUR = np.dtype([("dist2", "<f4"), ("primID", "<u4"), ("geomID", "<u2"), ("
 BOX = np.dtype([("lo", "<f4", (3,)), ("reserved0", "<u4"), ("hi", "<f4", (3,)), ("reserved1", "<u4")])
 OVERLAP = np.dtype([("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("box", "<u4"), ("reserved", "<u4")])
 
+# mi_tri / mi_contact: a triangle query - a float32 [n, 3, 3] array viewed as records - and one record of its list (IpuScene.tri_touches /
+# count_contacts / list_contacts / tri_fill_device)
+TRI = np.dtype([("a", "<f4", (3,)), ("b", "<f4", (3,)), ("c", "<f4", (3,))])
+CONTACT = np.dtype([("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("tri", "<u4"), ("reserved", "<u4")])
+
 assert CROSSING.itemsize == 16 and NEIGHBOUR.itemsize == 16
+assert TRI.itemsize == 36 and CONTACT.itemsize == 16
 assert BOX.itemsize == 32 and OVERLAP.itemsize == 16
 assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
 assert POINT.itemsize == 16 and POINT_HIT.itemsize == 32
@@ -71,6 +77,7 @@ MODE_SHADOW_TRACE, MODE_PATH_TRACE = 0, 1
 QUERY_CLOSEST, QUERY_ANY = 0, 1
 POINT_CLOSEST, POINT_WITHIN = 0, 1
 BOX_ANY, BOX_COUNT = 0, 1
+TRI_ANY, TRI_COUNT = 0, 1
 OVERLAP_CONTAINED = 16      # MI_OVERLAP_CONTAINED: the primitive's own bounds lie inside the box
 SIGN_INSIDE, SIGN_DISTANCE = 0, 1
 # the ray direction of an inside test when none is given (mi_point_sign: no zero component, off the diagonals of axis-aligned boxes)
@@ -201,6 +208,9 @@ def host_lib() -> C.CDLL:
         lib.mi_box_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_box_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_box_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_tri_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_tri_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_tri_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
         lib.mi_sphere_roots_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)]
@@ -313,6 +323,12 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_box_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_box_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         lib.mi_box_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        lib.mi_tri_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_tri_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_tri_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_tri_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_tri_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        lib.mi_tri_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         lib.mi_point_sign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t]
         lib.mi_point_sign_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
@@ -597,6 +613,49 @@ def box_fill_host(desc: SceneDesc, boxes: np.ndarray, offsets: np.ndarray, capac
     visits = (C.c_uint64 * 2)()
     base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
     _check_host(host_lib().mi_box_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
+    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def tri_query_host(desc: SceneDesc, kind: int, tris: np.ndarray):
+    """mi_tri_query_host: the host twin of IpuScene.tri_touches / .count_contacts on desc's arrays and nodes - the same bytes. Returns
+    (out, visits): a bool array (TRI_ANY) or a uint32 array (TRI_COUNT), and {"box_tests", "prim_evals"} summed over the triangles
+    (what the device counts as nodes visited / leaf tests under option full_stats)."""
+    assert tris.dtype == TRI and tris.ndim == 1
+    src = np.ascontiguousarray(tris)
+    out = np.zeros(src.size, np.uint8 if kind == TRI_ANY else np.uint32)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_tri_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
+                                             out.ctypes.data if src.size else None, src.size, visits))
+    return (out.view(np.bool_) if kind == TRI_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def tri_offsets_host(desc: SceneDesc, tris: np.ndarray):
+    """mi_tri_offsets_host: the host twin of IpuScene.tri_offsets - the same uint64 offsets. Returns (offsets, visits)."""
+    assert tris.dtype == TRI and tris.ndim == 1
+    src = np.ascontiguousarray(tris)
+    offsets = np.zeros(src.size + 1, np.uint64)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_tri_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
+    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def tri_fill_host(desc: SceneDesc, tris: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
+    """mi_tri_fill_host: the host twin of IpuScene.tri_fill - the same bytes. Returns (recs, visits): recs is `hits` (a CONTACT
+    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
+    nothing at or past `capacity` (None: recs.size) is written."""
+    assert tris.dtype == TRI and tris.ndim == 1
+    src = np.ascontiguousarray(tris)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    assert offsets.ndim == 1 and offsets.size == src.size + 1
+    if hits is None:
+        size = int(offsets.max()) if capacity is None else int(capacity)
+        hits = np.zeros(max(size, 1), CONTACT)[:size]
+    assert hits.dtype == CONTACT and hits.flags["C_CONTIGUOUS"]
+    capacity = hits.size if capacity is None else int(capacity)
+    assert 0 <= capacity <= hits.size
+    visits = (C.c_uint64 * 2)()
+    base = hits.ctypes.data if hits.size else np.zeros(1, CONTACT).ctypes.data
+    _check_host(host_lib().mi_tri_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
     return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
 
 
@@ -1211,6 +1270,105 @@ class IpuScene:
         lo = torch.stack(torch.meshgrid(axes[0][:-1], axes[1][:-1], axes[2][:-1], indexing="ij"), dim=-1).reshape(-1, 3)
         hi = torch.stack(torch.meshgrid(axes[0][1:], axes[1][1:], axes[2][1:], indexing="ij"), dim=-1).reshape(-1, 3)
         return self.box_any(lo, hi).reshape(nx, ny, nz)
+
+    # -- triangle queries (mi_tri_query*, mi_tri_offsets*, mi_tri_fill*): every primitive that touches each triangle, by (geomID, primID) --
+    def _tri_query_host(self, kind: int, tris: np.ndarray, out: np.ndarray) -> np.ndarray:
+        src = self._source(tris, TRI)
+        self._check(self._lib.mi_tri_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
+        return out
+
+    def tri_touches(self, tris: np.ndarray) -> np.ndarray:
+        """Whether some primitive touches each triangle (a TRI array, host memory; contact counts): a bool array. Synchronous;
+        batched by setRayBatch."""
+        return self._tri_query_host(TRI_ANY, tris, aligned_bytes(tris.size)).view(np.bool_)
+
+    def count_contacts(self, tris: np.ndarray) -> np.ndarray:
+        """How many primitives touch each triangle (a TRI array, host memory): a uint32 array."""
+        return self._tri_query_host(TRI_COUNT, tris, np.zeros(tris.size, np.uint32))
+
+    def tri_offsets(self, tris: np.ndarray) -> np.ndarray:
+        """mi_tri_offsets: a uint64 array of tris.size + 1 offsets - 0, then the running total of count_contacts(tris)."""
+        return self._offsets_host(self._lib.mi_tri_offsets, self._source(tris, TRI))
+
+    def tri_fill(self, tris: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
+        """mi_tri_fill: the primitives touching triangle i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (a
+        CONTACT array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
+        (None: hits.size) is written."""
+        return self._fill_host(self._lib.mi_tri_fill, CONTACT, self._source(tris, TRI), offsets, hits, capacity)
+
+    def list_contacts(self, tris: np.ndarray):
+        """Every primitive that touches each triangle (a TRI array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs a
+        CONTACT array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are triangle i's primitives in ascending order of
+        (geomID, primID). Synchronous; batched by setRayBatch."""
+        return self._all_lists(self.tri_offsets, self.tri_fill, CONTACT, tris)
+
+    def first_contacts(self, tris: np.ndarray, k: int) -> np.ndarray:
+        """The k smallest (geomID, primID) of the primitives touching each triangle: a CONTACT array [n, k]; triangles with fewer
+        are padded with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
+        return self._first_k(self.tri_fill, CONTACT, tris, k)
+
+    def tri_query_device(self, kind: int, d_tris: int, d_out: int, n: int, stream: int = 0):
+        """mi_tri_query_device on device pointers (n TRI records in, n bytes or n uint32 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_tri_query_device(self._h, int(kind), C.c_void_p(d_tris), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
+
+    def tri_offsets_device(self, d_tris: int, d_offsets: int, n: int, stream: int = 0):
+        """mi_tri_offsets_device on device pointers (n TRI records in, n + 1 uint64 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_tri_offsets_device(self._h, C.c_void_p(d_tris), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
+
+    def tri_fill_device(self, d_tris: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
+        """mi_tri_fill_device on device pointers (n TRI records and n + 1 uint64 in, `capacity` CONTACT records out), asynchronous
+        on `stream`."""
+        self._check(self._lib.mi_tri_fill_device(self._h, C.c_void_p(d_tris), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
+                                                 int(n), C.c_void_p(stream)))
+
+    @staticmethod
+    def _torch_tris(what, tris):
+        import torch
+        t = tris.to(torch.float32)
+        if t.ndim != 3 or t.shape[1:] != (3, 3) or not t.is_cuda:
+            raise ValueError(f"{what}: triangles must be an [N, 3, 3] tensor on a GPU")
+        return t.contiguous(), t.shape[0]      # [N, 3, 3] = n mi_tri
+
+    @staticmethod
+    def _torch_mesh(what, vertices, faces):
+        import torch
+        if vertices.ndim != 2 or vertices.shape[1] != 3 or faces.ndim != 2 or faces.shape[1] != 3 or not vertices.is_cuda or faces.device != vertices.device:
+            raise ValueError(f"{what}: vertices [V, 3] and faces [F, 3] must be tensors on one GPU")
+        return vertices.to(torch.float32)[faces.to(torch.int64)]      # [F, 3, 3]: the gather is the batch
+
+    def tri_any(self, tris):
+        """Torch convenience over mi_tri_query_device (TRI_ANY): a float32 device tensor of shape [N, 3, 3] (vertices[faces]),
+        enqueued on torch.cuda.current_stream(). Returns an [N] bool device tensor: a primitive touches the triangle."""
+        t, n = self._torch_tris("tri_any", tris)
+        return self._torch_flags(t, n, self.tri_query_device, TRI_ANY)
+
+    def tri_count(self, tris):
+        """The same for TRI_COUNT: an [N] int32 device tensor, the number of primitives touching each triangle."""
+        import torch
+        t, n = self._torch_tris("tri_count", tris)
+        out = torch.empty(n, dtype=torch.int32, device=t.device)
+        self.tri_query_device(TRI_COUNT, t.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(t.device).cuda_stream)
+        return out
+
+    def tri_list(self, tris):
+        """Torch convenience over mi_tri_offsets_device + mi_tri_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 - the
+        words of the CONTACT records: primID, geomID | flags << 16, tri, 0), triangle by triangle in ascending (geomID, primID). It
+        runs the offsets, reads the total with one .item() (the one synchronisation), then allocates and fills."""
+        t, n = self._torch_tris("tri_list", tris)
+        return self._torch_all_lists(self.tri_offsets_device, self.tri_fill_device, t, n, sync_when_empty=False)
+
+    def mesh_contacts(self, vertices, faces):
+        """Mesh against scene: every (face of the mesh, primitive of the scene) pair that touches, as an int64 device tensor [m, 3]
+        of rows (face, geomID, primID), sorted. vertices: float32 [V, 3], faces: integer [F, 3], device tensors; vertices[faces] is
+        gathered on the device and goes through tri_list, on torch.cuda.current_stream(), with no host round trip but the total."""
+        import torch
+        _, recs = self.tri_list(self._torch_mesh("mesh_contacts", vertices, faces))
+        words = recs.to(torch.int64) & 0xFFFFFFFF
+        return torch.stack([words[:, 2], words[:, 1] & 0xFFFF, words[:, 0]], dim=1)
+
+    def collides(self, vertices, faces) -> bool:
+        """Whether any face of the mesh touches the scene (one TRI_ANY launch over vertices[faces], then any())."""
+        return bool(self.tri_any(self._torch_mesh("collides", vertices, faces)).any().item())
 
     # -- crossing counts, inside tests, signed distance (mi_count_query*, mi_point_sign*) -----------------------------------------------
     def count_crossings(self, rays: np.ndarray) -> np.ndarray:

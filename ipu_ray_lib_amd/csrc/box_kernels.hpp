@@ -9,7 +9,7 @@
 //                        accept(leaf index, geomID, contained) is called for each touching primitive; returning true ends the walk.
 //   box_query_kernel     one thread per box: a byte (MI_BOX_ANY: the walk stops at the first accept) or a uint32 count.
 //   box_count_kernel     one thread per box: the count as 64 bits (scan_*_kernel of list_kernels.hpp then runs in place on them).
-//   box_fill_kernel      one thread per box, into the box's OWN segment [offsets[i], offsets[i + 1]) cut at `capacity`. The key
+//   box_fill_kernel      (key_heap_fill, which the triangle queries' fill shares) one thread per box, into the box's OWN segment [offsets[i], offsets[i + 1]) cut at `capacity`. The key
 //                        (geomID, primID) has no spatial bound, so the fill cannot prune: it walks what the count walk walks. The
 //                        segment holds the `len` smallest keys seen so far as a binary MAX-heap (a box routinely holds hundreds of
 //                        primitives, and list_fill_kernel's insertion moves O(len^2) records): appended and sifted up while
@@ -119,6 +119,51 @@ __device__ __forceinline__ void overlap_sift_down(uint4* seg, uint64_t m, const 
   seg[j] = rec;
 }
 
+// The fill of the lists whose key is (geomID, primID) - the box lists here, the triangle queries' contact lists
+// (contact_kernels.hpp): item idx's segment [offsets[idx], offsets[idx + 1]) cut at `capacity` receives the `len` smallest keys,
+// ascending, then the empty record. walk(accept) runs the item's walk - it is not called for an empty segment, so it is also what
+// loads the query - and calls accept(leaf index, geomID, flags) for each touching primitive; `item` is the record's third word.
+template <class Walk>
+__device__ __forceinline__ void key_heap_fill(const DeviceScene& sc, const uint64_t* offsets, void* hits, uint64_t capacity, uint32_t idx, uint32_t item,
+                                              const Walk& walk) {
+  // the segment: [lo, hi) cut at capacity; a decreasing pair, or a start at or past capacity, is an empty one
+  const uint64_t first = offsets[idx], last = offsets[idx + 1];
+  uint64_t len = 0;
+  if (last > first && first < capacity) len = (last < capacity ? last : capacity) - first;
+  if (!len) return;                                                     // (an empty segment: nothing to write, no walk)
+  uint4* seg = reinterpret_cast<uint4*>(hits) + first;                  // every access below is seg[j] with j < len
+  uint64_t held = 0;                                                    // seg[0 .. held) is a max-heap by key, held <= len
+  uint64_t rootKey = 0;                                                 // the key of seg[0] once held > 0: a copy in registers
+  walk([&](uint32_t at, uint32_t geomID, uint32_t flags) {
+    const uint4 rec = overlap_words(sc.leaves[at].primID, geomID, flags, item);
+    const uint64_t key = overlap_key_of(rec);
+    if (held < len) {
+      uint64_t j = held++;                                              // appended, then sifted up: parents smaller than it move down
+      while (j > 0) {
+        const uint64_t p = (j - 1) >> 1;
+        const uint4 parent = seg[p];
+        if (!(key > overlap_key_of(parent))) break;
+        seg[j] = parent;
+        j = p;
+      }
+      seg[j] = rec;
+      if (j == 0) rootKey = key;
+    } else if (key < rootKey) {                                         // full: the largest key kept makes room for a smaller one
+      overlap_sift_down(seg, len, rec);
+      rootKey = overlap_key_of(seg[0]);
+    }
+    return false;
+  });
+  // heap sort in place: the largest key of seg[0 .. m) goes to seg[m - 1], the record that was there is sifted down from the root
+  for (uint64_t m = held; m > 1; --m) {
+    const uint4 top = seg[0], moved = seg[m - 1];
+    seg[m - 1] = top;
+    overlap_sift_down(seg, m - 1, moved);
+  }
+  const uint4 pad = overlap_words(MI_INVALID_PRIM, (uint32_t)MI_INVALID_GEOM, (uint32_t)MI_FLAG_ESCAPED, item);
+  for (uint64_t j = held; j < len; ++j) seg[j] = pad;
+}
+
 // boxBase: what is added to the thread's index for the record's `box` field (the host entry's batches; 0 for the device entry).
 template <bool STATS>
 __global__ void __launch_bounds__(256) box_fill_kernel(DeviceScene sc, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits,
@@ -126,46 +171,11 @@ __global__ void __launch_bounds__(256) box_fill_kernel(DeviceScene sc, const mi_
   const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
   CastStats cs = {0, 0};
   if (idx < n) {
-    // the segment: [lo, hi) cut at capacity; a decreasing pair, or a start at or past capacity, is an empty one
-    const uint64_t first = offsets[idx], last = offsets[idx + 1];
-    uint64_t len = 0;
-    if (last > first && first < capacity) len = (last < capacity ? last : capacity) - first;
-    if (len) {                                                            // (an empty segment: nothing to write, no walk)
+    key_heap_fill(sc, offsets, hits, capacity, idx, boxBase + idx, [&](const auto& accept) {
       f3 lo, hi;
       load_box(boxes, idx, lo, hi);
-      uint4* seg = reinterpret_cast<uint4*>(hits) + first;                // every access below is seg[j] with j < len
-      const uint32_t box = boxBase + idx;
-      uint64_t held = 0;                                                  // seg[0 .. held) is a max-heap by key, held <= len
-      uint64_t rootKey = 0;                                               // the key of seg[0] once held > 0: a copy in registers
-      box_walk<STATS>(sc, lo, hi, cs, [&](uint32_t at, uint32_t geomID, bool contained) {
-        const uint4 rec = overlap_words(sc.leaves[at].primID, geomID, contained ? (uint32_t)MI_OVERLAP_CONTAINED : 0u, box);
-        const uint64_t key = overlap_key_of(rec);
-        if (held < len) {
-          uint64_t j = held++;                                            // appended, then sifted up: parents smaller than it move down
-          while (j > 0) {
-            const uint64_t p = (j - 1) >> 1;
-            const uint4 parent = seg[p];
-            if (!(key > overlap_key_of(parent))) break;
-            seg[j] = parent;
-            j = p;
-          }
-          seg[j] = rec;
-          if (j == 0) rootKey = key;
-        } else if (key < rootKey) {                                       // full: the largest key kept makes room for a smaller one
-          overlap_sift_down(seg, len, rec);
-          rootKey = overlap_key_of(seg[0]);
-        }
-        return false;
-      });
-      // heap sort in place: the largest key of seg[0 .. m) goes to seg[m - 1], the record that was there is sifted down from the root
-      for (uint64_t m = held; m > 1; --m) {
-        const uint4 top = seg[0], moved = seg[m - 1];
-        seg[m - 1] = top;
-        overlap_sift_down(seg, m - 1, moved);
-      }
-      const uint4 pad = overlap_words(MI_INVALID_PRIM, (uint32_t)MI_INVALID_GEOM, (uint32_t)MI_FLAG_ESCAPED, box);
-      for (uint64_t j = held; j < len; ++j) seg[j] = pad;
-    }
+      box_walk<STATS>(sc, lo, hi, cs, [&](uint32_t at, uint32_t geomID, bool contained) { return accept(at, geomID, contained ? (uint32_t)MI_OVERLAP_CONTAINED : 0u); });
+    });
   }
   if constexpr (STATS) flush_stats(sc, 0u, cs, 0u);
 }

@@ -54,15 +54,22 @@ MI_HD bool sat_edge_separates(f3 e, f3 v0, f3 v1, f3 v2, f3 h) {
   return sat_separates(e.x * v0.y - e.y * v0.x, e.x * v1.y - e.y * v1.x, e.x * v2.y - e.y * v2.x, h.x * a.y + h.y * a.x);
 }
 
+// The bounds of the three kinds of primitive (triangle_bounds, sphere_bounds, disc_bounds below, each before the test that defines
+// it): the triangle queries (contact_math.hpp) test a primitive's bounds by the same functions.
+//
 // Triangle (a, b, c). Its bounds are the per-axis minimum and maximum of the vertices (compares only): the box's three axes
 // and CONTAINED are decided by them, exactly. Then: a vertex in the box accepts at once (compares only); otherwise the
 // separating-axis test in centre / half-extent form - cb = 0.5 lo + 0.5 hi, h = 0.5 hi - 0.5 lo, v0 = a - cb, v1 = b - cb,
 // v2 = c - cb, e0 = v1 - v0, e1 = v2 - v1, e2 = v0 - v2 -, the nine edge axes edge by edge (e0, e1, e2), then the plane:
 // n = cross(e0, e1), s = n.v0, r = (h.x |n.x| + h.y |n.y|) + h.z |n.z|, separated when s > r || s < -r. A collapsed
 // triangle has zero axes, which separate nothing: what its bounds and the remaining axes say stands.
+MI_HD void triangle_bounds(f3 a, f3 b, f3 c, f3& mn, f3& mx) {
+  mn = mk(sel_min(sel_min(a.x, b.x), c.x), sel_min(sel_min(a.y, b.y), c.y), sel_min(sel_min(a.z, b.z), c.z));
+  mx = mk(sel_max(sel_max(a.x, b.x), c.x), sel_max(sel_max(a.y, b.y), c.y), sel_max(sel_max(a.z, b.z), c.z));
+}
 MI_HD bool box_touches_triangle(f3 a, f3 b, f3 c, f3 lo, f3 hi, bool* contained) {
-  const f3 mn = mk(sel_min(sel_min(a.x, b.x), c.x), sel_min(sel_min(a.y, b.y), c.y), sel_min(sel_min(a.z, b.z), c.z));
-  const f3 mx = mk(sel_max(sel_max(a.x, b.x), c.x), sel_max(sel_max(a.y, b.y), c.y), sel_max(sel_max(a.z, b.z), c.z));
+  f3 mn, mx;
+  triangle_bounds(a, b, c, mn, mx);
   *contained = box_holds_bounds(mn, mx, lo, hi);
   if (!box_meets_bounds(mn, mx, lo, hi)) return false;
   if (point_in_box(a, lo, hi) || point_in_box(b, lo, hi) || point_in_box(c, lo, hi)) return true;
@@ -82,8 +89,13 @@ MI_HD bool box_touches_triangle(f3 a, f3 b, f3 c, f3 lo, f3 hi, bool* contained)
 // the sphere when it reaches the shell from outside and from inside - dmin2 <= r2 && dmax2 >= r2, dmin2 = point_box_dist2 of
 // the centre, dmax2 = the squared distance of the farthest corner: per axis f = max(|c - lo|, |hi - c|), (fx fx + fy fy) +
 // fz fz. Written as !(dmin2 > r2) && !(dmax2 < r2). The bounds are c - radius and c + radius, one rounded operation each.
+MI_HD void sphere_bounds(f3 c, float radius, f3& mn, f3& mx) {
+  mn = mk(c.x - radius, c.y - radius, c.z - radius);
+  mx = mk(c.x + radius, c.y + radius, c.z + radius);
+}
 MI_HD bool box_touches_sphere(f3 c, float radius, float r2, f3 lo, f3 hi, bool* contained) {
-  const f3 mn = mk(c.x - radius, c.y - radius, c.z - radius), mx = mk(c.x + radius, c.y + radius, c.z + radius);
+  f3 mn, mx;
+  sphere_bounds(c, radius, mn, mx);
   *contained = box_holds_bounds(mn, mx, lo, hi);
   if (!box_meets_bounds(mn, mx, lo, hi)) return false;
   const float dmin2 = point_box_dist2(lo.x, hi.x, lo.y, hi.y, lo.z, hi.z, c);
@@ -104,11 +116,16 @@ MI_HD bool box_touches_sphere(f3 c, float radius, float r2, f3 lo, f3 hi, bool* 
 // No touching disc is missed (up to the rounding of the operations above). A box that passes the disc's rim within its own
 // size may list it although it does not touch: the three conditions can hold together where the plane's part inside the box
 // lies just outside the rim.
-MI_HD bool box_touches_disc(f3 n, f3 c, float r2, f3 lo, f3 hi, bool* contained) {
+MI_HD void disc_bounds(f3 n, f3 c, float r2, f3& mn, f3& mx) {
   const float r = sqrtf(r2), nn = dot(n, n);
   const float tx = 1.f - n.x * n.x / nn, ty = 1.f - n.y * n.y / nn, tz = 1.f - n.z * n.z / nn;
   const f3 ext = mk(r * sqrtf(tx > 0.f ? tx : 0.f), r * sqrtf(ty > 0.f ? ty : 0.f), r * sqrtf(tz > 0.f ? tz : 0.f));
-  const f3 mn = c - ext, mx = c + ext;
+  mn = c - ext;
+  mx = c + ext;
+}
+MI_HD bool box_touches_disc(f3 n, f3 c, float r2, f3 lo, f3 hi, bool* contained) {
+  f3 mn, mx;
+  disc_bounds(n, c, r2, mn, mx);
   *contained = box_holds_bounds(mn, mx, lo, hi);
   if (!box_meets_bounds(mn, mx, lo, hi)) return false;
   const f3 cb = lo * 0.5f + hi * 0.5f, h = hi * 0.5f - lo * 0.5f;

@@ -200,6 +200,26 @@ int mi_box_fill_host(const mi_scene_desc* desc, const mi_box* boxes, const uint6
   return guarded([&] { boxFillHost(*desc, boxes, offsets, hits, capacity, n, visits); });
 }
 
+// Triangle queries: the host twins of mi_tri_query* / mi_tri_offsets* / mi_tri_fill* (tri_query_host.cpp)
+int mi_tri_query_host(const mi_scene_desc* desc, int kind, const mi_tri* tris, void* out, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_tri_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (kind != MI_TRI_ANY && kind != MI_TRI_COUNT) { g_err = "mi_tri_query_host: unknown triangle kind"; return MI_ERR_INVALID_ARG; }
+  if (n && (!tris || !out)) { g_err = "mi_tri_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { triQueryHost(*desc, kind, tris, out, n, visits); });
+}
+
+int mi_tri_offsets_host(const mi_scene_desc* desc, const mi_tri* tris, uint64_t* offsets, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_tri_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!tris || !offsets)) { g_err = "mi_tri_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { triOffsetsHost(*desc, tris, offsets, n, visits); });
+}
+
+int mi_tri_fill_host(const mi_scene_desc* desc, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_tri_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!tris || !offsets || !hits)) { g_err = "mi_tri_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { triFillHost(*desc, tris, offsets, hits, capacity, n, visits); });
+}
+
 // The canonical primitive table of desc's arrays: the host twin of canon_prim_kernel (canon_kernels.hpp, mi_scene_set_geometry*) -
 // the same prefix, the same search and record per canonical index (canon_prims.hpp), the same checks with mi_scene_create's words
 int mi_canonical_prims(const mi_scene_desc* desc, void* out, uint32_t capacity, uint32_t* count) {

@@ -121,6 +121,10 @@ void nearFillHost(const mi_scene_desc& desc, const mi_point* points, const uint6
 void boxQueryHost(const mi_scene_desc& desc, int kind, const mi_box* boxes, void* out, size_t n, uint64_t* visits);
 void boxOffsetsHost(const mi_scene_desc& desc, const mi_box* boxes, uint64_t* offsets, size_t n, uint64_t* visits);
 void boxFillHost(const mi_scene_desc& desc, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t* visits);
+// tri_query_host.cpp: the host twins of mi_tri_query / mi_tri_offsets / mi_tri_fill (the same visits)
+void triQueryHost(const mi_scene_desc& desc, int kind, const mi_tri* tris, void* out, size_t n, uint64_t* visits);
+void triOffsetsHost(const mi_scene_desc& desc, const mi_tri* tris, uint64_t* offsets, size_t n, uint64_t* visits);
+void triFillHost(const mi_scene_desc& desc, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity, size_t n, uint64_t* visits);
 
 // glb_reader.cpp: meshes of a glTF-binary file with node transforms baked in, file order kept
 std::vector<TriMesh> loadGlbMeshes(const std::string& path, bool loadNormals);

@@ -1,5 +1,6 @@
-// The host side of the six query families - ray queries (mi_query*), point queries (mi_point_query*), crossing counts and
-// signs (mi_count_query*, mi_point_sign*), crossing lists (mi_list_*), neighbour lists (mi_near_*) and box queries (mi_box_*): one launch frame, one
+// The host side of the seven query families - ray queries (mi_query*), point queries (mi_point_query*), crossing counts and
+// signs (mi_count_query*, mi_point_sign*), crossing lists (mi_list_*), neighbour lists (mi_near_*), box queries (mi_box_*) and
+// triangle queries (mi_tri_*): one launch frame, one
 // build selection, one argument checker, one two-slot host pipeline, and the extern "C" entries on top of them. Included by
 // raylib.hip, in its translation unit, once mi_scene, LaunchSlot, guarded, HIP_CHECK and kMaxWorkItems are defined
 // (group_render.hpp is included the same way). A new family supplies a kernel header, a launcher body inside launchFrame, its
@@ -209,6 +210,39 @@ void launchBoxFill(mi_scene& S, const mi_box* d_boxes, const uint64_t* d_offsets
   });
 }
 
+// Triangle queries (mi_tri_query_device): whether a primitive touches each triangle (MI_TRI_ANY, n bytes) or how many do
+// (MI_TRI_COUNT, n uint32_t), one thread per triangle (contact_kernels.hpp). full_stats picks the instrumented build; no other
+// option applies.
+void launchTriQuery(mi_scene& S, int kind, const mi_tri* d_tris, void* d_out, size_t n, hipStream_t stream) {
+  launchFrame(S, "mi_tri_query", "triangles", n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
+    withFlag(kind == MI_TRI_COUNT, [&](auto count) { pickBuild<false, false>(S.opt, [&](auto b) {
+      hipLaunchKernelGGL((tri_query_kernel<decltype(count)::value, decltype(b)::stats>), grid, block, 0, stream, dsv, d_tris, d_out, cnt);
+    }); });
+  });
+}
+
+// Contact lists, step 1 (mi_tri_offsets_device): d_incl[i] = the primitives touching triangles 0 .. i. tri_count_kernel writes the
+// counts as 64 bits, scanOffsets sums them.
+void launchTriOffsets(mi_scene& S, const mi_tri* d_tris, uint64_t* d_incl, size_t n, hipStream_t stream) {
+  launchFrame(S, "mi_tri_offsets", "triangles", n, stream, [&](LaunchSlot& slot, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
+    pickBuild<false, false>(S.opt, [&](auto b) {
+      hipLaunchKernelGGL(tri_count_kernel<decltype(b)::stats>, grid, block, 0, stream, dsv, d_tris, d_incl, cnt);
+    });
+    HIP_CHECK(hipGetLastError());
+    scanOffsets(slot, d_incl, cnt, stream);
+  });
+}
+
+// Contact lists, step 2 (mi_tri_fill_device): tri_fill_kernel, one thread per triangle. triBase: the index of the launch's first
+// triangle in the caller's numbering (the host entry's batches).
+void launchTriFill(mi_scene& S, const mi_tri* d_tris, const uint64_t* d_offsets, mi_contact* d_hits, size_t capacity, uint32_t triBase, size_t n, hipStream_t stream) {
+  launchFrame(S, "mi_tri_fill", "triangles", n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
+    pickBuild<false, false>(S.opt, [&](auto b) {
+      hipLaunchKernelGGL(tri_fill_kernel<decltype(b)::stats>, grid, block, 0, stream, dsv, d_tris, d_offsets, d_hits, (uint64_t)capacity, triBase, cnt);
+    });
+  });
+}
+
 // ------------------------------------------------------------------------------------------------------
 // argument rules
 // ------------------------------------------------------------------------------------------------------
@@ -221,6 +255,7 @@ constexpr const char* kBuffers16 = "buffers must be 16-byte aligned";
 constexpr const char* kRays16 = "rays must be 16-byte aligned";
 constexpr const char* kPoints16 = "points must be 16-byte aligned";
 constexpr const char* kBoxes16 = "boxes must be 16-byte aligned";
+constexpr const char* kTris4 = "triangles must be 4-byte aligned";
 constexpr size_t kNoLimit = ~(size_t)0;      // (a host entry: its limit is per batch, hostBatch)
 
 // The argument rules of every query entry, in the order the entries have always applied them: the scene, the kind (kindBad: the
@@ -266,10 +301,16 @@ bool boxQueryBad(const char* fn, const mi_scene* scene, int kind, const void* bo
   return queryArgsBad(fn, scene, kind != MI_BOX_ANY && kind != MI_BOX_COUNT ? "unknown box kind" : nullptr, nullptr, n, limit, "boxes",
                       {{boxes, 16, kBoxes16}, {out, kind == MI_BOX_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
 }
-// (the entries of the crossing lists, the neighbour lists and the box lists: `in` the rays, the points or the boxes; hits: only the fill's)
-bool listQueryBad(const char* fn, const mi_scene* scene, const char* noun, const char* inWhy, const void* in, const void* offsets, const void* hits, bool fill, size_t n, size_t limit) {
+bool triQueryBad(const char* fn, const mi_scene* scene, int kind, const void* tris, const void* out, size_t n, size_t limit) {
+  return queryArgsBad(fn, scene, kind != MI_TRI_ANY && kind != MI_TRI_COUNT ? "unknown triangle kind" : nullptr, nullptr, n, limit, "triangles",
+                      {{tris, 4, kTris4}, {out, kind == MI_TRI_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
+}
+// (the entries of the crossing lists, the neighbour lists, the box lists and the contact lists: `in` the rays, the points, the boxes -
+// 16-byte aligned - or the triangles - inAlign = 4; hits: only the fill's)
+bool listQueryBad(const char* fn, const mi_scene* scene, const char* noun, const char* inWhy, const void* in, const void* offsets, const void* hits, bool fill, size_t n, size_t limit,
+                  size_t inAlign = 16) {
   return queryArgsBad(fn, scene, nullptr, nullptr, n, limit, noun,
-                      {{in, 16, inWhy}, {offsets, 8, "offsets must be 8-byte aligned"}, {hits, fill ? 16u : 0u, "hits must be 16-byte aligned"}});
+                      {{in, inAlign, inWhy}, {offsets, 8, "offsets must be 8-byte aligned"}, {hits, fill ? 16u : 0u, "hits must be 16-byte aligned"}});
 }
 
 // The direction of an inside test: the caller's three floats or the default.
@@ -293,14 +334,16 @@ size_t hostBatch(const char* fn, const char* noun, const mi_scene* scene, size_t
 }
 
 // The device buffers and streams of the pipeline's slots: kept by the scene between calls, regrown when a batch is larger than
-// any before. A slot holds `batch` 32-byte records in and out: room for rays or points, any of the results, or batch + 1 offsets.
+// any before. A slot holds `batch` items in - sized for the largest, the 36-byte triangle; rays, points and boxes are 32 bytes - and
+// `batch` 32-byte records out: room for any of the results, or batch + 1 offsets.
+constexpr size_t kQueryItemBytes = std::max({sizeof(mi_ray), sizeof(mi_point), sizeof(mi_box), sizeof(mi_tri)});
 void ensureQuerySlots(mi_scene* scene, size_t batch, int slots) {
   for (int i = 0; i < slots; ++i) {
     if (scene->qCap[i] < batch) {
       if (scene->d_qRays[i] || scene->d_qOut[i]) HIP_CHECK(hipDeviceSynchronize());
       for (void** p : {&scene->d_qRays[i], &scene->d_qOut[i]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
       scene->qCap[i] = 0;
-      HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * sizeof(mi_ray)));
+      HIP_CHECK(hipMalloc(&scene->d_qRays[i], batch * kQueryItemBytes));
       HIP_CHECK(hipMalloc(&scene->d_qOut[i], batch * sizeof(mi_query_hit)));
       scene->qCap[i] = batch;
     }
@@ -329,7 +372,7 @@ void pipelinedQuery(mi_scene* scene, const void* in, size_t inSize, void* out, s
   } catch (...) { (void)hipDeviceSynchronize(); throw; }
 }
 
-// mi_list_offsets, mi_near_offsets and mi_box_offsets on host buffers: every batch's prefix sum starts at 0 on the device; what precedes the
+// mi_list_offsets, mi_near_offsets, mi_box_offsets and mi_tri_offsets on host buffers: every batch's prefix sum starts at 0 on the device; what precedes the
 // batch is added here, batch by batch.
 template <class Launch>
 void offsetsHost(mi_scene* scene, const void* in, size_t inSize, uint64_t* offsets, size_t n, size_t batch, const Launch& launch) {
@@ -342,7 +385,7 @@ void offsetsHost(mi_scene* scene, const void* in, size_t inSize, uint64_t* offse
   }
 }
 
-// mi_list_fill, mi_near_fill and mi_box_fill on host buffers (in: rays, points or boxes of inSize bytes; hits: 16-byte records of any of the kinds;
+// mi_list_fill, mi_near_fill, mi_box_fill and mi_tri_fill on host buffers (in: rays, points, boxes or triangles of inSize bytes; hits: 16-byte records of any of the kinds;
 // launch(d_in, d_offsets, d_hits, capacity, base, cnt, stream) enqueues one batch's fill): the pipeline's slots - the result buffer
 // carries a batch's offsets in - plus a staging buffer of records per slot. A batch's segments are packed from 0 in the staging -
 // the device sees offsets of its own, cut at `capacity` here already - and copied to where the caller's offsets put them: in one
@@ -611,6 +654,63 @@ int mi_box_fill(mi_scene* scene, const mi_box* boxes, const uint64_t* offsets, m
   return guarded([&] {
     listFillHost(scene, boxes, sizeof(mi_box), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_overlap* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
       launchBoxFill(*scene, static_cast<const mi_box*>(d_in), d_off, d_hits, cap, base, cnt, st);
+    });
+  });
+}
+
+int mi_tri_query_device(mi_scene* scene, int kind, const void* d_tris, void* d_out, size_t n, void* hip_stream) {
+  if (triQueryBad("mi_tri_query_device", scene, kind, d_tris, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] { launchTriQuery(*scene, kind, static_cast<const mi_tri*>(d_tris), d_out, n, (hipStream_t)hip_stream); });
+}
+
+int mi_tri_query(mi_scene* scene, int kind, const mi_tri* tris, void* out, size_t n) {
+  if (triQueryBad("mi_tri_query", scene, kind, tris, out, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch("mi_tri_query", "triangles", scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    pipelinedQuery(scene, tris, sizeof(mi_tri), out, kind == MI_TRI_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchTriQuery(*scene, kind, static_cast<const mi_tri*>(d_in), d_out, cnt, st);
+    });
+  });
+}
+
+int mi_tri_offsets_device(mi_scene* scene, const void* d_tris, uint64_t* d_offsets, size_t n, void* hip_stream) {
+  if (listQueryBad("mi_tri_offsets_device", scene, "triangles", kTris4, d_tris, d_offsets, nullptr, false, n, kMaxWorkItems, 4)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] {
+    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
+    launchTriOffsets(*scene, static_cast<const mi_tri*>(d_tris), d_offsets + 1, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_tri_fill_device(mi_scene* scene, const void* d_tris, const uint64_t* d_offsets, mi_contact* d_hits, size_t capacity, size_t n, void* hip_stream) {
+  if (listQueryBad("mi_tri_fill_device", scene, "triangles", kTris4, d_tris, d_offsets, d_hits, true, n, kMaxWorkItems, 4)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] { launchTriFill(*scene, static_cast<const mi_tri*>(d_tris), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
+}
+
+int mi_tri_offsets(mi_scene* scene, const mi_tri* tris, uint64_t* offsets, size_t n) {
+  if (listQueryBad("mi_tri_offsets", scene, "triangles", kTris4, tris, offsets, nullptr, false, n, kNoLimit, 4)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch("mi_tri_offsets", "triangles", scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    offsetsHost(scene, tris, sizeof(mi_tri), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchTriOffsets(*scene, static_cast<const mi_tri*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
+    });
+  });
+}
+
+int mi_tri_fill(mi_scene* scene, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity, size_t n) {
+  if (listQueryBad("mi_tri_fill", scene, "triangles", kTris4, tris, offsets, hits, true, n, kNoLimit, 4)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch("mi_tri_fill", "triangles", scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    listFillHost(scene, tris, sizeof(mi_tri), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_contact* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
+      launchTriFill(*scene, static_cast<const mi_tri*>(d_in), d_off, d_hits, cap, base, cnt, st);
     });
   });
 }

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import RAY, POINT, POINT_HIT, BOX, INVALID_PRIM      # noqa: F401  (the record dtypes of ray and point queries, side by side)
+from . import RAY, POINT, POINT_HIT, BOX, TRI, INVALID_PRIM      # noqa: F401  (the record dtypes of ray and point queries, side by side)
 
 RAY_EPSILON = np.float32(5.9604644775390625e-08 * 1500.0)       # ray_math.h kRayEpsilon (precision_utils.hpp)
 LIGHT = np.array([18.0, 257.0, -1060.0], np.float32)            # the reference's shadow-trace light (trace.cpp:247)
@@ -42,6 +42,17 @@ def make_boxes(lo: np.ndarray, hi: np.ndarray) -> np.ndarray:
     b["lo"] = lo
     b["hi"] = hi
     return b
+
+
+def make_tris(a: np.ndarray, b: np.ndarray, c: np.ndarray | None = None) -> np.ndarray:
+    """A TRI array (triangle queries: IpuScene.tri_touches / count_contacts / list_contacts) from three [N, 3] arrays of corners, or,
+    with two arguments, from (vertices [V, 3], faces [F, 3]): the batch is vertices[faces]."""
+    if c is None:
+        corners = np.asarray(a, np.float32)[np.asarray(b, np.int64)]
+    else:
+        corners = np.stack([np.asarray(a, np.float32), np.asarray(b, np.float32), np.asarray(c, np.float32)], axis=1)
+    assert corners.ndim == 3 and corners.shape[1:] == (3, 3)
+    return np.ascontiguousarray(corners, np.float32).reshape(-1, 9).view(TRI).reshape(-1)
 
 
 def primary_rays(host_scene) -> np.ndarray:
