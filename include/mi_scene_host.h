@@ -34,7 +34,13 @@ int mi_host_scene_builtin(const char* scene_name, const char* mesh_file, mi_host
 int mi_host_scene_import(const char* file, int load_normals, mi_host_scene** out);
 
 /* Build a scene from caller-provided arrays (same array contract as mi_scene_desc, but
- * bvh_nodes/max_leaf_depth are ignored and rebuilt). Used by tests with synthetic geometry. */
+ * bvh_nodes/max_leaf_depth are ignored and rebuilt). Used by tests with synthetic geometry.
+ * A geometry is one mesh, sphere or disc; its geomID is 16 bit with 0xFFFF kept for "interior node"
+ * (mi_bvh_node::geom_id) and mi_geom_ref::index is 16 bit. So num_meshes + num_spheres + num_discs above
+ * 65535 is refused before anything is built, with MI_ERR_INVALID_ARG and mi_scene_create's words,
+ * "more than 65535 geometries (geomID is 16 bit)"; that bound also keeps every mesh, sphere and disc index
+ * inside mi_geom_ref::index. mi_host_scene_import refuses a file with more geometries the same way, and
+ * the host twins below and mi_refit_compact_bvh refuse a desc whose num_geometry exceeds 65535. */
 int mi_host_scene_from_arrays(const mi_scene_desc* geometry_only, mi_host_scene** out);
 
 /* Fill `desc` with pointers into the host scene's storage and the reference CLI's default

@@ -21,7 +21,7 @@ struct CanonPrim { Box3 box; uint16_t geomID; uint32_t primID; };
 void buildLbvhCompact(const mi_scene_desc& d, std::vector<mi_bvh_node>& out, uint32_t& maxDepth) {
   auto need = [](bool ok, const char* what) { if (!ok) throw std::invalid_argument(std::string("mi_build_lbvh_compact: ") + what); };
   need(d.num_geometry == 0 || d.geometry, "geometry is null");
-  need(d.num_geometry <= 0xFFFF, "more than 65535 geometries (geomID is 16 bit)");
+  need(d.num_geometry <= kMaxGeometries, kTooManyGeometries);
   need(d.num_meshes == 0 || (d.mesh_info && d.mesh_tris && d.mesh_verts), "mesh arrays are null");
   need(d.num_spheres == 0 || d.spheres, "spheres is null");
   need(d.num_discs == 0 || d.discs, "discs is null");

@@ -20,6 +20,7 @@ std::vector<WalkNode> walkTable(const mi_scene_desc& d, const char* fn) {
   const uint32_t N = d.num_nodes;
   need(N == 0 || d.bvh_nodes, "bvh_nodes is null");
   need(d.num_geometry == 0 || d.geometry, "geometry is null");
+  need(d.num_geometry <= kMaxGeometries, kTooManyGeometries);
   need(d.num_meshes == 0 || (d.mesh_info && d.mesh_tris && d.mesh_verts), "mesh arrays are null");
   need(d.num_spheres == 0 || d.spheres, "spheres is null");
   need(d.num_discs == 0 || d.discs, "discs is null");

@@ -68,6 +68,9 @@ int mi_host_scene_import(const char* file, int load_normals, mi_host_scene** out
 int mi_host_scene_from_arrays(const mi_scene_desc* g, mi_host_scene** out) {
   if (!g || !out) { g_err = "null argument"; return MI_ERR_INVALID_ARG; }
   return guarded([&] {
+    // before anything is copied or built (packScene would refuse it too, after the copies)
+    if ((uint64_t)g->num_meshes + g->num_spheres + g->num_discs > kMaxGeometries)
+      throw std::invalid_argument(std::string("mi_host_scene_from_arrays: ") + kTooManyGeometries);
     SceneDescription d;
     for (uint32_t m = 0; m < g->num_meshes; ++m) {
       const mi_mesh_info& mi_ = g->mesh_info[m];

@@ -169,6 +169,10 @@ SceneDescription makeMonkeyScene(const std::string& meshFile) {
 
 // buildSceneData (src/app_utils.cpp:291-371) + makeBuildPrimitivesForEmbree (:145-188)
 PackedScene packScene(const SceneDescription& scene) {
+  // refused before anything is built: past 65535 geometries a geomID would read as "interior node" or wrap, and the (uint16_t)
+  // casts below would alias geometries (every importer's scene comes through here too). A geometry is one mesh, sphere or disc, so
+  // the bound on their sum also keeps every mesh, sphere and disc index inside mi_geom_ref::index.
+  if (scene.meshes.size() + scene.spheres.size() + scene.discs.size() > kMaxGeometries) throw std::invalid_argument(kTooManyGeometries);
   PackedScene d;
   for (const auto& m : scene.meshes) {
     d.meshInfo.push_back({(uint32_t)(d.meshTris.size() / 3), (uint32_t)d.meshVerts.size(),

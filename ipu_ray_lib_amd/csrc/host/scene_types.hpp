@@ -92,6 +92,12 @@ struct PackedScene {
   float horizontalFov = 0.f;
 };
 
+// A geomID is 16 bit with 0xFFFF kept for "interior node" (mi_bvh_node::geom_id), and mi_geom_ref::index is 16 bit: the bound, and
+// the words the host library's entries refuse a larger scene with. The device library (raylib.hip) and canon_prims.hpp, which it
+// shares, do not include this header and spell the same words themselves; tests/test_id_range_*.py hold all of them to one text.
+constexpr uint32_t kMaxGeometries = 0xFFFF;
+constexpr const char* kTooManyGeometries = "more than 65535 geometries (geomID is 16 bit)";
+
 struct BuildPrim { Bounds box; uint16_t geomID; uint32_t primID; };
 
 // bvh_sah.cpp

@@ -263,33 +263,51 @@ def sphere_crossings64(c, radius, o, d, t_min, t_max):
 # ------------------------------------------------------------------------------------------------------
 # the checker
 # ------------------------------------------------------------------------------------------------------
+class _Prims(dict):
+    """Checker's leaf primitives by node index, an entry made when it is first read."""
+
+    def __init__(self, make):
+        super().__init__()
+        self.make = make
+
+    def __missing__(self, i):
+        self[i] = self.make(i)
+        return self[i]
+
+
 class Checker:
     """The crossing count of a ray on a host scene's compact nodes: the reference's walk (a stack, first child first) with the
     oracle's box test over the FIXED interval [t_min, t_max] and, at every leaf whose box is hit, the oracle's primitive test."""
 
-    def __init__(self, hs):
+    def __init__(self, hs, lazy=False):
+        """lazy: a leaf's primitive is resolved when a walk first reaches it (a tree of hundreds of thousands of nodes)."""
         self.desc = hs.desc
         nodes = np.ascontiguousarray(hs.nodes)
         self.n = nodes.size
         self.nodes = (ol.Node * max(self.n, 1)).from_buffer_copy(nodes.tobytes() if self.n else bytes(C.sizeof(ol.Node)))
         self.link = nodes["link"].tolist()
         self.geom = nodes["geomID"].tolist()
-        self.prims = {}
-        tris = hs.tris.reshape(-1, 3)
-        for i in range(self.n):
-            if self.geom[i] == irl.INVALID_GEOM:
-                continue
-            ref = hs.geometry[self.geom[i]]
-            if ref["type"] == 0:
-                info = hs.mesh_info[ref["index"]]
-                tri = tris[int(info["firstIndex"]) + self.link[i]]
-                v = hs.verts[int(info["firstVertex"]) + tri.astype(np.int64)]
-                self.prims[i] = (0, [ol.Vec3(float(p["x"]), float(p["y"]), float(p["z"])) for p in v])
-            elif ref["type"] == 1:
-                s = hs.spheres[ref["index"]]
-                self.prims[i] = (1, (np.array([s["x"], s["y"], s["z"]], F), F(F(s["radius"]) * F(s["radius"]))))
-            else:
-                self.prims[i] = (2, ol.Disc.from_buffer_copy(hs.discs[ref["index"]].tobytes()))
+        self.prims = _Prims(lambda i: self._prim_of(hs, i))
+        if not lazy:
+            for i in range(self.n):
+                if self.geom[i] != irl.INVALID_GEOM:
+                    self.prims[i]
+
+    @classmethod
+    def lazy(cls, hs):
+        return cls(hs, lazy=True)
+
+    def _prim_of(self, hs, i):
+        ref = hs.geometry[self.geom[i]]
+        if ref["type"] == 0:
+            info = hs.mesh_info[ref["index"]]
+            tri = hs.tris.reshape(-1, 3)[int(info["firstIndex"]) + self.link[i]]
+            v = hs.verts[int(info["firstVertex"]) + tri.astype(np.int64)]
+            return (0, [ol.Vec3(float(p["x"]), float(p["y"]), float(p["z"])) for p in v])
+        if ref["type"] == 1:
+            s = hs.spheres[ref["index"]]
+            return (1, (np.array([s["x"], s["y"], s["z"]], F), F(F(s["radius"]) * F(s["radius"]))))
+        return (2, ol.Disc.from_buffer_copy(hs.discs[ref["index"]].tobytes()))
 
     def count(self, ray):
         """(crossings, box tests, primitive tests) of one RAY record."""

@@ -22,6 +22,18 @@ def key(rec):
     return (float(rec[0]), int(rec[1]), int(rec[2]))
 
 
+class _LazyLeaves:
+    """NearChecker.lazy's `leaf`: a sequence whose entries are made when they are first read."""
+
+    def __init__(self, hs, nodes, verts, leaf_of):
+        self.hs, self.nodes, self.verts, self.leaf_of, self.made = hs, nodes, verts, leaf_of, {}
+
+    def __getitem__(self, i):
+        if i not in self.made:
+            self.made[i] = self.leaf_of(self.hs, self.verts, self.nodes[i])
+        return self.made[i]
+
+
 class NearChecker:
     """The contract over a host scene's compact nodes (or `nodes`, a BVH_NODE array over the same primitives)."""
 
@@ -29,30 +41,54 @@ class NearChecker:
         nodes = hs.nodes if nodes is None else np.asarray(nodes, irl.BVH_NODE)
         self.n = len(nodes)
         self.lo, self.hi, self.skip, self.leaf = [], [], [0] * self.n, []
-        verts = np.stack([hs.verts[c] for c in "xyz"], 1).astype(F) if hs.verts.size else np.zeros((0, 3), F)
+        verts = self._verts(hs)
         for i in range(self.n):
             nd = nodes[i]
             lo = np.array([nd["min_x"], nd["min_y"], nd["min_z"]], F)
             ext = np.array([nd["dx"], nd["dy"], nd["dz"]], np.uint16).view(np.float16).astype(F)
             self.lo.append(tuple(lo)); self.hi.append(tuple((lo + ext).astype(F)))       # max = min + (float)extent: one rounded add
-            g = int(nd["geomID"])
-            if g == irl.INVALID_GEOM:
-                self.leaf.append(None)
-                continue
-            ref = hs.geometry[g]
-            if ref["type"] == 0:
-                m = hs.mesh_info[ref["index"]]
-                prim = int(nd["link"])
-                t = hs.tris[int(m["firstIndex"]) + prim].astype(np.int64) + int(m["firstVertex"])
-                self.leaf.append((0, (verts[t[0]], verts[t[1]], verts[t[2]]), g, prim))
-            elif ref["type"] == 1:
-                s = hs.spheres[ref["index"]]
-                self.leaf.append((1, ((s["x"], s["y"], s["z"]), s["radius"]), g, 0))
-            else:
-                d = hs.discs[ref["index"]]
-                self.leaf.append((2, ((d["nx"], d["ny"], d["nz"]), (d["cx"], d["cy"], d["cz"]), d["r"]), g, 0))
+            self.leaf.append(self._leaf_of(hs, verts, nd))
         for i in range(self.n - 1, -1, -1):              # the node behind a node's subtree
             self.skip[i] = i + 1 if self.leaf[i] is not None else self.skip[int(nodes[i]["link"])]
+
+    @staticmethod
+    def _verts(hs):
+        return np.stack([hs.verts[c] for c in "xyz"], 1).astype(F) if hs.verts.size else np.zeros((0, 3), F)
+
+    @staticmethod
+    def _leaf_of(hs, verts, nd):
+        """A node's entry of `leaf`: None for an interior node, else (kind, the primitive's data, geomID, primID)."""
+        g = int(nd["geomID"])
+        if g == irl.INVALID_GEOM:
+            return None
+        ref = hs.geometry[g]
+        if ref["type"] == 0:
+            m = hs.mesh_info[ref["index"]]
+            prim = int(nd["link"])
+            t = hs.tris[int(m["firstIndex"]) + prim].astype(np.int64) + int(m["firstVertex"])
+            return (0, (verts[t[0]], verts[t[1]], verts[t[2]]), g, prim)
+        if ref["type"] == 1:
+            s = hs.spheres[ref["index"]]
+            return (1, ((s["x"], s["y"], s["z"]), s["radius"]), g, 0)
+        d = hs.discs[ref["index"]]
+        return (2, ((d["nx"], d["ny"], d["nz"]), (d["cx"], d["cy"], d["cz"]), d["r"]), g, 0)
+
+    @classmethod
+    def lazy(cls, hs, nodes=None):
+        """The same checker for a tree of hundreds of thousands of nodes, made in milliseconds: boxes and skip links by numpy, a
+        leaf's entry (_leaf_of, as above) when a walk first reads it."""
+        nodes = np.ascontiguousarray(hs.nodes if nodes is None else nodes, irl.BVH_NODE)
+        ck = cls.__new__(cls)
+        ck.n = len(nodes)
+        lo = np.stack([nodes["min_x"], nodes["min_y"], nodes["min_z"]], 1).astype(F)
+        ext = np.stack([nodes["dx"], nodes["dy"], nodes["dz"]], 1).astype(np.uint16).view(np.float16).astype(F)
+        ck.lo, ck.hi = lo, (lo + ext).astype(F)              # max = min + (float)extent: one rounded add
+        link, interior = nodes["link"].tolist(), (nodes["geomID"] == irl.INVALID_GEOM).tolist()
+        ck.skip = [0] * ck.n
+        for i in range(ck.n - 1, -1, -1):
+            ck.skip[i] = ck.skip[link[i]] if interior[i] else i + 1
+        ck.leaf = _LazyLeaves(hs, nodes, cls._verts(hs), cls._leaf_of)
+        return ck
 
     def _d2(self, i, p):
         kind, data, _, _ = self.leaf[i]
