@@ -2,12 +2,12 @@
 // include/mi_raylib.h): how many surfaces a ray crosses inside its interval, and from the parity of that count whether a point
 // lies inside (Open3D's count_intersections / compute_occupancy / compute_signed_distance).
 //
-//   count_crossings      the walk, one copy: the stackless preorder walk of every kernel here over the same GNode / GLeaf records
-//                        with the literal box test of traverse<> over the FIXED interval [tMin, tMax] - a closest-hit cast shrinks
-//                        its interval and prunes what lies behind the hit, a count must not -, so the leaves visited are a function
-//                        of the ray and the nodes alone and the count, a sum over them, does not depend on the visit order. A
-//                        triangle or a disc adds 1 when prim_hit accepts it against tMax, a sphere adds sphere_crossings
-//                        (cross_math.hpp: both roots, which the reference's one-t sphere test cannot give).
+//   count_crossings      walk_preorder (bvh_walk.hpp) with the literal box test of traverse<> over the FIXED interval [tMin, tMax]
+//                        (ray_meets_node) - a closest-hit cast shrinks its interval and prunes what lies behind the hit, a count
+//                        must not -, so the leaves visited are a function of the ray and the nodes alone and the count, a sum
+//                        over them, does not depend on the visit order. A triangle or a disc adds 1 when prim_hit accepts it
+//                        against tMax, a sphere adds sphere_crossings (cross_math.hpp: both roots, which the reference's one-t
+//                        sphere test cannot give).
 //   count_query_kernel   one thread per ray, the form of query_plain_kernel: one uint32 per ray.
 //   point_sign_kernel    one thread per point: the ray from the point along the launch's direction over (0, +inf); an odd count is
 //                        "inside". MI_SIGN_INSIDE writes a byte; MI_SIGN_DISTANCE finds the record point_query_kernel wrote for
@@ -16,45 +16,40 @@
 // one counter.
 #pragma once
 
+#include "bvh_walk.hpp"
 #include "query_kernels.hpp"      // load_query_ray
 #include "point_math.hpp"         // point_query_valid
 #include "cross_math.hpp"
 
 namespace mi {
 
+// The literal box test of traverse<> over the FIXED interval [tMin, tMax] (never narrowed by a hit: nothing is pruned): what the
+// walks of count_crossings and list_crossings (list_kernels.hpp) enter a node by.
+__device__ __forceinline__ bool ray_meets_node(const GNode& nd, f3 o, f3 inv, float tMin, float tMax) {
+  float t0 = tMin, t1 = tMax;
+  box_hit_literal_axis((nd.minx - o.x) * inv.x, (nd.maxx - o.x) * inv.x, t0, t1);
+  box_hit_literal_axis((nd.miny - o.y) * inv.y, (nd.maxy - o.y) * inv.y, t0, t1);
+  box_hit_literal_axis((nd.minz - o.z) * inv.z, (nd.maxz - o.z) * inv.z, t0, t1);
+  return !(t0 > t1);
+}
+
 template <bool STATS, bool DF>
 __device__ __forceinline__ uint32_t count_crossings(const DeviceScene& sc, f3 o, f3 d, float tMin, float tMax, CastStats& cs) {
   const f3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
   const Shear sh = make_shear(d, inv);
   uint32_t count = 0;
-  // node positions are BYTE offsets into the node array (GNode)
-  const uint32_t end = sc.numNodes << 5;
-  uint32_t node = 0;
-  while (node < end) {
-    const GNode nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + node);
-    if (STATS) cs.nodes++;
-    float t0 = tMin, t1 = tMax;      // (never narrowed by a hit: nothing is pruned)
-    box_hit_literal_axis((nd.minx - o.x) * inv.x, (nd.maxx - o.x) * inv.x, t0, t1);
-    box_hit_literal_axis((nd.miny - o.y) * inv.y, (nd.maxy - o.y) * inv.y, t0, t1);
-    box_hit_literal_axis((nd.minz - o.z) * inv.z, (nd.maxz - o.z) * inv.z, t0, t1);
-    uint32_t next = !(t0 > t1) ? nd.hit : nd.link;
-    if (next & kLeafFlag) {
-      // a leaf's hit successor is its link with kLeafFlag: the primitive of THIS node is tested, the walk goes on behind it
-      next &= ~kLeafFlag;
-      if (STATS) cs.leaves++;
-      const float4* rec = reinterpret_cast<const float4*>(sc.leaves + (node >> 5));      // the first 40 bytes: type, nine floats
-      const float4 r0 = rec[0], r1 = rec[1];
-      const float2 r2 = *reinterpret_cast<const float2*>(rec + 2);
-      const GLeafBlock B = {__float_as_uint(r0.x), {r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y}};
+  walk_preorder<STATS>(sc, true, cs,
+    [&](const GNode& nd) { return ray_meets_node(nd, o, inv, tMin, tMax); },
+    [&](uint32_t, uint32_t type, const float (&f)[9]) {
+      const GLeafBlock B = {type, {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]}};
       if (leaf_kind(B) == LEAF_SPHERE) {
         count += sphere_crossings(mk(B.f[0], B.f[1], B.f[2]), B.f[4], o, d, tMin, tMax);
       } else {
         float t, b0, b1, b2;
         count += prim_hit<DF>(B, o, d, sh, tMin, tMax, t, b0, b1, b2) ? 1u : 0u;
       }
-    }
-    node = next;
-  }
+      return false;
+    });
   return count;
 }
 

@@ -105,7 +105,7 @@ void buildCompactBvh(const std::vector<BuildPrim>& prims, std::vector<mi_bvh_nod
 void refitCompactBvh(const mi_scene_desc& desc, mi_bvh_node* out);
 // lbvh.cpp: the host twin of mi_scene_rebuild
 void buildLbvhCompact(const mi_scene_desc& desc, std::vector<mi_bvh_node>& nodes, uint32_t& maxDepth);
-// point_query_host.cpp: what the host twins' walks read of a node - the decoded box, where the walk goes on when the box is passed,
+// walk_table.cpp: what the host twins' walk (walkHost, walk_host.hpp) reads of a node - the decoded box, where the walk goes on when the box is passed,
 // and for a leaf the first 40 bytes of the device's leaf record (kind, nine floats) with the ids a result reports - and the table of
 // desc's nodes (fn: the entry's name, for the message of what is refused)
 struct WalkNode {

@@ -6,10 +6,11 @@
 //   scan_*_kernel        an inclusive prefix sum of those counts in place, in 64 bits: tile sums, a scan of the tile sums by one
 //                        workgroup, the scan of every tile with its tile's base added. The sums are integers: the result does not
 //                        depend on the order they are added in.
-//   list_crossings       the walk of count_crossings, one copy more: the same nodes, box test, leaf load, prim_hit and sphere
-//                        arithmetic (sphere_roots: the operations of sphere_crossings with their t kept), calling `emit` where
-//                        count_crossings adds to its counter. The interval is FIXED, so the set of crossings is a function of the
-//                        ray and the geometry alone; sorted by a key of the crossing itself the list is the same bytes on any tree.
+//   list_crossings       count_crossings' two lambdas over walk_preorder (bvh_walk.hpp) - the same box test (ray_meets_node),
+//                        prim_hit and sphere arithmetic (sphere_roots: the operations of sphere_crossings with their t kept) -
+//                        calling `emit` where count_crossings adds to its counter. The interval is FIXED, so the set of crossings
+//                        is a function of the ray and the geometry alone; sorted by a key of the crossing itself the list is the
+//                        same bytes on any tree.
 //   list_fill_kernel     one thread per ray: each accepted crossing is inserted at its sorted place into the ray's OWN segment of
 //                        the output, [offsets[i], offsets[i + 1]) cut at `capacity`: records behind it move up by one, the last one
 //                        is dropped when the segment is full, and what the walk leaves unused is padded with the empty record.
@@ -23,6 +24,7 @@
 #pragma once
 
 #include "count_kernels.hpp"
+#include "list_segment.hpp"
 
 namespace mi {
 
@@ -44,31 +46,17 @@ __device__ __forceinline__ bool crossing_before(const uint4& a, const uint4& b) 
   return ta < tb || (ta == tb && crossing_rank(a) < crossing_rank(b));
 }
 
-// The walk of count_crossings (count_kernels.hpp), statement for statement; emit(t, primID, geomID, flags) is called for each
-// crossing count_crossings counts.
+// The walk of count_crossings (count_kernels.hpp); emit(t, primID, geomID, flags) is called for each crossing count_crossings
+// counts.
 template <bool STATS, bool DF, class Emit>
 __device__ __forceinline__ void list_crossings(const DeviceScene& sc, f3 o, f3 d, float tMin, float tMax, CastStats& cs, const Emit& emit) {
   const f3 inv = mk(1.f / d.x, 1.f / d.y, 1.f / d.z);
   const Shear sh = make_shear(d, inv);
-  // node positions are BYTE offsets into the node array (GNode)
-  const uint32_t end = sc.numNodes << 5;
-  uint32_t node = 0;
-  while (node < end) {
-    const GNode nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + node);
-    if (STATS) cs.nodes++;
-    float t0 = tMin, t1 = tMax;      // (never narrowed by a hit: nothing is pruned)
-    box_hit_literal_axis((nd.minx - o.x) * inv.x, (nd.maxx - o.x) * inv.x, t0, t1);
-    box_hit_literal_axis((nd.miny - o.y) * inv.y, (nd.maxy - o.y) * inv.y, t0, t1);
-    box_hit_literal_axis((nd.minz - o.z) * inv.z, (nd.maxz - o.z) * inv.z, t0, t1);
-    uint32_t next = !(t0 > t1) ? nd.hit : nd.link;
-    if (next & kLeafFlag) {
-      next &= ~kLeafFlag;
-      if (STATS) cs.leaves++;
-      const GLeaf* leaf = sc.leaves + (node >> 5);
-      const float4* rec = reinterpret_cast<const float4*>(leaf);      // the first 40 bytes: type, nine floats
-      const float4 r0 = rec[0], r1 = rec[1];
-      const float2 r2 = *reinterpret_cast<const float2*>(rec + 2);
-      const GLeafBlock B = {__float_as_uint(r0.x), {r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y}};
+  walk_preorder<STATS>(sc, true, cs,
+    [&](const GNode& nd) { return ray_meets_node(nd, o, inv, tMin, tMax); },
+    [&](uint32_t at, uint32_t type, const float (&f)[9]) {
+      const GLeafBlock B = {type, {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]}};
+      const GLeaf* leaf = sc.leaves + at;
       const uint32_t geomID = B.type >> 16;
       if (leaf_kind(B) == LEAF_SPHERE) {
         float t[2];
@@ -79,9 +67,8 @@ __device__ __forceinline__ void list_crossings(const DeviceScene& sc, f3 o, f3 d
         float t, b0, b1, b2;
         if (prim_hit<DF>(B, o, d, sh, tMin, tMax, t, b0, b1, b2)) emit(t, leaf->primID, geomID, 0u);
       }
-    }
-    node = next;
-  }
+      return false;
+    });
 }
 
 // counts[i] = ray i's crossing count, as 64 bits (the scan below runs in place on them)
@@ -165,10 +152,7 @@ __global__ void __launch_bounds__(256) list_fill_kernel(DeviceScene sc, const mi
   CastStats cs = {0, 0};
   if (idx < n) {
     const QueryRay r = load_query_ray(rays, idx);
-    // the segment: [lo, hi) cut at capacity; a decreasing pair, or a start at or past capacity, is an empty one
-    const uint64_t lo = offsets[idx], hi = offsets[idx + 1];
-    uint64_t len = 0;
-    if (hi > lo && lo < capacity) len = (hi < capacity ? hi : capacity) - lo;
+    const uint64_t lo = offsets[idx], len = segment_len(lo, offsets[idx + 1], capacity);      // (list_segment.hpp)
     uint4* seg = reinterpret_cast<uint4*>(hits) + (len ? lo : 0);      // every access below is seg[j] with j < len
     const uint32_t ray = rayBase + idx;
     uint64_t held = 0;                                                  // seg[0 .. held) is sorted, held <= len

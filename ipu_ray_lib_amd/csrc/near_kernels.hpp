@@ -3,8 +3,8 @@
 // nearestKSearch, Open3D's search_radius_vector_3d / search_knn_vector_3d. The form is that of the crossing lists
 // (list_kernels.hpp): count -> prefix sum -> fill.
 //
-//   near_walk            point_query_kernel's walk (point_kernels.hpp), one copy more: the same node and leaf loads, box distance,
-//                        closest_on_prim and point_dist2 (point_math.hpp). A node is entered when its box distance db satisfies
+//   near_walk            walk_preorder (bvh_walk.hpp) with point_query_kernel's box distance, closest_on_prim and point_dist2
+//                        (point_math.hpp). A node is entered when its box distance db satisfies
 //                        db < r2 && db <= bound: `bound` is +inf for the count - the FIXED radius alone decides, so the set of
 //                        neighbours is a function of the point and the geometry - and may be lowered by the fill's accept.
 //                        accept(d2, leaf index, geomID) is called for each primitive of a reached leaf with d2 < r2 (strictly; a NaN never).
@@ -18,8 +18,8 @@
 //                        when the last record changes; it is never read back from memory. A point whose segment is empty is not
 //                        walked.
 // No LDS, no stack, no per-lane array, no scratch: a lane carries the point, r2, the bound, the segment's base and length, the
-// number of records held and the record being placed. The host twin (host/point_query_host.cpp) runs the same walk statement for
-// statement over the compact nodes and returns the same bytes and the same visit totals.
+// number of records held and the record being placed. The host twin (host/point_query_host.cpp) passes the same two lambdas to
+// walkHost over the compact nodes and returns the same bytes and the same visit totals.
 #pragma once
 
 #include "list_kernels.hpp"
@@ -41,33 +41,22 @@ __device__ __forceinline__ bool neighbour_before(const uint4& a, const uint4& b)
   return da < db || (da == db && ra < rb);
 }
 
-// The walk of point_query_kernel with a fixed radius and a bound the caller may lower inside `accept`.
+// walk_preorder with the point queries' arithmetic, a fixed radius and a bound the caller may lower inside `accept`.
 template <bool STATS, class Accept>
 __device__ __forceinline__ void near_walk(const DeviceScene& sc, f3 p, float radius, float r2, float& bound, CastStats& cs, const Accept& accept) {
-  // node positions are BYTE offsets into the node array (GNode); a query that is not walked ends before its first node
-  const uint32_t end = point_query_valid(p, radius) ? sc.numNodes << 5 : 0u;
-  uint32_t node = 0;
-  while (node < end) {
-    const GNode nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + node);
-    if (STATS) cs.nodes++;
-    const float db = point_box_dist2(nd.minx, nd.maxx, nd.miny, nd.maxy, nd.minz, nd.maxz, p);
-    const bool enter = db < r2 && db <= bound;      // (bound = +inf: db < r2 alone; db is never NaN, point_math.hpp)
-    uint32_t next = enter ? nd.hit : nd.link;
-    if (next & kLeafFlag) {
-      // a leaf's hit successor is its link with kLeafFlag: the primitive of THIS node is evaluated, the walk goes on behind it
-      next &= ~kLeafFlag;
-      if (STATS) cs.leaves++;
-      const uint32_t at = node >> 5;
-      const float4* rec = reinterpret_cast<const float4*>(sc.leaves + at);      // the first 40 bytes: type, nine floats
-      const float4 r0 = rec[0], r1 = rec[1];
-      const float2 r2w = *reinterpret_cast<const float2*>(rec + 2);
-      const float f[9] = {r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2w.x, r2w.y};
-      const ClosestPoint c = closest_on_prim(__float_as_uint(r0.x) & 0xFFFFu, f, p);
+  walk_preorder<STATS>(sc, point_query_valid(p, radius), cs,
+    [&](const GNode& nd) {
+      const float db = point_box_dist2(nd.minx, nd.maxx, nd.miny, nd.maxy, nd.minz, nd.maxz, p);
+      // (bound = +inf: db < r2 alone; db is never NaN, point_math.hpp. `&`, not `&&`: two compares and no branch, so that the
+      // walk's choice between GNode.hit and GNode.link stays a select behind one 16-byte load of the node's second half)
+      return (db < r2) & (db <= bound);
+    },
+    [&](uint32_t at, uint32_t type, const float (&f)[9]) {
+      const ClosestPoint c = closest_on_prim(type & 0xFFFFu, f, p);
       const float d2 = point_dist2(p, c.q);
-      if (d2 < r2) accept(d2, at, __float_as_uint(r0.x) >> 16);
-    }
-    node = next;
-  }
+      if (d2 < r2) accept(d2, at, type >> 16);
+      return false;
+    });
 }
 
 // counts[i] = the number of primitives strictly within point i's radius, as 64 bits (the scan runs in place on them)
@@ -92,10 +81,7 @@ __global__ void __launch_bounds__(256) near_fill_kernel(DeviceScene sc, const mi
   const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
   CastStats cs = {0, 0};
   if (idx < n) {
-    // the segment: [lo, hi) cut at capacity; a decreasing pair, or a start at or past capacity, is an empty one
-    const uint64_t lo = offsets[idx], hi = offsets[idx + 1];
-    uint64_t len = 0;
-    if (hi > lo && lo < capacity) len = (hi < capacity ? hi : capacity) - lo;
+    const uint64_t lo = offsets[idx], len = segment_len(lo, offsets[idx + 1], capacity);      // (list_segment.hpp)
     if (len) {                                                            // (an empty segment: nothing to write, no walk)
       const float4 pt = reinterpret_cast<const float4*>(points)[idx];    // mi_point: x, y, z, radius
       uint4* seg = reinterpret_cast<uint4*>(hits) + lo;                   // every access below is seg[j] with j < len

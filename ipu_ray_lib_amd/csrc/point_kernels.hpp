@@ -3,10 +3,9 @@
 //   that primitive (MI_POINT_CLOSEST, Embree's rtcPointQuery), or whether any primitive lies within the radius (MI_POINT_WITHIN).
 //
 //   point_query_kernel   one thread per point, the form of query_plain_kernel (DESIGN.md §6 measured it faster than the persistent
-//                        form for ray queries). The walk is the stackless preorder walk of every kernel here over the same GNode /
-//                        GLeaf records, with a distance test in place of the slab test: at a node the squared distance of the
-//                        point from the node's box is compared with the best squared distance so far (radius^2 at the start), a
-//                        box strictly nearer is entered (GNode.hit), any other is passed (GNode.link). At a leaf so reached the
+//                        form for ray queries). The walk is walk_preorder (bvh_walk.hpp) with a distance test at the nodes: the
+//                        squared distance of the point from the node's box is compared with the best squared distance so far
+//                        (radius^2 at the start), a box strictly nearer is entered, any other is passed. At a leaf so reached the
 //                        primitive's closest point is evaluated (point_math.hpp) and accepted when strictly nearer: of equal
 //                        distances the first leaf in preorder wins, and a NaN distance is never accepted.
 // No LDS, no stack, no scratch: a lane carries the point, the best squared distance, the winning leaf's index, its closest point
@@ -14,7 +13,7 @@
 // the same bytes.
 #pragma once
 
-#include "trace_kernels.hpp"
+#include "bvh_walk.hpp"
 #include "point_math.hpp"
 
 namespace mi {
@@ -35,33 +34,18 @@ __global__ void __launch_bounds__(256) point_query_kernel(DeviceScene sc, const 
     uint32_t leaf = kNoPointLeaf;
     ClosestPoint win;
     win.q = mk(0.f, 0.f, 0.f); win.v = win.w = 0.f;
-    // node positions are BYTE offsets into the node array (GNode); a query that is not walked ends before its first node
-    const uint32_t end = point_query_valid(p, pt.w) ? sc.numNodes << 5 : 0u;
-    uint32_t node = 0;
-    while (node < end) {
-      const GNode nd = *reinterpret_cast<const GNode*>(reinterpret_cast<const char*>(sc.nodes) + node);
-      if (STATS) cs.nodes++;
-      const bool enter = point_box_dist2(nd.minx, nd.maxx, nd.miny, nd.maxy, nd.minz, nd.maxz, p) < best;
-      uint32_t next = enter ? nd.hit : nd.link;
-      if (next & kLeafFlag) {
-        // a leaf's hit successor is its link with kLeafFlag: the primitive of THIS node is evaluated, the walk goes on behind it
-        next &= ~kLeafFlag;
-        if (STATS) cs.leaves++;
-        const uint32_t at = node >> 5;
-        const float4* rec = reinterpret_cast<const float4*>(sc.leaves + at);      // the first 40 bytes: type, nine floats
-        const float4 r0 = rec[0], r1 = rec[1];
-        const float2 r2 = *reinterpret_cast<const float2*>(rec + 2);
-        const float f[9] = {r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, r2.y};
-        const ClosestPoint c = closest_on_prim(__float_as_uint(r0.x) & 0xFFFFu, f, p);
+    walk_preorder<STATS>(sc, point_query_valid(p, pt.w), cs,
+      [&](const GNode& nd) { return point_box_dist2(nd.minx, nd.maxx, nd.miny, nd.maxy, nd.minz, nd.maxz, p) < best; },
+      [&](uint32_t at, uint32_t type, const float (&f)[9]) {
+        const ClosestPoint c = closest_on_prim(type & 0xFFFFu, f, p);
         const float d2 = point_dist2(p, c.q);
         if (d2 < best) {
           leaf = at;
-          if constexpr (WITHIN) break;
+          if constexpr (WITHIN) return true;
           best = d2; win = c;
         }
-      }
-      node = next;
-    }
+        return false;
+      });
     if constexpr (WITHIN) {
       static_cast<uint8_t*>(out)[idx] = leaf != kNoPointLeaf ? 1u : 0u;
     } else {

@@ -178,67 +178,41 @@ void launchNearFill(mi_scene& S, const mi_point* d_points, const uint64_t* d_off
   });
 }
 
-// Box queries (mi_box_query_device): whether a primitive touches each box (MI_BOX_ANY, n bytes) or how many do (MI_BOX_COUNT, n
-// uint32_t), one thread per box (box_kernels.hpp). full_stats picks the instrumented build; no other option applies.
-void launchBoxQuery(mi_scene& S, int kind, const mi_box* d_boxes, void* d_out, size_t n, hipStream_t stream) {
-  launchFrame(S, "mi_box_query", "boxes", n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
-    withFlag(kind == MI_BOX_COUNT, [&](auto count) { pickBuild<false, false>(S.opt, [&](auto b) {
-      hipLaunchKernelGGL((box_query_kernel<decltype(count)::value, decltype(b)::stats>), grid, block, 0, stream, dsv, d_boxes, d_out, cnt);
-    }); });
-  });
-}
-
-// Box lists, step 1 (mi_box_offsets_device): d_incl[i] = the primitives touching boxes 0 .. i. box_count_kernel writes the counts
-// as 64 bits, scanOffsets sums them.
-void launchBoxOffsets(mi_scene& S, const mi_box* d_boxes, uint64_t* d_incl, size_t n, hipStream_t stream) {
-  launchFrame(S, "mi_box_offsets", "boxes", n, stream, [&](LaunchSlot& slot, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
-    pickBuild<false, false>(S.opt, [&](auto b) {
-      hipLaunchKernelGGL(box_count_kernel<decltype(b)::stats>, grid, block, 0, stream, dsv, d_boxes, d_incl, cnt);
-    });
-    HIP_CHECK(hipGetLastError());
-    scanOffsets(slot, d_incl, cnt, stream);
-  });
-}
-
-// Box lists, step 2 (mi_box_fill_device): box_fill_kernel, one thread per box. boxBase: the index of the launch's first box in the
-// caller's numbering (the host entry's batches).
-void launchBoxFill(mi_scene& S, const mi_box* d_boxes, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, uint32_t boxBase, size_t n, hipStream_t stream) {
-  launchFrame(S, "mi_box_fill", "boxes", n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
-    pickBuild<false, false>(S.opt, [&](auto b) {
-      hipLaunchKernelGGL(box_fill_kernel<decltype(b)::stats>, grid, block, 0, stream, dsv, d_boxes, d_offsets, d_hits, (uint64_t)capacity, boxBase, cnt);
-    });
-  });
-}
-
-// Triangle queries (mi_tri_query_device): whether a primitive touches each triangle (MI_TRI_ANY, n bytes) or how many do
-// (MI_TRI_COUNT, n uint32_t), one thread per triangle (contact_kernels.hpp). full_stats picks the instrumented build; no other
+// Touch queries - the box queries (Q = BoxTouch, box_kernels.hpp) and the triangle queries (Q = TriTouch, contact_kernels.hpp); the
+// entry's name and the items' noun for what launchFrame refuses come from Q. full_stats picks the instrumented build; no other
 // option applies.
-void launchTriQuery(mi_scene& S, int kind, const mi_tri* d_tris, void* d_out, size_t n, hipStream_t stream) {
-  launchFrame(S, "mi_tri_query", "triangles", n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
-    withFlag(kind == MI_TRI_COUNT, [&](auto count) { pickBuild<false, false>(S.opt, [&](auto b) {
-      hipLaunchKernelGGL((tri_query_kernel<decltype(count)::value, decltype(b)::stats>), grid, block, 0, stream, dsv, d_tris, d_out, cnt);
+// mi_box_query_device / mi_tri_query_device: whether a primitive touches each item (kind 0, MI_BOX_ANY = MI_TRI_ANY: n bytes) or
+// how many do (kind 1, MI_BOX_COUNT = MI_TRI_COUNT: n uint32_t), one thread per item (touch_query_kernel).
+static_assert((int)MI_BOX_COUNT == (int)MI_TRI_COUNT, "launchTouchQuery takes either family's kind");
+template <class Q>
+void launchTouchQuery(mi_scene& S, int kind, const typename Q::Item* d_items, void* d_out, size_t n, hipStream_t stream) {
+  launchFrame(S, Q::kQuery, Q::kNoun, n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
+    withFlag(kind == MI_BOX_COUNT, [&](auto count) { pickBuild<false, false>(S.opt, [&](auto b) {
+      hipLaunchKernelGGL((touch_query_kernel<Q, decltype(count)::value, decltype(b)::stats>), grid, block, 0, stream, dsv, d_items, d_out, cnt);
     }); });
   });
 }
 
-// Contact lists, step 1 (mi_tri_offsets_device): d_incl[i] = the primitives touching triangles 0 .. i. tri_count_kernel writes the
-// counts as 64 bits, scanOffsets sums them.
-void launchTriOffsets(mi_scene& S, const mi_tri* d_tris, uint64_t* d_incl, size_t n, hipStream_t stream) {
-  launchFrame(S, "mi_tri_offsets", "triangles", n, stream, [&](LaunchSlot& slot, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
+// Box and contact lists, step 1 (mi_box_offsets_device / mi_tri_offsets_device): d_incl[i] = the primitives touching items 0 .. i.
+// touch_count_kernel writes the counts as 64 bits, scanOffsets sums them.
+template <class Q>
+void launchTouchOffsets(mi_scene& S, const typename Q::Item* d_items, uint64_t* d_incl, size_t n, hipStream_t stream) {
+  launchFrame(S, Q::kOffsets, Q::kNoun, n, stream, [&](LaunchSlot& slot, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
     pickBuild<false, false>(S.opt, [&](auto b) {
-      hipLaunchKernelGGL(tri_count_kernel<decltype(b)::stats>, grid, block, 0, stream, dsv, d_tris, d_incl, cnt);
+      hipLaunchKernelGGL((touch_count_kernel<Q, decltype(b)::stats>), grid, block, 0, stream, dsv, d_items, d_incl, cnt);
     });
     HIP_CHECK(hipGetLastError());
     scanOffsets(slot, d_incl, cnt, stream);
   });
 }
 
-// Contact lists, step 2 (mi_tri_fill_device): tri_fill_kernel, one thread per triangle. triBase: the index of the launch's first
-// triangle in the caller's numbering (the host entry's batches).
-void launchTriFill(mi_scene& S, const mi_tri* d_tris, const uint64_t* d_offsets, mi_contact* d_hits, size_t capacity, uint32_t triBase, size_t n, hipStream_t stream) {
-  launchFrame(S, "mi_tri_fill", "triangles", n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
+// Box and contact lists, step 2 (mi_box_fill_device / mi_tri_fill_device): touch_fill_kernel, one thread per item. itemBase: the
+// index of the launch's first item in the caller's numbering (the host entry's batches).
+template <class Q>
+void launchTouchFill(mi_scene& S, const typename Q::Item* d_items, const uint64_t* d_offsets, typename Q::Record* d_hits, size_t capacity, uint32_t itemBase, size_t n, hipStream_t stream) {
+  launchFrame(S, Q::kFill, Q::kNoun, n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
     pickBuild<false, false>(S.opt, [&](auto b) {
-      hipLaunchKernelGGL(tri_fill_kernel<decltype(b)::stats>, grid, block, 0, stream, dsv, d_tris, d_offsets, d_hits, (uint64_t)capacity, triBase, cnt);
+      hipLaunchKernelGGL((touch_fill_kernel<Q, decltype(b)::stats>), grid, block, 0, stream, dsv, d_items, d_offsets, d_hits, (uint64_t)capacity, itemBase, cnt);
     });
   });
 }
@@ -412,7 +386,7 @@ void listFillHost(mi_scene* scene, const void* in, size_t inSize, const uint64_t
       for (size_t j = 0; j < cnt; ++j) {
         const uint64_t lo = offsets[first + j], hi = offsets[first + j + 1];
         ascending = ascending && hi >= lo;
-        loc[j + 1] = loc[j] + ((hi > lo && lo < capacity) ? std::min<uint64_t>(hi, capacity) - lo : 0);
+        loc[j + 1] = loc[j] + segment_len(lo, hi, capacity);
       }
       const size_t need = (size_t)loc[cnt];
       if (scene->listHitsCap[i] < need) {
@@ -604,7 +578,7 @@ int mi_near_fill(mi_scene* scene, const mi_point* points, const uint64_t* offset
 int mi_box_query_device(mi_scene* scene, int kind, const void* d_boxes, void* d_out, size_t n, void* hip_stream) {
   if (boxQueryBad("mi_box_query_device", scene, kind, d_boxes, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
   if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchBoxQuery(*scene, kind, static_cast<const mi_box*>(d_boxes), d_out, n, (hipStream_t)hip_stream); });
+  return deviceEntry(scene, [&] { launchTouchQuery<BoxTouch>(*scene, kind, static_cast<const mi_box*>(d_boxes), d_out, n, (hipStream_t)hip_stream); });
 }
 
 int mi_box_query(mi_scene* scene, int kind, const mi_box* boxes, void* out, size_t n) {
@@ -614,7 +588,7 @@ int mi_box_query(mi_scene* scene, int kind, const mi_box* boxes, void* out, size
   if (!batch) return MI_ERR_INVALID_ARG;
   return guarded([&] {
     pipelinedQuery(scene, boxes, sizeof(mi_box), out, kind == MI_BOX_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchBoxQuery(*scene, kind, static_cast<const mi_box*>(d_in), d_out, cnt, st);
+      launchTouchQuery<BoxTouch>(*scene, kind, static_cast<const mi_box*>(d_in), d_out, cnt, st);
     });
   });
 }
@@ -624,14 +598,14 @@ int mi_box_offsets_device(mi_scene* scene, const void* d_boxes, uint64_t* d_offs
   if (n == 0) return MI_OK;
   return deviceEntry(scene, [&] {
     HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
-    launchBoxOffsets(*scene, static_cast<const mi_box*>(d_boxes), d_offsets + 1, n, (hipStream_t)hip_stream);
+    launchTouchOffsets<BoxTouch>(*scene, static_cast<const mi_box*>(d_boxes), d_offsets + 1, n, (hipStream_t)hip_stream);
   });
 }
 
 int mi_box_fill_device(mi_scene* scene, const void* d_boxes, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream) {
   if (listQueryBad("mi_box_fill_device", scene, "boxes", kBoxes16, d_boxes, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
   if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchBoxFill(*scene, static_cast<const mi_box*>(d_boxes), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
+  return deviceEntry(scene, [&] { launchTouchFill<BoxTouch>(*scene, static_cast<const mi_box*>(d_boxes), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
 }
 
 int mi_box_offsets(mi_scene* scene, const mi_box* boxes, uint64_t* offsets, size_t n) {
@@ -641,7 +615,7 @@ int mi_box_offsets(mi_scene* scene, const mi_box* boxes, uint64_t* offsets, size
   if (!batch) return MI_ERR_INVALID_ARG;
   return guarded([&] {
     offsetsHost(scene, boxes, sizeof(mi_box), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchBoxOffsets(*scene, static_cast<const mi_box*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
+      launchTouchOffsets<BoxTouch>(*scene, static_cast<const mi_box*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
     });
   });
 }
@@ -653,7 +627,7 @@ int mi_box_fill(mi_scene* scene, const mi_box* boxes, const uint64_t* offsets, m
   if (!batch) return MI_ERR_INVALID_ARG;
   return guarded([&] {
     listFillHost(scene, boxes, sizeof(mi_box), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_overlap* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
-      launchBoxFill(*scene, static_cast<const mi_box*>(d_in), d_off, d_hits, cap, base, cnt, st);
+      launchTouchFill<BoxTouch>(*scene, static_cast<const mi_box*>(d_in), d_off, d_hits, cap, base, cnt, st);
     });
   });
 }
@@ -661,7 +635,7 @@ int mi_box_fill(mi_scene* scene, const mi_box* boxes, const uint64_t* offsets, m
 int mi_tri_query_device(mi_scene* scene, int kind, const void* d_tris, void* d_out, size_t n, void* hip_stream) {
   if (triQueryBad("mi_tri_query_device", scene, kind, d_tris, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
   if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTriQuery(*scene, kind, static_cast<const mi_tri*>(d_tris), d_out, n, (hipStream_t)hip_stream); });
+  return deviceEntry(scene, [&] { launchTouchQuery<TriTouch>(*scene, kind, static_cast<const mi_tri*>(d_tris), d_out, n, (hipStream_t)hip_stream); });
 }
 
 int mi_tri_query(mi_scene* scene, int kind, const mi_tri* tris, void* out, size_t n) {
@@ -671,7 +645,7 @@ int mi_tri_query(mi_scene* scene, int kind, const mi_tri* tris, void* out, size_
   if (!batch) return MI_ERR_INVALID_ARG;
   return guarded([&] {
     pipelinedQuery(scene, tris, sizeof(mi_tri), out, kind == MI_TRI_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTriQuery(*scene, kind, static_cast<const mi_tri*>(d_in), d_out, cnt, st);
+      launchTouchQuery<TriTouch>(*scene, kind, static_cast<const mi_tri*>(d_in), d_out, cnt, st);
     });
   });
 }
@@ -681,14 +655,14 @@ int mi_tri_offsets_device(mi_scene* scene, const void* d_tris, uint64_t* d_offse
   if (n == 0) return MI_OK;
   return deviceEntry(scene, [&] {
     HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
-    launchTriOffsets(*scene, static_cast<const mi_tri*>(d_tris), d_offsets + 1, n, (hipStream_t)hip_stream);
+    launchTouchOffsets<TriTouch>(*scene, static_cast<const mi_tri*>(d_tris), d_offsets + 1, n, (hipStream_t)hip_stream);
   });
 }
 
 int mi_tri_fill_device(mi_scene* scene, const void* d_tris, const uint64_t* d_offsets, mi_contact* d_hits, size_t capacity, size_t n, void* hip_stream) {
   if (listQueryBad("mi_tri_fill_device", scene, "triangles", kTris4, d_tris, d_offsets, d_hits, true, n, kMaxWorkItems, 4)) return MI_ERR_INVALID_ARG;
   if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTriFill(*scene, static_cast<const mi_tri*>(d_tris), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
+  return deviceEntry(scene, [&] { launchTouchFill<TriTouch>(*scene, static_cast<const mi_tri*>(d_tris), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
 }
 
 int mi_tri_offsets(mi_scene* scene, const mi_tri* tris, uint64_t* offsets, size_t n) {
@@ -698,7 +672,7 @@ int mi_tri_offsets(mi_scene* scene, const mi_tri* tris, uint64_t* offsets, size_
   if (!batch) return MI_ERR_INVALID_ARG;
   return guarded([&] {
     offsetsHost(scene, tris, sizeof(mi_tri), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTriOffsets(*scene, static_cast<const mi_tri*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
+      launchTouchOffsets<TriTouch>(*scene, static_cast<const mi_tri*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
     });
   });
 }
@@ -710,7 +684,7 @@ int mi_tri_fill(mi_scene* scene, const mi_tri* tris, const uint64_t* offsets, mi
   if (!batch) return MI_ERR_INVALID_ARG;
   return guarded([&] {
     listFillHost(scene, tris, sizeof(mi_tri), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_contact* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
-      launchTriFill(*scene, static_cast<const mi_tri*>(d_in), d_off, d_hits, cap, base, cnt, st);
+      launchTouchFill<TriTouch>(*scene, static_cast<const mi_tri*>(d_in), d_off, d_hits, cap, base, cnt, st);
     });
   });
 }
