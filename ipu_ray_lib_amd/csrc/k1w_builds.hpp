@@ -51,7 +51,17 @@ template <class B> struct K1wBase {
   static constexpr bool firstInSetup = B::slots != 0 && B::merge && !B::spec && !B::fast && !B::ldsNodes && !B::df && !B::hot;      // (see the cast set-up of the merged SHADE / GEN turn)
   static constexpr bool phInNode = !B::spec;                    // a lane's phase is read off its node word (SPEC lanes wait for a primitive test while their node walks on)
   static constexpr bool coordsFromStream = B::waves >= 7;       // seven workgroups' LDS in a unit: 21 cold words, the pixel's (row, col) fetched again by every GEN
-  static constexpr uint32_t coldWords = B::waves >= 7 ? 21u : 23u;
+  // lastThrough (round 20): what only the hit record of a pixel's LAST sample reads - the last hit's leaf and distance, the normal carried from
+  // bounce to bounce - is not kept in LDS for every sample; a lane on its pixel's last sample writes those fields of the record as they arise
+  // (trace_wavefront.hpp). 18 cold words, not 23. ldsCounts: casts and paths are not counted per turn in registers; a lane that ends a path adds its
+  // bounce count and 1 to two LDS words of its wave. The six-wave plain-render builds of the default form count that way (K1wPlain*, K1wHot*,
+  // K1wFast); the HOT builds among them also write the last sample through - their staged prefix grows from 316 to 793 nodes for it. The
+  // 256-thread builds have no prefix to grow and measured 1.4 % SLOWER with the write-through (K1wPlainRot, K1wFast; K1wFast also spills four
+  // vector registers with it): they keep their 23 words. The NIF-slot builds, the instrumented and four-wave builds, the two-turn form and
+  // K1wWaves5 / K1wWaves7 keep their words and their per-turn counts: they were not measured (profiles/r20_k1w_cold_state.txt).
+  static constexpr bool ldsCounts = B::slots == 0 && B::waves == 6 && B::fixedTune && B::merge && !B::stats && !B::spec && !B::ldsNodes;
+  static constexpr bool lastThrough = B::hot && B::ldsCounts;
+  static constexpr uint32_t coldWords = B::lastThrough ? 18u : B::waves >= 7 ? 21u : 23u;
   static constexpr bool leafFrame = !B::bary && B::slots == 0;  // a diffuse bounce loads its tangent frame from the leaf's record
   static constexpr int minBlocksPerUnit = ((B::block == 256 || B::hot) && B::waves > 4) ? B::waves : 1;       // (of __launch_bounds__)
   static constexpr bool wellFormed = !B::hot || (B::merge && !B::spec && !B::fast && !B::ldsNodes && !B::df);   // HOT is a form of the default kernel's plain-render builds
@@ -69,7 +79,7 @@ struct K1wPlainRot : K1wDefaultForm<K1wPlainRot> { static constexpr K1wId id = K
 struct K1wSlotsBary : K1wDefaultForm<K1wSlotsBary> { static constexpr K1wId id = K1wId::SlotsBary; static constexpr int slots = 1; };
 struct K1wSlotsLean : K1wDefaultForm<K1wSlotsLean> { static constexpr K1wId id = K1wId::SlotsLean; static constexpr int slots = 1; static constexpr bool bary = false; };
 struct K1wSlotsRot : K1wDefaultForm<K1wSlotsRot> { static constexpr K1wId id = K1wId::SlotsRot; static constexpr int slots = 1; static constexpr bool bary = false, rot = true; };
-// ... with hot nodes (Lean has none). 768 threads: two workgroups per compute unit, six waves per SIMD - the larger the workgroup, the larger the prefix its copies of the cold state leave room for (256 x 6: 68 nodes, 512 x 3: 172, 768 x 2: 316)
+// ... with hot nodes (Lean has none). 768 threads: two workgroups per compute unit, six waves per SIMD - the larger the workgroup, the larger the prefix its copies of the cold state leave room for (with 23 cold words 256 x 6: 68 nodes, 512 x 3: 172, 768 x 2: 316; with today's 18 words 768 x 2: 793)
 struct K1wHotBary : K1wDefaultForm<K1wHotBary> { static constexpr K1wId id = K1wId::HotBary; static constexpr int block = 768; static constexpr bool hot = true; };
 struct K1wHotRot : K1wDefaultForm<K1wHotRot> { static constexpr K1wId id = K1wId::HotRot; static constexpr int block = 768; static constexpr bool bary = false, rot = true, hot = true; };
 struct K1wFast : K1wDefaultForm<K1wFast> { static constexpr K1wId id = K1wId::Fast; static constexpr bool fast = true; };

@@ -332,7 +332,22 @@ MI_HD void sincos_deg_table_turn(float th, const float* tbl, float& s, float& c)
 
 // ---- xoroshiro128** / splitmix64: include/xoshiro.hpp:18-80 ------------------------------------------
 struct Rng { uint64_t s0, s1; };
-MI_HD uint64_t rotl64(uint64_t x, int k) { return (x << k) | (x >> (64 - k)); }
+// A 64-bit rotation by a constant 0 < k < 64, k != 32, on the two 32-bit halves: k >= 32 swaps the halves, then each half of the result is
+// 32 bits cut out of a pair of halves - alignbit(a, b, s), the low word of (a : b) >> s. One v_alignbit_b32 per half on the device, where
+// hipcc compiles (x << k) | (x >> (64 - k)) as a 64-bit shift, a 32-bit shift and an OR (host/rotl_halves_check.cpp holds the two forms
+// against each other).
+MI_HD uint32_t alignbit(uint32_t a, uint32_t b, uint32_t s) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_alignbit(a, b, s);
+#else
+  return (uint32_t)((((uint64_t)a << 32) | b) >> s);
+#endif
+}
+MI_HD uint64_t rotl64(uint64_t x, int k) {
+  const uint32_t xl = (uint32_t)x, xh = (uint32_t)(x >> 32);
+  const uint32_t lo = k >= 32 ? xh : xl, hi = k >= 32 ? xl : xh, s = 32u - ((uint32_t)k & 31u);
+  return ((uint64_t)alignbit(hi, lo, s) << 32) | alignbit(lo, hi, s);
+}
 MI_HD uint64_t splitmix64(uint64_t z) {
   z += 0x9e3779b97f4a7c15ull;
   z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;

@@ -192,33 +192,50 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
   Hit hit; hit.t = kInf; hit.leaf = 0xFFFFFFFFu; hit.geomID = 0xFFFFu; hit.b0 = hit.b1 = hit.b2 = 0.f;
   uint32_t oFlags = 0;
   bool exactSlab = false;
-  // Cold per-lane state lives in LDS (23 dwords per lane, [word][thread] so a wave's accesses are conflict-free): the
+  // Cold per-lane state lives in LDS (23 dwords per lane by name, [word][thread] so a wave's accesses are conflict-free): the
   // pixel's stream index (0), its (row, col) (1, 2) and its running rgb sum (3..5) are touched once per path or per
   // pixel, and holding them in VGPRs made the 96-register build spill inside the traversal loop.
   // A build for seven waves per SIMD must fit seven workgroups' LDS into a compute unit: it keeps 21 words, not 23 - the pixel's
   // (row, col) (1, 2) are fetched again from the stream's compact copy by every GEN instead (8 bytes, an L2 hit: the lane's 64
   // samples of one (pixel, segment) unit read the same address).
+  // LAST_THROUGH (the HOT builds, k1w_builds.hpp) keeps 18: the last hit's leaf and distance (6, 7) and the normal
+  // (18..20) feed nothing but the hit record a pixel's LAST sample leaves - prim_id, geom_id, t_max, normal; every other use of a normal
+  // takes one computed in the same turn - so a lane on that sample writes those four fields into rays[pixel].h as they arise (GEN: the
+  // empty record's; a SHADE with a hit: the hit's; a SHADE without: t_max alone, the ids and the normal of the bounce before stand) and the
+  // other samples carry nothing. No other work unit touches a pixel's h during a launch (FETCH reads u, v and rgb), and a lane's stores
+  // to one address arrive in its order. The five words were a fifth of what bounds the staged prefix of the HOT builds.
+  constexpr bool LAST_THROUGH = Build::lastThrough, LDS_COUNTS = Build::ldsCounts;
+  static_assert(!LAST_THROUGH || (MERGE && SLOTS == 0 && !Build::coordsFromStream), "the last sample's record is written through by the merged turn of the plain-render builds");
+  static_assert(!LDS_COUNTS || (MERGE && !STATS), "paths are counted where they end by the merged turn alone");
   __shared__ uint32_t coldLds[Build::coldWords * BLOCK];   // + the last hit's leaf and distance (6, 7) + the path state (8..22)
-  auto coldU = [&](uint32_t w) -> uint32_t& { return coldLds[((Build::coordsFromStream && w > 2u) ? w - 2u : w) * BLOCK + threadIdx.x]; };
-  auto coldF = [&](uint32_t w) -> float& { return reinterpret_cast<float*>(coldLds)[((Build::coordsFromStream && w > 2u) ? w - 2u : w) * BLOCK + threadIdx.x]; };
+  auto coldAt = [](uint32_t w) -> uint32_t { return LAST_THROUGH ? (w < 6u ? w : w < 18u ? w - 2u : w - 5u) : (Build::coordsFromStream && w > 2u) ? w - 2u : w; };      // (every word is named by a literal)
+  auto coldU = [&](uint32_t w) -> uint32_t& { return coldLds[coldAt(w) * BLOCK + threadIdx.x]; };
+  auto coldF = [&](uint32_t w) -> float& { return reinterpret_cast<float*>(coldLds)[coldAt(w) * BLOCK + threadIdx.x]; };
 
   auto getPix = [&]() -> uint32_t { return coldU(0); };
   // Path state that only SHADE / GEN / FETCH touch - the RNG, radiance, throughput, normal, bounce and sample
   // counters - is loaded at the top of those phases and stored at their end, so it holds no registers while the
-  // wave traverses (words 8..22).
+  // wave traverses (words 8..22; without 18..20 in the LAST_THROUGH builds).
   auto pathLoad = [&]() {
     rng.s0 = (uint64_t)coldU(8) | ((uint64_t)coldU(9) << 32); rng.s1 = (uint64_t)coldU(10) | ((uint64_t)coldU(11) << 32);
-    color = mk(coldF(12), coldF(13), coldF(14)); tp = mk(coldF(15), coldF(16), coldF(17)); nrm = mk(coldF(18), coldF(19), coldF(20));
+    color = mk(coldF(12), coldF(13), coldF(14)); tp = mk(coldF(15), coldF(16), coldF(17));
+    if constexpr (!LAST_THROUGH) nrm = mk(coldF(18), coldF(19), coldF(20));
     { const uint32_t w = coldU(21); bounce = w >> 2; oFlags = w & 3u; } sample = coldU(22);     // (MI_FLAG_ERROR | MI_FLAG_ESCAPED ride in the bounce word: the host sends path lengths of 2^30 and more to K1)
   };
   auto pathStore = [&]() {
     coldU(8) = (uint32_t)rng.s0; coldU(9) = (uint32_t)(rng.s0 >> 32); coldU(10) = (uint32_t)rng.s1; coldU(11) = (uint32_t)(rng.s1 >> 32);
     coldF(12) = color.x; coldF(13) = color.y; coldF(14) = color.z; coldF(15) = tp.x; coldF(16) = tp.y; coldF(17) = tp.z;
-    coldF(18) = nrm.x; coldF(19) = nrm.y; coldF(20) = nrm.z;
+    if constexpr (!LAST_THROUGH) { coldF(18) = nrm.x; coldF(19) = nrm.y; coldF(20) = nrm.z; }
     coldU(21) = (bounce << 2) | oFlags; coldU(22) = sample;
   };
   CastStats cs = {0, 0};
-  uint32_t casts = 0, paths = 0;       // wave-uniform: counted per turn from the turn's ballots, so they live in scalar registers
+  // Wave-uniform, counted per turn from the turn's ballots. LDS_COUNTS (the six-wave plain-render builds): hipcc keeps the two sums in vector registers - the
+  // build has no scalar register to spare - and re-ballots the turn's masks for them. Every cast is resolved by exactly one SHADE, so a
+  // path's casts are its bounce count when it ends: the lane that ends a path adds that, and 1, to two LDS words of its wave.
+  uint32_t casts = 0, paths = 0;
+  __shared__ uint32_t waveCounts[LDS_COUNTS ? 2 * (BLOCK / 64) : 1];      // [wave][casts, paths]
+  auto waveCount = [&](uint32_t which) -> uint32_t* { return &waveCounts[LDS_COUNTS ? 2u * (threadIdx.x >> 6) + which : 0u]; };
+  if (LDS_COUNTS && lane < 2u) *waveCount(lane) = 0u;      // (the wave's own words: its LDS operations run in order)
   // STATS only: per-wave phase executions and the lanes that were active in them (wave-uniform values)
   uint32_t itN = 0, itL = 0, itS = 0, itG = 0, lnN = 0, lnL = 0, lnS = 0, lnG = 0;
   uint32_t itH = 0, lnH = 0, itC = 0, lnC = 0;      // (instrumented HOT build) box-test steps that ran from LDS and their lanes, the steps that ran from global memory and theirs
@@ -616,9 +633,15 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
             }
           }
           hit.geomID = leaf_geom(L);
-          coldU(6) = hit.leaf; coldF(7) = hit.t;
+          if constexpr (!LAST_THROUGH) { coldU(6) = hit.leaf; coldF(7) = hit.t; }
           o = o + d * hit.t;
           nrm = hit_normal(sc, hit, o);
+          if constexpr (LAST_THROUGH) {
+            if (sample + 1u >= spp) {      // the pixel's last sample: the hit as the record shows it
+              mi_hit_record* h = &rays[getPix()].h;
+              h->r.t_max = hit.t; h->prim_id = L.primID; h->normal = {nrm.x, nrm.y, nrm.z}; h->geom_id = (uint16_t)hit.geomID;      // (a 16-bit store: flags shares the word)
+            }
+          }
           // (two loads under a wave-uniform branch: as a select of the two addresses hipcc made FLAT loads of it, which go through the
           // texture addresser as well as the LDS and wait on both counters)
           mi_material mat;
@@ -646,7 +669,8 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
             oFlags |= MI_FLAG_ERROR;
           }
         } else {
-          coldF(7) = kInf;
+          if constexpr (LAST_THROUGH) { if (sample + 1u >= spp) rays[getPix()].h.r.t_max = kInf; }      // (the ids and the normal of the bounce before stand)
+          else coldF(7) = kInf;
           oFlags |= MI_FLAG_ESCAPED;
           terminated = true;
         }
@@ -666,6 +690,10 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
             envSlot = (uint32_t)q;
             if (!envRay) ex.u[q] = -1.f;
           } else { coldF(3) = coldF(3) + color.x; coldF(4) = coldF(4) + color.y; coldF(5) = coldF(5) + color.z; }
+          if constexpr (LDS_COUNTS) {      // (no value returned: two ds_add_u32)
+            __hip_atomic_fetch_add(waveCount(0), bounce, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(waveCount(1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
           pathEnd = true;
           ++sample;
           const bool more = segd ? ((sample & segMask) != 0u && sample < spp) : (sample < spp);
@@ -682,6 +710,14 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
               part[0] = coldF(3); part[1] = coldF(4); part[2] = coldF(5);
             } else
             if (!slots) res->rgb = {coldF(3), coldF(4), coldF(5)};
+            if constexpr (LAST_THROUGH) {
+              // the rest of the record: t_max, prim_id, normal and geom_id were written as this sample went
+              mi_hit_record* h = &res->h;
+              h->r.origin = {o.x, o.y, o.z}; h->r.t_min = 0.f;
+              h->r.direction = {d.x, d.y, d.z};
+              h->throughput = {tp.x, tp.y, tp.z};
+              h->flags = (uint16_t)oFlags;      // (a 16-bit store: geom_id shares the word)
+            } else {
             uint32_t oPrim = MI_INVALID_PRIM, oGeom = MI_INVALID_GEOM;
             const uint32_t lastLeaf = coldU(6);
             if (lastLeaf != 0xFFFFFFFFu) { const GLeaf LL = sc.leaves[lastLeaf]; oPrim = LL.primID; oGeom = leaf_geom(LL); }
@@ -693,6 +729,7 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
             hr.throughput = {tp.x, tp.y, tp.z};
             hr.geom_id = (uint16_t)oGeom; hr.flags = (uint16_t)oFlags;
             res->h = hr;
+            }
             park(PH_FETCH);
           }
         } else {
@@ -712,7 +749,12 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
         d = pixel_to_ray_dir(jc, jr, sc.imageWidth, sc.imageHeight, sc.tanTheta);
         o = mk(0.f, 0.f, 0.f);
         nrm = mk(0.f, 0.f, 1.f);
-        coldU(6) = 0xFFFFFFFFu; coldF(7) = kInf;
+        if constexpr (LAST_THROUGH) {
+          if (sample + 1u >= spp) {      // the pixel's last sample starts from the empty record (HitRecord ctor, geometry.hpp:236-242)
+            mi_hit_record* h = &rays[getPix()].h;
+            h->r.t_max = kInf; h->prim_id = MI_INVALID_PRIM; h->normal = {0.f, 0.f, 1.f}; h->geom_id = (uint16_t)MI_INVALID_GEOM;
+          }
+        } else { coldU(6) = 0xFFFFFFFFu; coldF(7) = kInf; }
         oFlags = 0;
         tp = mk(1.f, 1.f, 1.f);
         color = mk(0.f, 0.f, 0.f);
@@ -758,8 +800,10 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
         }
       }
       if (wasShade || wasGen) pathStore();
-      paths += (uint32_t)__popcll(__ballot(pathEnd));
-      casts += (uint32_t)__popcll(__ballot(setup));
+      if constexpr (!LDS_COUNTS) {
+        paths += (uint32_t)__popcll(__ballot(pathEnd));
+        casts += (uint32_t)__popcll(__ballot(setup));
+      }
       if (STATS) tShade += __builtin_amdgcn_s_memtime() - tq1;
     } else if (run == 2) {
       // ---------------- SHADE: traversal of bounce `bounce` is complete ----------------
@@ -909,6 +953,7 @@ __global__ void __launch_bounds__(Build::block, Build::minBlocksPerUnit) path_tr
     const uint32_t padEnd = min(envEnd, (envNext + kEnvBlock - 1u) & ~(kEnvBlock - 1u));
     for (uint32_t k = envNext + lane; k < envEnd; k += 64u) ex.index[k] = k < padEnd ? envFill : kEnvHole;
   }
+  if constexpr (LDS_COUNTS) { casts = *waveCount(0); paths = *waveCount(1); }
   flush_stats(sc, lane == 0 ? casts : 0u, cs, lane == 0 ? paths : 0u);
   if (STATS && HOT) {
     for (int off = 32; off > 0; off >>= 1) visHot += __shfl_down(visHot, off);
