@@ -529,6 +529,79 @@ int mi_tri_fill_device(mi_scene* scene, const void* d_tris, const uint64_t* d_of
 int mi_tri_offsets(mi_scene* scene, const mi_tri* tris, uint64_t* offsets /* n + 1 */, size_t n);
 int mi_tri_fill(mi_scene* scene, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity, size_t n);
 
+/* Oriented-box queries: the primitives of the scene's CURRENT BVH that TOUCH each of n caller-supplied ROTATED boxes - a rigid body's
+ * bounding box, a robot link, a beam, a selection volume, a voxel of a rotated grid, a portal (FCL's and Bullet's OBB, Open3D's
+ * OrientedBoundingBox). A caller with such a box had to ask mi_box_* about its world bounds and filter; a long box on a diagonal
+ * lists many times what it touches. Whether there is one (MI_OBOX_ANY), how many (MI_OBOX_COUNT), or which: two steps as for the box
+ * lists - the offsets of the boxes' segments, then the fill of a buffer the caller sized from them.
+ * Touching is CLOSED everywhere: contact counts. Queries see SURFACES, as everywhere in this library.
+ * The oriented box: centre[3], half[3] (the half extents along the box's own axes) and quat[4] = x, y, z, w, the rotation that turns
+ * an axis-aligned box into this one (U, V, W below are the box's axes in world coordinates); reserved0 and reserved1 are not read. The quaternion NEED NOT BE UNIT: the frame below is orthogonal
+ * for any non-zero quaternion, which is why the orientation is a quaternion and not nine floats a caller could get wrong. The record
+ * is mi_overlap: the ids as mi_point_hit carries them, flags = 0 or MI_OVERLAP_CONTAINED, box = the index of the query the record
+ * belongs to, reserved = 0. The empty record is {MI_INVALID_PRIM, MI_INVALID_GEOM, MI_FLAG_ESCAPED, box, 0}.
+ * Arithmetic: binary32, one rounding per operation in the order written below, no contraction, correctly rounded divide (and sqrt,
+ * in the disc's bounds); dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z. Every separation is a strict compare that a NaN fails: a NaN
+ * never separates, and a query so large that its products overflow errs towards listing. One definition
+ * (ipu_ray_lib_amd/csrc/obox_math.hpp, over box_math.hpp) serves the kernels and the host twins (mi_scene_host.h), which return the
+ * same bytes.
+ * Validity: a query is valid when all ten floats are finite, half >= 0 on every axis, qq = ((x x + y y) + z z) + w w > 0 and
+ *   s = 2.f / qq is finite. Any other query is not walked and finds nothing; so does an empty scene. A zero half extent is legal: a
+ *   rectangle, a segment, a point. The two ends of the quaternion's range are not alike: a norm below about 1e-19 makes s overflow and
+ *   the query invalid, but a finite quaternion whose SQUARED NORM overflows (a norm above about 1.8e19) gives qq = +inf and s = 0, which
+ *   is finite: the query is valid, every product of the frame is 0 and the frame is the IDENTITY, whatever rotation the quaternion
+ *   stood for. Nothing is rescaled. A caller whose quaternions can be that large scales them down first (any positive scale keeps the
+ *   rotation).
+ * The frame: xs = x s, ys = y s, zs = z s; wx = w xs, wy = w ys, wz = w zs; xx = x xs, xy = x ys, xz = x zs, yy = y ys, yz = y zs,
+ *   zz = z zs; U = (1 - (yy + zz), xy + wz, xz - wy), V = (xy - wz, 1 - (xx + zz), yz + wx), W = (xz + wy, yz - wx, 1 - (xx + yy)).
+ *   A point p has the local coordinates (dot(U, d), dot(V, d), dot(W, d)), d = p - centre; a direction rotates the same way without
+ *   the subtraction.
+ * The query's world bounds: ext.x = (|U.x| half.x + |V.x| half.y) + |W.x| half.z, likewise y and z; qmn = centre - ext,
+ *   qmx = centre + ext.
+ * The bounds test obox_meets_bounds(mn, mx), used at every node and, unchanged, as the first step at every leaf on the primitive's
+ *   own bounds: first the six closed compares of mi_box_* against [qmn, qmx] (mn <= qmx && mx >= qmn on all axes). Then
+ *   dl = mn - centre, dh = mx - centre, and for each axis A of U, V, W with its half extent hA: up = (t0 + t1) + t2 with
+ *   t_k = A_k > 0 ? A_k dh_k : A_k dl_k; dn the same with dl and dh exchanged; the axis separates when dn > hA || up < -hA. The
+ *   bounds are met when the six compares hold and no axis separates. The test has no other arithmetic.
+ * The walk is the stackless preorder walk of the box queries. A node is entered when obox_meets_bounds of its box holds, else passed.
+ * At a leaf so reached the primitive is tested; MI_OBOX_ANY stops at the first one that touches.
+ * Primitive test, two steps. 1: obox_meets_bounds on the primitive's OWN bounds - those mi_box_* defines for that kind of primitive.
+ *   2: mi_box_*'s test of that kind, exactly as it stands, in the box's frame with lo = -half, hi = half: a triangle's three vertices,
+ *   a sphere's centre, a disc's centre and normal are moved into the frame first (radius and r2 are kept). There cb is an exact zero
+ *   and h is exactly half. MI_OVERLAP_CONTAINED is what that test reports: for a triangle it is exact - all three moved vertices lie
+ *   in the box, faces included -, for a sphere and a disc it is decided by their bounds about the moved centre; the disc stays
+ *   conservative as everywhere else. A flat or collapsed box errs towards listing; mi_tri_* is the exact answer for flat queries.
+ * Order: records are sorted by the key (geom_id, prim_id), ascending; keys are unique within a query. This IS the definition: a
+ * segment shorter than the box's count holds the len smallest keys, and a list is the same bytes after a refit, a rebuild or
+ * mi_scene_set_geometry of the same contents. The node test has arithmetic, so this needs an argument: fl(a - c), fl(x a) for a fixed
+ * x and fl(a + b) are monotone in a and b, so for bounds A that contain bounds B every t_k of up is no smaller and every t_k of dn no
+ * larger for A than for B, and so are the sums as computed: up(A) >= up(B), dn(A) <= dn(B). Whatever B does not separate, A does not,
+ * and the six compares nest likewise. A node's device box contains its primitives' bounds as those functions compute them - the fact
+ * the box family rests on -, so a primitive whose own bounds pass has every ancestor's box pass, whatever tree is walked.
+ * mi_obox_query_device: d_oboxes = n mi_obox, d_out = n uint8_t, 1 = a primitive touches the box (MI_OBOX_ANY; the bytes need no
+ *   alignment) or n uint32_t counts (MI_OBOX_COUNT), DEVICE memory.
+ * mi_obox_offsets_device / mi_obox_fill_device: offsets, segments, the cut at capacity (NO record at an index >= capacity is ever
+ *   written and none outside the segment), a decreasing pair = an empty segment, which is not walked, caller-made offsets (K i = the K
+ *   smallest keys of every box, padded), overlapping segments (unspecified records inside them) and the form (a max-heap inside the
+ *   segment, heap-sorted in place) are mi_box_offsets_device's and mi_box_fill_device's, with d_hits = `capacity` mi_overlap.
+ * Host entries: the same on HOST buffers, synchronous, in batches of mi_scene_set_ray_batch oriented boxes; offsets and the `box` field
+ *   are global across batches (`box` is the index modulo 2^32). The fill shares mi_list_fill's device staging.
+ * Asynchrony, ordering against update / rebuild / set-geometry, destruction, groups, batches and stream rules: those of mi_box_*.
+ * n == 0 is a no-op. MI_ERR_INVALID_ARG, before any device work and without reading the scene: a null scene or buffer, an unknown kind
+ * ("unknown oriented-box kind"), oriented boxes or hits that are not 16-byte aligned, counts that are not 4-byte aligned, offsets that
+ * are not 8-byte aligned, or more oriented boxes in one launch (host entries: in one batch) than the 32-bit work index allows
+ * (0xFFBFFFFF).
+ * Options: none apply (one kernel, one arithmetic). Counters: nothing is added to casts or paths; under full_stats the box tests are
+ * added to "nodes visited" and the primitive tests to "leaf tests". */
+typedef struct { float centre[3]; uint32_t reserved0; float half[3]; uint32_t reserved1; float quat[4]; } mi_obox;  /* 48 B, three 16-byte loads; quat = x, y, z, w */
+enum { MI_OBOX_ANY = 0, MI_OBOX_COUNT = 1 };
+int mi_obox_query_device(mi_scene* scene, int kind, const void* d_oboxes, void* d_out, size_t n, void* hip_stream);
+int mi_obox_query(mi_scene* scene, int kind, const mi_obox* oboxes, void* out, size_t n);
+int mi_obox_offsets_device(mi_scene* scene, const void* d_oboxes, uint64_t* d_offsets /* n + 1 */, size_t n, void* hip_stream);
+int mi_obox_fill_device(mi_scene* scene, const void* d_oboxes, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream);
+int mi_obox_offsets(mi_scene* scene, const mi_obox* oboxes, uint64_t* offsets /* n + 1 */, size_t n);
+int mi_obox_fill(mi_scene* scene, const mi_obox* oboxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n);
+
 /* Geometry updates: new positions for the primitives of a live scene, the topology kept - triangles, geometry list, materials and
  * the BVH's shape - and every BVH box recomputed on the device (a refit: Embree's RTC_BUILD_QUALITY_REFIT commit, OptiX's
  * OPTIX_BUILD_OPERATION_UPDATE). Any pointer may be NULL = keep; a non-NULL array must have exactly the scene's count (a NULL array

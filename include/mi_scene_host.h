@@ -158,6 +158,26 @@ int mi_tri_offsets_host(const mi_scene_desc* desc, const mi_tri* tris, uint64_t*
 int mi_tri_fill_host(const mi_scene_desc* desc, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity,
                      size_t n, uint64_t visits[2]);
 
+/* Oriented-box queries on the host: the twins of mi_obox_query* / mi_obox_offsets* / mi_obox_fill* (mi_raylib.h, where the contract is
+ * written), over desc->bvh_nodes and desc's arrays as mi_point_query_host reads them, boxes and primitives tested through the code the
+ * kernels run (ipu_ray_lib_amd/csrc/obox_math.hpp). out: n uint8_t (MI_OBOX_ANY) or n uint32_t (MI_OBOX_COUNT); offsets: n + 1
+ * uint64_t, written by mi_obox_offsets_host (0, then the running total of the boxes' counts) and read by mi_obox_fill_host, which
+ * writes `hits` as the device writes it - the len smallest keys (geom_id, prim_id) of each box ascending, then the empty record;
+ * nothing at or past `capacity`, nothing outside a segment, a box with an empty segment not walked. No alignment asked. They return
+ * the bytes the device returns; visits (may be NULL) receives {box tests, primitive tests} summed over the n boxes, what the device
+ * adds to "nodes visited" and "leaf tests" under option full_stats. MI_ERR_INVALID_ARG, with the function's name in
+ * mi_host_last_error: a null desc, an unknown kind, a null buffer with n > 0, nodes that are not a depth-first BVH2, a leaf whose
+ * geometry, primitive or vertex index is out of range. */
+int mi_obox_query_host(const mi_scene_desc* desc, int kind, const mi_obox* oboxes, void* out, size_t n, uint64_t visits[2]);
+int mi_obox_offsets_host(const mi_scene_desc* desc, const mi_obox* oboxes, uint64_t* offsets /* n + 1 */, size_t n, uint64_t visits[2]);
+int mi_obox_fill_host(const mi_scene_desc* desc, const mi_obox* oboxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity,
+                      size_t n, uint64_t visits[2]);
+
+/* obox_meets_bounds of mi_obox_* (mi_raylib.h) on its own: 1 when the bounds [mn, mx] meet the oriented box, 0 when they do not or
+ * the query is not valid, from the function the kernels and the twins run. What the tests pin the test's monotonicity with. A null
+ * pointer gives 0. */
+int mi_obox_meets_bounds_host(const mi_obox* obox, const float mn[3], const float mx[3]);
+
 /* Sphere crossings on the host: how often the ray origin + t direction, t_min < t < t_max, crosses the shell of the sphere (centre,
  * radius2 = the squared radius) - 0, 1 or 2 -, from the definition the crossing-count kernels run (mi_count_query / mi_point_sign,
  * mi_raylib.h, where the formula is written; ipu_ray_lib_amd/csrc/cross_math.hpp). The triangle and disc tests of a crossing count

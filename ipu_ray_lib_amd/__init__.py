@@ -63,7 +63,12 @@ OVERLAP = np.dtype([("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("bo
 TRI = np.dtype([("a", "<f4", (3,)), ("b", "<f4", (3,)), ("c", "<f4", (3,))])
 CONTACT = np.dtype([("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("tri", "<u4"), ("reserved", "<u4")])
 
+# mi_obox: an oriented-box query - centre, half extents, a quaternion x, y, z, w that need not be unit; its list holds OVERLAP records
+# (IpuScene.obox_touches / count_obox_overlaps / list_obox_overlaps / obox_fill_device)
+OBOX = np.dtype([("centre", "<f4", (3,)), ("reserved0", "<u4"), ("half", "<f4", (3,)), ("reserved1", "<u4"), ("quat", "<f4", (4,))])
+
 assert CROSSING.itemsize == 16 and NEIGHBOUR.itemsize == 16
+assert OBOX.itemsize == 48
 assert TRI.itemsize == 36 and CONTACT.itemsize == 16
 assert BOX.itemsize == 32 and OVERLAP.itemsize == 16
 assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
@@ -78,6 +83,7 @@ QUERY_CLOSEST, QUERY_ANY = 0, 1
 POINT_CLOSEST, POINT_WITHIN = 0, 1
 BOX_ANY, BOX_COUNT = 0, 1
 TRI_ANY, TRI_COUNT = 0, 1
+OBOX_ANY, OBOX_COUNT = 0, 1
 OVERLAP_CONTAINED = 16      # MI_OVERLAP_CONTAINED: the primitive's own bounds lie inside the box
 SIGN_INSIDE, SIGN_DISTANCE = 0, 1
 # the ray direction of an inside test when none is given (mi_point_sign: no zero component, off the diagonals of axis-aligned boxes)
@@ -211,6 +217,10 @@ def host_lib() -> C.CDLL:
         lib.mi_tri_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_tri_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_tri_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_obox_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_obox_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_obox_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_obox_meets_bounds_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
         lib.mi_sphere_roots_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)]
@@ -329,6 +339,12 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_tri_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_tri_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         lib.mi_tri_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        lib.mi_obox_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_obox_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_obox_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_obox_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_obox_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        lib.mi_obox_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         lib.mi_point_sign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t]
         lib.mi_point_sign_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
@@ -614,6 +630,57 @@ def box_fill_host(desc: SceneDesc, boxes: np.ndarray, offsets: np.ndarray, capac
     base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
     _check_host(host_lib().mi_box_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
     return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def obox_query_host(desc: SceneDesc, kind: int, oboxes: np.ndarray):
+    """mi_obox_query_host: the host twin of IpuScene.obox_touches / .count_obox_overlaps on desc's arrays and nodes - the same bytes. Returns
+    (out, visits): a bool array (OBOX_ANY) or a uint32 array (OBOX_COUNT), and {"box_tests", "prim_evals"} summed over the oriented boxes (what
+    the device counts as nodes visited / leaf tests under option full_stats)."""
+    assert oboxes.dtype == OBOX and oboxes.ndim == 1
+    src = np.ascontiguousarray(oboxes)
+    out = np.zeros(src.size, np.uint8 if kind == OBOX_ANY else np.uint32)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_obox_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
+                                             out.ctypes.data if src.size else None, src.size, visits))
+    return (out.view(np.bool_) if kind == OBOX_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def obox_offsets_host(desc: SceneDesc, oboxes: np.ndarray):
+    """mi_obox_offsets_host: the host twin of IpuScene.obox_offsets - the same uint64 offsets. Returns (offsets, visits)."""
+    assert oboxes.dtype == OBOX and oboxes.ndim == 1
+    src = np.ascontiguousarray(oboxes)
+    offsets = np.zeros(src.size + 1, np.uint64)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_obox_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
+    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def obox_fill_host(desc: SceneDesc, oboxes: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
+    """mi_obox_fill_host: the host twin of IpuScene.obox_fill - the same bytes. Returns (recs, visits): recs is `hits` (an OVERLAP
+    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
+    nothing at or past `capacity` (None: recs.size) is written."""
+    assert oboxes.dtype == OBOX and oboxes.ndim == 1
+    src = np.ascontiguousarray(oboxes)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    assert offsets.ndim == 1 and offsets.size == src.size + 1
+    if hits is None:
+        size = int(offsets.max()) if capacity is None else int(capacity)
+        hits = np.zeros(max(size, 1), OVERLAP)[:size]
+    assert hits.dtype == OVERLAP and hits.flags["C_CONTIGUOUS"]
+    capacity = hits.size if capacity is None else int(capacity)
+    assert 0 <= capacity <= hits.size
+    visits = (C.c_uint64 * 2)()
+    base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
+    _check_host(host_lib().mi_obox_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
+    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def obox_meets_bounds_host(obox: np.ndarray, mn, mx) -> bool:
+    """mi_obox_meets_bounds_host: obox_meets_bounds of the oriented-box queries on its own - whether the bounds [mn, mx] (three floats
+    each) meet the one OBOX record `obox`; False for a query that is not valid."""
+    q = np.ascontiguousarray(obox, OBOX).reshape(1)
+    lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
+    return bool(host_lib().mi_obox_meets_bounds_host(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
 
 
 def tri_query_host(desc: SceneDesc, kind: int, tris: np.ndarray):
@@ -1270,6 +1337,88 @@ class IpuScene:
         lo = torch.stack(torch.meshgrid(axes[0][:-1], axes[1][:-1], axes[2][:-1], indexing="ij"), dim=-1).reshape(-1, 3)
         hi = torch.stack(torch.meshgrid(axes[0][1:], axes[1][1:], axes[2][1:], indexing="ij"), dim=-1).reshape(-1, 3)
         return self.box_any(lo, hi).reshape(nx, ny, nz)
+
+    # -- oriented-box queries (mi_obox_query*, mi_obox_offsets*, mi_obox_fill*): every primitive that touches each rotated box, by (geomID, primID) --
+    def _obox_query_host(self, kind: int, oboxes: np.ndarray, out: np.ndarray) -> np.ndarray:
+        src = self._source(oboxes, OBOX)
+        self._check(self._lib.mi_obox_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
+        return out
+
+    def obox_touches(self, oboxes: np.ndarray) -> np.ndarray:
+        """Whether some primitive touches each box (an OBOX array, host memory; contact counts): a bool array. Synchronous; batched
+        by setRayBatch."""
+        return self._obox_query_host(OBOX_ANY, oboxes, aligned_bytes(oboxes.size)).view(np.bool_)
+
+    def count_obox_overlaps(self, oboxes: np.ndarray) -> np.ndarray:
+        """How many primitives touch each box (an OBOX array, host memory): a uint32 array."""
+        return self._obox_query_host(OBOX_COUNT, oboxes, np.zeros(oboxes.size, np.uint32))
+
+    def obox_offsets(self, oboxes: np.ndarray) -> np.ndarray:
+        """mi_obox_offsets: a uint64 array of oboxes.size + 1 offsets - 0, then the running total of count_obox_overlaps(oboxes)."""
+        return self._offsets_host(self._lib.mi_obox_offsets, self._source(oboxes, OBOX))
+
+    def obox_fill(self, oboxes: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
+        """mi_obox_fill: the primitives touching box i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (an
+        OVERLAP array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
+        (None: hits.size) is written."""
+        return self._fill_host(self._lib.mi_obox_fill, OVERLAP, self._source(oboxes, OBOX), offsets, hits, capacity)
+
+    def list_obox_overlaps(self, oboxes: np.ndarray):
+        """Every primitive that touches each box (an OBOX array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs an
+        OVERLAP array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are box i's primitives in ascending order of (geomID,
+        primID), flags = OVERLAP_CONTAINED where the primitive lies inside the box (a triangle: exactly; mi_raylib.h). Synchronous; batched by setRayBatch."""
+        return self._all_lists(self.obox_offsets, self.obox_fill, OVERLAP, oboxes)
+
+    def first_obox_overlaps(self, oboxes: np.ndarray, k: int) -> np.ndarray:
+        """The k smallest (geomID, primID) of the primitives touching each box: an OVERLAP array [n, k]; boxes with fewer are padded
+        with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
+        return self._first_k(self.obox_fill, OVERLAP, oboxes, k)
+
+    def obox_query_device(self, kind: int, d_oboxes: int, d_out: int, n: int, stream: int = 0):
+        """mi_obox_query_device on device pointers (n OBOX records in, n bytes or n uint32 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_obox_query_device(self._h, int(kind), C.c_void_p(d_oboxes), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
+
+    def obox_offsets_device(self, d_oboxes: int, d_offsets: int, n: int, stream: int = 0):
+        """mi_obox_offsets_device on device pointers (n OBOX records in, n + 1 uint64 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_obox_offsets_device(self._h, C.c_void_p(d_oboxes), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
+
+    def obox_fill_device(self, d_oboxes: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
+        """mi_obox_fill_device on device pointers (n OBOX records and n + 1 uint64 in, `capacity` OVERLAP records out), asynchronous
+        on `stream`."""
+        self._check(self._lib.mi_obox_fill_device(self._h, C.c_void_p(d_oboxes), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
+                                                 int(n), C.c_void_p(stream)))
+
+    @staticmethod
+    def _torch_oboxes(what, centre, half, quat):
+        import torch
+        c, h, q = centre.to(torch.float32), half.to(torch.float32), quat.to(torch.float32)
+        if c.ndim != 2 or c.shape[1] != 3 or h.shape != c.shape or q.shape != (c.shape[0], 4) or not c.is_cuda or h.device != c.device or q.device != c.device:
+            raise ValueError(f"{what}: centre and half must be [N, 3] tensors and quat an [N, 4] tensor (x, y, z, w) on one GPU")
+        n = c.shape[0]
+        pad = torch.zeros((n, 1), dtype=torch.float32, device=c.device)
+        return torch.cat([c, pad, h, pad, q], dim=1).contiguous(), n      # [N, 12] = n mi_obox
+
+    def obox_any(self, centre, half, quat):
+        """Torch convenience over mi_obox_query_device (OBOX_ANY): float32 device tensors centre, half [N, 3] and quat [N, 4] (x, y,
+        z, w; need not be unit), packed on the device and enqueued on torch.cuda.current_stream(). Returns an [N] bool device
+        tensor: a primitive touches the oriented box."""
+        oboxes, n = self._torch_oboxes("obox_any", centre, half, quat)
+        return self._torch_flags(oboxes, n, self.obox_query_device, OBOX_ANY)
+
+    def obox_count(self, centre, half, quat):
+        """The same for OBOX_COUNT: an [N] int32 device tensor, the number of primitives touching each oriented box."""
+        import torch
+        oboxes, n = self._torch_oboxes("obox_count", centre, half, quat)
+        out = torch.empty(n, dtype=torch.int32, device=oboxes.device)
+        self.obox_query_device(OBOX_COUNT, oboxes.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(oboxes.device).cuda_stream)
+        return out
+
+    def obox_list(self, centre, half, quat):
+        """Torch convenience over mi_obox_offsets_device + mi_obox_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 - the
+        words of the OVERLAP records: primID, geomID | flags << 16, box, 0), box by box in ascending (geomID, primID). It runs the
+        offsets, reads the total with one .item() (the one synchronisation), then allocates and fills."""
+        oboxes, n = self._torch_oboxes("obox_list", centre, half, quat)
+        return self._torch_all_lists(self.obox_offsets_device, self.obox_fill_device, oboxes, n, sync_when_empty=False)
 
     # -- triangle queries (mi_tri_query*, mi_tri_offsets*, mi_tri_fill*): every primitive that touches each triangle, by (geomID, primID) --
     def _tri_query_host(self, kind: int, tris: np.ndarray, out: np.ndarray) -> np.ndarray:

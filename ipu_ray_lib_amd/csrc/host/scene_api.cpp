@@ -223,6 +223,33 @@ int mi_tri_fill_host(const mi_scene_desc* desc, const mi_tri* tris, const uint64
   return guarded([&] { triFillHost(*desc, tris, offsets, hits, capacity, n, visits); });
 }
 
+// Oriented-box queries: the host twins of mi_obox_query* / mi_obox_offsets* / mi_obox_fill* (obox_query_host.cpp)
+int mi_obox_query_host(const mi_scene_desc* desc, int kind, const mi_obox* oboxes, void* out, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_obox_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (kind != MI_OBOX_ANY && kind != MI_OBOX_COUNT) { g_err = "mi_obox_query_host: unknown oriented-box kind"; return MI_ERR_INVALID_ARG; }
+  if (n && (!oboxes || !out)) { g_err = "mi_obox_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { oboxQueryHost(*desc, kind, oboxes, out, n, visits); });
+}
+
+int mi_obox_offsets_host(const mi_scene_desc* desc, const mi_obox* oboxes, uint64_t* offsets, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_obox_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!oboxes || !offsets)) { g_err = "mi_obox_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { oboxOffsetsHost(*desc, oboxes, offsets, n, visits); });
+}
+
+int mi_obox_fill_host(const mi_scene_desc* desc, const mi_obox* oboxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_obox_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!oboxes || !offsets || !hits)) { g_err = "mi_obox_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { oboxFillHost(*desc, oboxes, offsets, hits, capacity, n, visits); });
+}
+
+int mi_obox_meets_bounds_host(const mi_obox* obox, const float mn[3], const float mx[3]) {
+  if (!obox || !mn || !mx) return 0;
+  mi_obox q;
+  memcpy(&q, obox, sizeof q);
+  return oboxMeetsBoundsHost(q, mn, mx) ? 1 : 0;
+}
+
 // The canonical primitive table of desc's arrays: the host twin of canon_prim_kernel (canon_kernels.hpp, mi_scene_set_geometry*) -
 // the same prefix, the same search and record per canonical index (canon_prims.hpp), the same checks with mi_scene_create's words
 int mi_canonical_prims(const mi_scene_desc* desc, void* out, uint32_t capacity, uint32_t* count) {

@@ -131,6 +131,11 @@ void boxFillHost(const mi_scene_desc& desc, const mi_box* boxes, const uint64_t*
 void triQueryHost(const mi_scene_desc& desc, int kind, const mi_tri* tris, void* out, size_t n, uint64_t* visits);
 void triOffsetsHost(const mi_scene_desc& desc, const mi_tri* tris, uint64_t* offsets, size_t n, uint64_t* visits);
 void triFillHost(const mi_scene_desc& desc, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity, size_t n, uint64_t* visits);
+// obox_query_host.cpp: the host twins of mi_obox_query / mi_obox_offsets / mi_obox_fill (the same visits), and the bounds test alone
+void oboxQueryHost(const mi_scene_desc& desc, int kind, const mi_obox* oboxes, void* out, size_t n, uint64_t* visits);
+void oboxOffsetsHost(const mi_scene_desc& desc, const mi_obox* oboxes, uint64_t* offsets, size_t n, uint64_t* visits);
+void oboxFillHost(const mi_scene_desc& desc, const mi_obox* oboxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t* visits);
+bool oboxMeetsBoundsHost(const mi_obox& obox, const float mn[3], const float mx[3]);
 
 // glb_reader.cpp: meshes of a glTF-binary file with node transforms baked in, file order kept
 std::vector<TriMesh> loadGlbMeshes(const std::string& path, bool loadNormals);

@@ -23,7 +23,8 @@
 #include "list_kernels.hpp"          // crossing lists: offsets and the sorted fill
 #include "near_kernels.hpp"          // neighbour lists: every primitive within a point's radius, nearest first
 #include "box_kernels.hpp"           // box queries: every primitive that touches a caller's box
-#include "contact_kernels.hpp"       // triangle queries: every primitive that touches a caller's triangle (these seven: launched and entered in query_drivers.hpp, included below)
+#include "contact_kernels.hpp"       // triangle queries: every primitive that touches a caller's triangle
+#include "obox_kernels.hpp"          // oriented-box queries: every primitive that touches a caller's rotated box (these eight: launched and entered in query_drivers.hpp, included below)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
 #include "canon_kernels.hpp"         // new contents for a live scene: the canonical primitive table on the device (mi_scene_set_geometry*)

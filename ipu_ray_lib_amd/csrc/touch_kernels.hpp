@@ -1,8 +1,9 @@
 // touch_kernels.hpp — the kernels of a "touch query": every primitive that TOUCHES a caller-supplied item, with no distance and
-// no order among the touching primitives but their key (geomID, primID). The box queries (box_kernels.hpp, Q = BoxTouch) and the
-// triangle queries (contact_kernels.hpp, Q = TriTouch) are the two there are; a family describes itself by a struct Q:
+// no order among the touching primitives but their key (geomID, primID). The box queries (box_kernels.hpp, Q = BoxTouch), the
+// triangle queries (contact_kernels.hpp, Q = TriTouch) and the oriented-box queries (obox_kernels.hpp, Q = OBoxTouch) are the three
+// there are; a family describes itself by a struct Q:
 //
-//   Q::Item, Q::Record                      what a batch holds (mi_box, mi_tri) and what a list holds (mi_overlap, mi_contact: 16
+//   Q::Item, Q::Record                      what a batch holds (mi_box, mi_tri, mi_obox) and what a list holds (mi_overlap, mi_contact: 16
 //                                           bytes, {primID, geomID | flags << 16, item, 0})
 //   Q::Loaded, Q::load(items, idx)          item idx as the walk wants it, and its loads
 //   Q::walk<STATS>(sc, item, cs, accept)    the item's walk over walk_preorder (bvh_walk.hpp): accept(leaf index, geomID, flags) is
@@ -21,7 +22,7 @@
 //                        and padded. Keys are unique within an item, so the bytes do not depend on the visit order. An item whose
 //                        segment is empty is not walked.
 // No LDS, no stack, no per-lane array, no scratch: a lane carries the item, the segment's base and length, the number of records
-// held, the root's key and the record being placed. The host twins are host/touch_host.hpp (DESIGN.md §25, §30).
+// held, the root's key and the record being placed. The host twins are host/touch_host.hpp (DESIGN.md §25, §30, §34).
 #pragma once
 
 #include "bvh_walk.hpp"

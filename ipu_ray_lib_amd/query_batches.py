@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import RAY, POINT, POINT_HIT, BOX, TRI, INVALID_PRIM      # noqa: F401  (the record dtypes of ray and point queries, side by side)
+from . import RAY, POINT, POINT_HIT, BOX, TRI, OBOX, INVALID_PRIM      # noqa: F401  (the record dtypes of ray and point queries, side by side)
 
 RAY_EPSILON = np.float32(5.9604644775390625e-08 * 1500.0)       # ray_math.h kRayEpsilon (precision_utils.hpp)
 LIGHT = np.array([18.0, 257.0, -1060.0], np.float32)            # the reference's shadow-trace light (trace.cpp:247)
@@ -53,6 +53,48 @@ def make_tris(a: np.ndarray, b: np.ndarray, c: np.ndarray | None = None) -> np.n
         corners = np.stack([np.asarray(a, np.float32), np.asarray(b, np.float32), np.asarray(c, np.float32)], axis=1)
     assert corners.ndim == 3 and corners.shape[1:] == (3, 3)
     return np.ascontiguousarray(corners, np.float32).reshape(-1, 9).view(TRI).reshape(-1)
+
+
+def matrix_to_quat(matrix: np.ndarray) -> np.ndarray:
+    """[n, 3, 3] rotation matrices (columns = the rotated axes) as [n, 4] quaternions x, y, z, w, in float64: the branch on the
+    largest diagonal term (Shepperd), so that the divisor is never small."""
+    m = np.asarray(matrix, np.float64)
+    assert m.ndim == 3 and m.shape[1:] == (3, 3)
+    m00, m11, m22 = m[:, 0, 0], m[:, 1, 1], m[:, 2, 2]
+    tr = m00 + m11 + m22
+    q = np.empty((len(m), 4), np.float64)
+    pick = np.where(tr > 0, 3, np.argmax(np.stack([m00, m11, m22], 1), axis=1))
+    for k in range(4):
+        i = pick == k
+        if not i.any():
+            continue
+        a = m[i]
+        if k == 3:
+            w = np.sqrt(1.0 + tr[i]) * 0.5
+            q[i] = np.stack([(a[:, 2, 1] - a[:, 1, 2]) / (4 * w), (a[:, 0, 2] - a[:, 2, 0]) / (4 * w), (a[:, 1, 0] - a[:, 0, 1]) / (4 * w), w], 1)
+        elif k == 0:
+            x = np.sqrt(1.0 + a[:, 0, 0] - a[:, 1, 1] - a[:, 2, 2]) * 0.5
+            q[i] = np.stack([x, (a[:, 0, 1] + a[:, 1, 0]) / (4 * x), (a[:, 0, 2] + a[:, 2, 0]) / (4 * x), (a[:, 2, 1] - a[:, 1, 2]) / (4 * x)], 1)
+        elif k == 1:
+            y = np.sqrt(1.0 - a[:, 0, 0] + a[:, 1, 1] - a[:, 2, 2]) * 0.5
+            q[i] = np.stack([(a[:, 0, 1] + a[:, 1, 0]) / (4 * y), y, (a[:, 1, 2] + a[:, 2, 1]) / (4 * y), (a[:, 0, 2] - a[:, 2, 0]) / (4 * y)], 1)
+        else:
+            z = np.sqrt(1.0 - a[:, 0, 0] - a[:, 1, 1] + a[:, 2, 2]) * 0.5
+            q[i] = np.stack([(a[:, 0, 2] + a[:, 2, 0]) / (4 * z), (a[:, 1, 2] + a[:, 2, 1]) / (4 * z), z, (a[:, 1, 0] - a[:, 0, 1]) / (4 * z)], 1)
+    return q
+
+
+def make_oboxes(centre: np.ndarray, half: np.ndarray, quat: np.ndarray | None = None, matrix: np.ndarray | None = None) -> np.ndarray:
+    """An OBOX array (oriented-box queries: IpuScene.obox_touches / count_obox_overlaps / list_obox_overlaps) from [N, 3] centres and
+    half extents and EITHER quat, [N, 4] quaternions x, y, z, w (they need not be unit), OR matrix, [N, 3, 3] rotation matrices whose
+    columns are the box's axes in world coordinates (converted by matrix_to_quat). Exactly one of the two must be given."""
+    if (quat is None) == (matrix is None):
+        raise ValueError("make_oboxes: exactly one of quat and matrix must be given")
+    b = np.zeros(len(centre), OBOX)
+    b["centre"] = centre
+    b["half"] = half
+    b["quat"] = matrix_to_quat(matrix) if quat is None else quat
+    return b
 
 
 def primary_rays(host_scene) -> np.ndarray:
