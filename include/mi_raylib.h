@@ -635,6 +635,60 @@ int mi_scene_get_bvh(mi_scene* scene, mi_bvh_node* out, uint32_t capacity, uint3
  * out = {leaf boxes, interior boxes, record rewrite and copies}; zeros unless scene option "refit_timing" is 1. */
 int mi_get_refit_timing(mi_scene* scene, double out[3]);
 
+/* Rigid poses: move whole geometries of a live scene by one transform each - a rotation (a quaternion that need not be unit), a
+ * uniform scale and a translation - and refit (Embree's and OptiX's per-instance transform; this library has one BVH over all
+ * primitives, so the geometry is posed on the device and the BVH refitted: every later render and query works unchanged on the posed
+ * scene). 32 bytes per geometry cross the bus, not 12 per vertex.
+ * Poses and the geometry list. One pose per entry of the scene's geometry list, in its order; num_geometry must equal the scene's
+ * geometry count.
+ * Rest geometry. Poses are ABSOLUTE: each is applied to the rest geometry, never to the previous pose's result - "pose A, then pose
+ * B" gives the bytes of "pose B" alone, nothing drifts. The rest geometry is the scene's current geometry - vertices, vertex normals,
+ * spheres, discs - at the first pose call after mi_scene_create*, mi_scene_update*, mi_scene_set_geometry* or mi_scene_bake_poses:
+ * those calls invalidate the snapshot and reset the stored poses to the identity. A rebuild, an automatic one included, changes
+ * topology only and keeps both. A scene that is never posed allocates nothing (a posed one keeps a rest copy, a scratch copy and a
+ * uint16_t owner per vertex: 26 bytes per vertex, 50 with normals).
+ * Arithmetic. Binary32, one rounding per operation, nothing contracted. U, V, W = obox_frame(x, y, z, w), the function mi_obox uses
+ * (ipu_ray_lib_amd/csrc/obox_math.hpp): qq = ((x x + y y) + z z) + w w, s = 2 / qq, xs = x s, ys = y s, zs = z s,
+ * U = (1 - (y ys + z zs), x ys + w zs, x zs - w ys), V = (x ys - w zs, 1 - (x xs + z zs), y zs + w xs),
+ * W = (x zs + w ys, y zs - w xs, 1 - (x xs + y ys)) - the columns of the rotation's matrix, so a body and its mi_obox turn alike.
+ * A point p becomes p'_k = fl(fl(scale r_k) + t_k) with r_k = fl(fl(fl(U_k p.x) + fl(V_k p.y)) + fl(W_k p.z)); a direction becomes
+ * r_k: no scale, no translation, not renormalised.
+ * What is moved. Mesh vertices are points, vertex normals directions; a sphere's centre is a point and radius' = fl(scale radius); a
+ * disc's centre is a point, its normal a direction and r' = fl(scale r).
+ * Identity. A pose is the identity when it compares equal to (0, 0, 0, 1; 0, 0, 0; 1) - float compares, -0 counts as zero. Such a
+ * pose copies the geometry's rest bytes: a -0 coordinate stays -0.
+ * Valid pose. Eight finite floats, qq > 0, a finite 2 / qq (mi_obox's rule) and scale > 0.
+ * Ownership. A vertex belongs to the geometry whose mesh's range [first_vertex, first_vertex + num_vertices) contains it; vertices in
+ * no referenced mesh's range, and spheres and discs no geometry references, keep their rest bytes. The call is refused when two
+ * meshes' vertex ranges intersect or when one mesh, sphere or disc is referenced by two geometry entries (the message names the
+ * pair); checked once per rest snapshot, on the host.
+ * Result. mi_pose_geometry_host (mi_scene_host.h) computes the posed arrays; after the call the scene is, bit for bit, what
+ * mi_scene_update with those arrays leaves: nodes, records, later renders and queries, "auto_rebuild" decisions and the counts of
+ * mi_get_live_stats.
+ * Ordering. The call waits for all work already enqueued on the scene, on any stream (renders and queries), before it overwrites a
+ * device record: a render or query enqueued before it sees the old geometry, whatever its stream.
+ * Synchronous return. The call returns once the new geometry is in place; work enqueued after it returns sees it. It reads back one
+ * small record more than an update does (whether every pose is valid). mi_scene_set_poses_device takes DEVICE poses (16-byte aligned)
+ * and does its kernels and copies on hip_stream (a hipStream_t as void*; NULL = the null stream), then waits for that stream only;
+ * mi_scene_set_poses takes HOST poses.
+ * Refusal. MI_ERR_INVALID_ARG leaves the scene unchanged - the scene, the stored poses and the rest snapshot: a null scene or a null
+ * array, a wrong num_geometry, an invalid pose (for the device entry decided on the device, before anything changes), an ownership
+ * conflict, a resulting node box that is not finite, an extent above 65504. The message names the entry.
+ * Zero geometries. num_geometry == 0 on a scene of zero geometries is a no-op that reads no pointer.
+ * mi_scene_get_poses copies the current poses to `out` (HOST memory, capacity poses); *num_geometry = the geometry count (out == NULL:
+ * only the count). mi_scene_bake_poses: the current geometry becomes the rest geometry and every pose the identity; it moves no byte
+ * of the scene. */
+typedef struct { float quat[4]; float translation[3]; float scale; } mi_pose;   /* 32 B, two 16-byte loads; quat = x, y, z, w */
+
+int mi_scene_set_poses(mi_scene* scene, const mi_pose* poses, uint32_t num_geometry);                                  /* host memory */
+int mi_scene_set_poses_device(mi_scene* scene, const void* d_poses, uint32_t num_geometry, void* hip_stream);          /* device memory */
+int mi_scene_get_poses(mi_scene* scene, mi_pose* out, uint32_t capacity, uint32_t* num_geometry);                      /* current poses, host out */
+int mi_scene_bake_poses(mi_scene* scene);
+/* Measurement only (tools/bench_pose.py): the last pose call's times in milliseconds from HIP events on its stream, out = {the
+ * pose pass (frames and posed arrays), everything after it (the read-back, the refit, the copies)}; zeros unless scene option
+ * "refit_timing" is 1. */
+int mi_get_pose_timing(mi_scene* scene, double out[2]);
+
 /* Rebuild the BVH topology of a live scene from its CURRENT geometry, on the device (Embree's RTC_BUILD_QUALITY_LOW rebuild next
  * to its refit, OptiX's BUILD next to UPDATE): a linear BVH - Morton keys of the primitive centroids, a radix sort, Karras' 2012
  * hierarchy - over the primitives in canonical order (geometry 0 .. G - 1, inside a mesh triangle 0 .. T - 1). The node count

@@ -178,6 +178,18 @@ int mi_obox_fill_host(const mi_scene_desc* desc, const mi_obox* oboxes, const ui
  * pointer gives 0. */
 int mi_obox_meets_bounds_host(const mi_obox* obox, const float mn[3], const float mx[3]);
 
+/* Rigid poses on the host: the twin of the pose pass of mi_scene_set_poses* (mi_raylib.h, where the contract is written). `rest`
+ * holds the rest geometry - its geometry list, mesh_info, vertices, normals, spheres and discs are read, nothing else -, poses one
+ * mi_pose per geometry entry. Writes the posed arrays - rest->num_verts vertices, as many normals (normals_out may be NULL when the
+ * scene has none), num_spheres spheres, num_discs discs - through the code the kernel runs (ipu_ray_lib_amd/csrc/pose_math.hpp): the
+ * bytes the device hands to its refit. Records no geometry owns and geometries under the identity pose keep their rest bytes.
+ * MI_ERR_INVALID_ARG, with the function's name in mi_host_last_error: a null desc, null poses with num_geometry > 0, a num_geometry
+ * that differs from rest's, a null output for a kind the scene has, a geometry reference or vertex range out of bounds, an invalid
+ * pose, an ownership conflict (two meshes' vertex ranges intersect; one mesh, sphere or disc referenced twice): nothing is
+ * written then. num_geometry == 0 on a description of zero geometries reads no pose. */
+int mi_pose_geometry_host(const mi_scene_desc* rest, const mi_pose* poses, uint32_t num_geometry, mi_vec3* verts_out, mi_vec3* normals_out,
+                          mi_sphere* spheres_out, mi_disc* discs_out);
+
 /* Sphere crossings on the host: how often the ray origin + t direction, t_min < t < t_max, crosses the shell of the sphere (centre,
  * radius2 = the squared radius) - 0, 1 or 2 -, from the definition the crossing-count kernels run (mi_count_query / mi_point_sign,
  * mi_raylib.h, where the formula is written; ipu_ray_lib_amd/csrc/cross_math.hpp). The triangle and disc tests of a crossing count

@@ -67,8 +67,12 @@ CONTACT = np.dtype([("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("tr
 # (IpuScene.obox_touches / count_obox_overlaps / list_obox_overlaps / obox_fill_device)
 OBOX = np.dtype([("centre", "<f4", (3,)), ("reserved0", "<u4"), ("half", "<f4", (3,)), ("reserved1", "<u4"), ("quat", "<f4", (4,))])
 
+# mi_pose: the rigid pose of one geometry - a quaternion x, y, z, w that need not be unit, a translation, a uniform scale
+# (IpuScene.set_poses / poses / pose; query_batches.make_poses)
+POSE = np.dtype([("quat", "<f4", (4,)), ("translation", "<f4", (3,)), ("scale", "<f4")])
+
 assert CROSSING.itemsize == 16 and NEIGHBOUR.itemsize == 16
-assert OBOX.itemsize == 48
+assert OBOX.itemsize == 48 and POSE.itemsize == 32
 assert TRI.itemsize == 36 and CONTACT.itemsize == 16
 assert BOX.itemsize == 32 and OVERLAP.itemsize == 16
 assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
@@ -221,6 +225,7 @@ def host_lib() -> C.CDLL:
         lib.mi_obox_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_obox_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_obox_meets_bounds_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mi_pose_geometry_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
         lib.mi_sphere_roots_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(C.c_float)]
@@ -345,6 +350,11 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_obox_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_obox_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         lib.mi_obox_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        lib.mi_scene_set_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.mi_scene_set_poses_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        lib.mi_scene_get_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        lib.mi_scene_bake_poses.argtypes = [C.c_void_p]
+        lib.mi_get_pose_timing.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.mi_point_sign.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t]
         lib.mi_point_sign_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_size_t, C.c_void_p]
         lib.mi_group_create.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_int32, C.POINTER(C.c_void_p)]
@@ -681,6 +691,19 @@ def obox_meets_bounds_host(obox: np.ndarray, mn, mx) -> bool:
     q = np.ascontiguousarray(obox, OBOX).reshape(1)
     lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
     return bool(host_lib().mi_obox_meets_bounds_host(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
+
+
+def pose_geometry_host(desc: SceneDesc, poses: np.ndarray) -> dict:
+    """mi_pose_geometry_host: the host twin of the pose pass of IpuScene.set_poses - desc's geometry as the rest geometry, one POSE per
+    geometry entry. Returns {"vertices": VEC3 [num_verts], "normals": VEC3 [num_normals], "spheres": SPHERE [...], "discs": DISC [...]}:
+    the arrays the device hands to its refit, byte for byte."""
+    assert poses.dtype == POSE and poses.ndim == 1
+    src = np.ascontiguousarray(poses)
+    out = {"vertices": np.zeros(desc.num_verts if desc.num_meshes else 0, VEC3), "normals": np.zeros(desc.num_normals, VEC3),
+           "spheres": np.zeros(desc.num_spheres, SPHERE), "discs": np.zeros(desc.num_discs, DISC)}
+    ptr = [a.ctypes.data if a.size else None for a in out.values()]
+    _check_host(host_lib().mi_pose_geometry_host(C.byref(desc), src.ctypes.data if src.size else None, src.size, *ptr))
+    return out
 
 
 def tri_query_host(desc: SceneDesc, kind: int, tris: np.ndarray):
@@ -1659,6 +1682,58 @@ class IpuScene:
         stream = torch.cuda.current_stream(dev).cuda_stream if dev is not None else 0
         self._check(self._lib.mi_scene_update_device(self._h, C.byref(u), C.c_void_p(stream)))
         return self
+
+    # -- rigid poses (mi_scene_set_poses*): whole geometries moved by one transform each, posed on the device from a rest copy, then the refit --
+    def set_poses(self, poses: np.ndarray) -> "IpuScene":
+        """One POSE per entry of the scene's geometry list (HOST memory; query_batches.make_poses builds them), applied to the REST
+        geometry - the scene's geometry at the first pose call after create, update_geometry*, set_geometry* or bake_poses -, never to
+        the previous pose's result. Afterwards the scene is what update_geometry with pose_geometry_host's arrays leaves, bit for
+        bit. Synchronous; work enqueued before sees the old geometry."""
+        src = self._source(poses, POSE)
+        self._check(self._lib.mi_scene_set_poses(self._h, src.ctypes.data if src.size else None, src.size))
+        return self
+
+    def set_poses_device(self, d_poses: int, n: int, stream: int = 0) -> "IpuScene":
+        """mi_scene_set_poses_device on a device pointer (n POSE records, 16-byte aligned), on `stream`; synchronous."""
+        self._check(self._lib.mi_scene_set_poses_device(self._h, C.c_void_p(d_poses), int(n), C.c_void_p(stream)))
+        return self
+
+    def poses(self) -> np.ndarray:
+        """mi_scene_get_poses: the current pose of every geometry, a POSE array (identities until the first set_poses)."""
+        n = C.c_uint32()
+        self._check(self._lib.mi_scene_get_poses(self._h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, POSE)
+        self._check(self._lib.mi_scene_get_poses(self._h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out
+
+    def bake_poses(self) -> "IpuScene":
+        """mi_scene_bake_poses: the current geometry becomes the rest geometry, every pose the identity; moves no byte of the scene."""
+        self._check(self._lib.mi_scene_bake_poses(self._h))
+        return self
+
+    def pose(self, quat, translation, scale=None) -> "IpuScene":
+        """Torch convenience over mi_scene_set_poses_device: float32 device tensors quat [G, 4] (x, y, z, w; need not be unit),
+        translation [G, 3] and scale [G] (None = 1), packed to [G, 8] on the device and enqueued on torch.cuda.current_stream()."""
+        import torch
+        q, t = quat, translation
+        if not (q.is_cuda and t.is_cuda and q.dtype == torch.float32 and t.dtype == torch.float32 and q.ndim == 2 and t.ndim == 2 and q.shape[1] == 4 and
+                t.shape[1] == 3 and q.shape[0] == t.shape[0]):
+            raise ValueError("pose: quat [G, 4] and translation [G, 3] must be float32 CUDA tensors of one length")
+        g = q.shape[0]
+        if scale is None:
+            s = torch.ones((g, 1), dtype=torch.float32, device=q.device)
+        else:
+            if not (scale.is_cuda and scale.dtype == torch.float32 and scale.numel() == g):
+                raise ValueError("pose: scale must be a float32 CUDA tensor of G elements")
+            s = scale.reshape(g, 1)
+        packed = torch.cat([q, t, s], dim=1).contiguous()      # [G, 8] = G mi_pose
+        return self.set_poses_device(packed.data_ptr() if g else 0, g, stream=torch.cuda.current_stream(q.device).cuda_stream)
+
+    def pose_timing(self) -> list:
+        """mi_get_pose_timing: the last pose call's {pose pass, everything after it} in ms (zeros unless option "refit_timing" is 1)."""
+        out = (C.c_double * 2)()
+        self._check(self._lib.mi_get_pose_timing(self._h, out))
+        return list(out)
 
     # -- new contents (mi_scene_set_geometry*): another geometry list, other meshes, other counts; the BVH built on the device ------------
     def set_geometry(self, desc: SceneDesc) -> int:

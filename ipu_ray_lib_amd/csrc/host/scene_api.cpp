@@ -243,6 +243,14 @@ int mi_obox_fill_host(const mi_scene_desc* desc, const mi_obox* oboxes, const ui
   return guarded([&] { oboxFillHost(*desc, oboxes, offsets, hits, capacity, n, visits); });
 }
 
+// Rigid poses: the host twin of the pose pass of mi_scene_set_poses* (pose_host.cpp)
+int mi_pose_geometry_host(const mi_scene_desc* rest, const mi_pose* poses, uint32_t num_geometry, mi_vec3* verts_out, mi_vec3* normals_out,
+                          mi_sphere* spheres_out, mi_disc* discs_out) {
+  if (!rest) { g_err = "mi_pose_geometry_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (num_geometry && !poses) { g_err = "mi_pose_geometry_host: null poses"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { poseGeometryHost(*rest, poses, num_geometry, verts_out, normals_out, spheres_out, discs_out); });
+}
+
 int mi_obox_meets_bounds_host(const mi_obox* obox, const float mn[3], const float mx[3]) {
   if (!obox || !mn || !mx) return 0;
   mi_obox q;

@@ -27,6 +27,7 @@
 #include "obox_kernels.hpp"          // oriented-box queries: every primitive that touches a caller's rotated box (these eight: launched and entered in query_drivers.hpp, included below)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
+#include "pose_kernels.hpp"          // rigid poses: the posed geometry from a rest copy and one pose per geometry (mi_scene_set_poses*)
 #include "canon_kernels.hpp"         // new contents for a live scene: the canonical primitive table on the device (mi_scene_set_geometry*)
 #include "cost_kernels.hpp"          // the surface-area cost of the current tree (mi_scene_bvh_cost, option auto_rebuild)
 #include "bvh_cost_host.hpp"         // its host twin: a scene whose nodes are still only on the host
@@ -459,7 +460,7 @@ struct mi_scene {
   struct Refit {
     std::vector<mi_bvh_node> nodes;                           // the compact nodes at create: the scene's current ones until the first update or rebuild (live < 0),
                                                               // what the first update derives the tables below from; not read afterwards (the count is ds.numNodes).
-                                                              // New contents (setGeometry) leave every host vector here empty: only the counts below are read then
+                                                              // New contents (setGeometry) keep geometry and meshInfo (the poses' owners) and leave the other host vectors empty: only the counts below are read then
     bool tables = false; uint32_t levelCap = 0;               // tables: d_prims, d_order and the level starts describe the current topology (derived on the host by
                                                               // the first update, written by the device passes of every rebuild); levelCap: entries d_levelStart holds
     std::vector<uint32_t> matIds;                             // per geometry (a rebuild writes leaf records)
@@ -497,6 +498,25 @@ struct mi_scene {
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // option "rebuild_timing"
     double ms[6] = {0, 0, 0, 0, 0, 0};                        // the last rebuild's {boxes + keys, sort, hierarchy + depths, level boxes, preorder, tables + scatter}
   } rebuild;
+  // mi_scene_set_poses*: the rest snapshot, the owner tables, the arrays the pose pass writes and the current poses, built at the
+  // first pose call after create, an update, new contents or a bake (poseSnapshot; a scene that is never posed allocates nothing)
+  struct Poses {
+    bool allocated = false;                                   // the buffers below exist, sized for the scene's current counts
+    bool snapshot = false;                                    // the rest arrays and the owner tables describe the rest geometry
+    bool posed = false;                                       // d_poses holds the current poses (else every pose is the identity)
+    mi_vec3* d_restVerts = nullptr; mi_vec3* d_restNormals = nullptr; mi_sphere* d_restSpheres = nullptr; mi_disc* d_restDiscs = nullptr;
+    mi_vec3* d_outVerts = nullptr; mi_vec3* d_outNormals = nullptr; mi_sphere* d_outSpheres = nullptr; mi_disc* d_outDiscs = nullptr;
+    uint16_t* d_vertOwner = nullptr; uint16_t* d_sphereOwner = nullptr; uint16_t* d_discOwner = nullptr;
+    PoseFrame* d_frames = nullptr;                            // [G]
+    mi_pose* d_poses = nullptr; mi_pose* d_staged = nullptr;  // [G] the current poses; the host entry's upload
+    uint32_t* d_bad = nullptr;                                // {some pose is not valid, the first such pose}
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};           // option "refit_timing": round the pose pass and what follows it
+    double ms[2] = {0, 0};                                    // the last pose call's {pose pass, everything after it}
+    std::vector<void*> buffers() const {
+      return {d_restVerts, d_restNormals, d_restSpheres, d_restDiscs, d_outVerts, d_outNormals, d_outSpheres, d_outDiscs, d_vertOwner, d_sphereOwner,
+              d_discOwner, d_frames, d_poses, d_staged, d_bad};
+    }
+  } poses;
   // the live loop (refit every frame, rebuild when the tree has degraded): the cost pass's scratch, the policy's baseline, what happened
   struct Live {
     Cost2* d_cost = nullptr;                                  // slot 0 = {a_root, -}, slot 1 = the last level's one entry, then the levels before it, the first last
@@ -530,6 +550,7 @@ struct mi_scene {
     for (auto& e : nifTimes) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
     for (hipEvent_t e : refit.ev) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : rebuild.ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : poses.ev) if (e) (void)hipEventDestroy(e);
     nif.release();
   }
   void freeNifSlots() {
@@ -963,7 +984,7 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream);
 // DeviceScene::leafNormalsOrFrames as the kernels that rewrite leaves[] take it: one of the two is null
 float* leafNormalsOf(const DeviceScene& ds) { return ds.hasNormals ? const_cast<float*>(ds.leafNormalsOrFrames) : nullptr; }
 GLeafFrame* leafFramesOf(const DeviceScene& ds) { return ds.hasNormals ? nullptr : reinterpret_cast<GLeafFrame*>(const_cast<float*>(ds.leafNormalsOrFrames)); }
-void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
+void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream, const char* fn = "mi_scene_update") {
   refitTables(S);
   mi_scene::Refit& R = S.refit;
   DeviceScene& ds = S.touchArrays();      // (K1w's private copies retire here: the update writes the shared arrays)
@@ -1004,8 +1025,8 @@ void refitScene(mi_scene& S, const mi_geometry_update& u, hipStream_t stream) {
     }
     // (an empty leaf box - every point NaN on an axis - also makes its parent's extent infinite: the leaf is named first)
     if (err) ++S.live.refused;
-    if (err & (1u << kBoxNotFinite)) throw ArgError("mi_scene_update: a node box is not finite; the scene is unchanged");
-    if (err) throw ArgError("mi_scene_update: a node extent is above 65504 (Cannot compress BVH bounds into fp16 (half)); the scene is unchanged");
+    if (err & (1u << kBoxNotFinite)) throw ArgError(std::string(fn) + ": a node box is not finite; the scene is unchanged");
+    if (err) throw ArgError(std::string(fn) + ": a node extent is above 65504 (Cannot compress BVH bounds into fp16 (half)); the scene is unchanged");
   }
   // option auto_rebuild: the baseline where there is none yet - the estimate of the tree as it stands before this update, which
   // is now certain to be applied (R.live still names it)
@@ -1265,6 +1286,120 @@ uint32_t rebuildScene(mi_scene& S, hipStream_t stream) {
   return S.live.maxLeafDepth;
 }
 
+// ---- rigid poses (mi_scene_set_poses*, pose_kernels.hpp) ---------------------------------------------------------------------------
+// The rest snapshot is no longer the scene's rest geometry and every pose is the identity again: after an update or a bake. The
+// buffers stay (the counts have not changed); the next pose call copies the current geometry into them.
+void poseInvalidate(mi_scene& S) { S.poses.snapshot = false; S.poses.posed = false; }
+
+// New contents: other counts, another geometry list. The buffers go; a scene that is not posed again allocates none.
+void poseDrop(mi_scene& S) {
+  mi_scene::Poses& P = S.poses;
+  for (void* p : P.buffers()) S.release(p);
+  mi_scene::Poses fresh;
+  for (int k = 0; k < 3; ++k) fresh.ev[k] = P.ev[k];
+  P = fresh;
+}
+
+// The rest snapshot: the scene's current geometry copied aside on `stream`, and the owner of every vertex, sphere and disc derived
+// on the host from the geometry list (pose_owners). An ownership conflict is refused before anything is allocated or copied.
+void poseSnapshot(mi_scene& S, hipStream_t stream, const char* fn) {
+  mi_scene::Poses& P = S.poses;
+  mi_scene::Refit& R = S.refit;
+  if (P.snapshot) return;
+  const uint32_t G = (uint32_t)R.geometry.size();
+  std::vector<uint16_t> vo, so, dso;
+  const std::string conflict = pose_owners(R.geometry.data(), G, R.meshInfo.data(), (uint32_t)R.meshInfo.size(), R.numVerts, R.numSpheres, R.numDiscs, vo, so, dso);
+  if (!conflict.empty()) throw ArgError(std::string(fn) + ": " + conflict + "; the scene is unchanged");
+  if (!P.allocated) {
+    auto alloc = [&](auto*& p, size_t count) { p = nullptr; if (count) { HIP_CHECK(hipMalloc(&p, count * sizeof(*p))); S.keep(p); } };
+    alloc(P.d_restVerts, R.numVerts); alloc(P.d_outVerts, R.numVerts); alloc(P.d_vertOwner, R.numVerts);
+    alloc(P.d_restNormals, R.numNormals); alloc(P.d_outNormals, R.numNormals);
+    alloc(P.d_restSpheres, R.numSpheres); alloc(P.d_outSpheres, R.numSpheres); alloc(P.d_sphereOwner, R.numSpheres);
+    alloc(P.d_restDiscs, R.numDiscs); alloc(P.d_outDiscs, R.numDiscs); alloc(P.d_discOwner, R.numDiscs);
+    alloc(P.d_frames, G); alloc(P.d_poses, G); alloc(P.d_staged, G); alloc(P.d_bad, 2);
+    P.allocated = true;
+  }
+  auto copy = [&](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) { if (bytes) HIP_CHECK(hipMemcpyAsync(dst, src, bytes, kind, stream)); };
+  copy(P.d_restVerts, R.d_verts, (size_t)R.numVerts * sizeof(mi_vec3), hipMemcpyDeviceToDevice);
+  copy(P.d_restNormals, S.ds.meshNormals, (size_t)R.numNormals * sizeof(mi_vec3), hipMemcpyDeviceToDevice);
+  copy(P.d_restSpheres, R.d_spheres, (size_t)R.numSpheres * sizeof(mi_sphere), hipMemcpyDeviceToDevice);
+  copy(P.d_restDiscs, R.d_discs, (size_t)R.numDiscs * sizeof(mi_disc), hipMemcpyDeviceToDevice);
+  copy(P.d_vertOwner, vo.data(), vo.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  copy(P.d_sphereOwner, so.data(), so.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  copy(P.d_discOwner, dso.data(), dso.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+  HIP_CHECK(hipStreamSynchronize(stream));      // (the owner tables are this function's own vectors)
+  P.snapshot = true;
+}
+
+// Argument rules of the two pose entries: the first two touch neither the scene nor a device.
+void poseArgs(const char* fn, const mi_scene* S, const void* poses, uint32_t numGeometry) {
+  auto bad = [&](const char* why) { throw ArgError(std::string(fn) + ": " + why); };
+  if (!S) bad("null scene");
+  if (!poses && numGeometry) bad("null poses");
+  if (numGeometry != S->refit.geometry.size()) bad("num_geometry differs from the scene's geometry count");
+}
+
+// The poses proper, G of them in DEVICE memory (d_poses) or in HOST memory (h_poses, staged into the scene's own array), on `stream`:
+// the rest snapshot where there is none, the frame kernel (which decides validity), the pose pass into the scene's scratch arrays,
+// one small read-back, then refitScene on those arrays - which copies them into the current geometry on success and moves nothing
+// on refusal. `snapshotWas`: a snapshot taken for a call that is then refused is dropped again, so that a refusal leaves the rest
+// geometry as undefined as it was.
+void poseScene(mi_scene& S, const mi_pose* d_poses, const mi_pose* h_poses, hipStream_t stream, const char* fn) {
+  mi_scene::Poses& P = S.poses;
+  mi_scene::Refit& R = S.refit;
+  const uint32_t G = (uint32_t)R.geometry.size();
+  if (!G) return;
+  refitTables(S);      // (the current geometry on the device: a scene's first update or pose uploads it)
+  const bool snapshotWas = P.snapshot;
+  poseSnapshot(S, stream, fn);
+  try {
+    if (h_poses) {
+      HIP_CHECK(hipMemcpyAsync(P.d_staged, h_poses, (size_t)G * sizeof(mi_pose), hipMemcpyHostToDevice, stream));
+      d_poses = P.d_staged;
+    }
+    const bool timing = S.opt.refitTiming;
+    if (timing && !P.ev[0]) for (hipEvent_t& e : P.ev) HIP_CHECK(hipEventCreate(&e));
+    const uint32_t preset[2] = {0u, 0xFFFFFFFFu};
+    HIP_CHECK(hipMemcpyAsync(P.d_bad, preset, sizeof preset, hipMemcpyHostToDevice, stream));
+    if (timing) HIP_CHECK(hipEventRecord(P.ev[0], stream));
+    hipLaunchKernelGGL(pose_frame_kernel, dim3((G + kPoseBlock - 1) / kPoseBlock), dim3(kPoseBlock), 0, stream, reinterpret_cast<const float4*>(d_poses), G,
+                       P.d_frames, P.d_bad);
+    const uint64_t total = (uint64_t)R.numVerts + R.numSpheres + R.numDiscs;
+    if (total) {
+      const PoseRest rest{P.d_restVerts, P.d_restNormals, P.d_restSpheres, P.d_restDiscs};
+      const PoseOwners owners{P.d_vertOwner, P.d_sphereOwner, P.d_discOwner};
+      const PoseOut out{P.d_outVerts, P.d_outNormals, P.d_outSpheres, P.d_outDiscs};
+      hipLaunchKernelGGL(pose_apply_kernel, dim3((uint32_t)((total + kPoseBlock - 1) / kPoseBlock)), dim3(kPoseBlock), 0, stream, R.numVerts, R.numSpheres,
+                         R.numDiscs, rest, owners, P.d_frames, out);
+    }
+    HIP_CHECK(hipGetLastError());
+    if (timing) HIP_CHECK(hipEventRecord(P.ev[1], stream));
+    uint32_t bad[2] = {0u, 0u};
+    HIP_CHECK(hipMemcpyAsync(bad, P.d_bad, sizeof bad, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    if (bad[0]) throw ArgError(std::string(fn) + ": pose " + std::to_string(bad[1]) + " is not valid (eight finite floats, a quaternion whose squared norm and its "
+                               "reciprocal are finite and positive, scale > 0); the scene is unchanged");
+    mi_geometry_update u{};
+    if (R.numVerts) { u.mesh_verts = P.d_outVerts; u.num_verts = R.numVerts; }
+    if (R.numNormals) { u.mesh_normals = P.d_outNormals; u.num_normals = R.numNormals; }
+    if (R.numSpheres) { u.spheres = P.d_outSpheres; u.num_spheres = R.numSpheres; }
+    if (R.numDiscs) { u.discs = P.d_outDiscs; u.num_discs = R.numDiscs; }
+    refitScene(S, u, stream, fn);
+    if (d_poses != P.d_poses) HIP_CHECK(hipMemcpyAsync(P.d_poses, d_poses, (size_t)G * sizeof(mi_pose), hipMemcpyDeviceToDevice, stream));
+    if (timing) HIP_CHECK(hipEventRecord(P.ev[2], stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    P.posed = true;
+    if (timing) {
+      float a = 0.f, b = 0.f;
+      HIP_CHECK(hipEventElapsedTime(&a, P.ev[0], P.ev[1])); HIP_CHECK(hipEventElapsedTime(&b, P.ev[1], P.ev[2]));
+      P.ms[0] = a; P.ms[1] = b;
+    }
+  } catch (...) {
+    if (!snapshotWas) P.snapshot = false;
+    throw;
+  }
+}
+
 // ---- new contents (mi_scene_set_geometry*, canon_kernels.hpp) ---------------------------------------------------------------------
 // The scene's contents replaced by the arrays of `g` (control plane on the host, data plane where `kind` says) and its BVH built from
 // them: everything the contents own - geometry, records, the refit's tables - is allocated aside, the canonical table is written by
@@ -1308,6 +1443,8 @@ uint32_t setGeometry(mi_scene& S, const mi_scene_geometry& g, hipStream_t stream
     alloc(normals, g.num_normals); put(normals, g.mesh_normals, (size_t)g.num_normals * sizeof(mi_vec3), kind);
     alloc(firstVertex, G);
     R.numVerts = numVerts; R.numNormals = g.num_normals; R.numSpheres = g.num_spheres; R.numDiscs = g.num_discs;
+    R.geometry.assign(g.geometry, g.geometry + G);                     // (what mi_scene_set_poses* derives the owners from)
+    R.meshInfo.assign(g.mesh_info, g.mesh_info + M);
     R.d_err = S.refit.d_err;
     for (int k = 0; k < 4; ++k) R.ev[k] = S.refit.ev[k];
     for (int k = 0; k < 3; ++k) R.ms[k] = S.refit.ms[k];
@@ -1372,6 +1509,7 @@ uint32_t setGeometry(mi_scene& S, const mi_scene_geometry& g, hipStream_t stream
   S.refit = std::move(R);
   S.rebuild = B;
   S.live.d_cost = nullptr;                       // (sized for the old node count: sceneCost allocates it again)
+  poseDrop(S);                                   // (the rest snapshot and the poses were the old contents')
   S.live.maxLeafDepth = depth;
   ++S.live.geometrySets;
   rebuildBaseline(S, stream);
@@ -1847,6 +1985,7 @@ int mi_scene_update_device(mi_scene* scene, const mi_geometry_update* device_arr
     updateArgs("mi_scene_update_device", scene, device_arrays);
     HIP_CHECK(hipSetDevice(scene->device));
     refitScene(*scene, *device_arrays, (hipStream_t)hip_stream);
+    poseInvalidate(*scene);
   });
 }
 
@@ -1870,9 +2009,69 @@ int mi_scene_update(mi_scene* scene, const mi_geometry_update* host_arrays) {
     u.spheres = (const mi_sphere*)stage(u.spheres, (size_t)u.num_spheres * sizeof(mi_sphere));
     u.discs = (const mi_disc*)stage(u.discs, (size_t)u.num_discs * sizeof(mi_disc));
     refitScene(*scene, u, nullptr);
+    poseInvalidate(*scene);
   });
   for (void* d : staged) (void)hipFree(d);
   return rc;
+}
+
+int mi_scene_set_poses_device(mi_scene* scene, const void* d_poses, uint32_t num_geometry, void* hip_stream) {
+  return guarded([&] {
+    poseArgs("mi_scene_set_poses_device", scene, d_poses, num_geometry);
+    if (!num_geometry) return;
+    if ((uintptr_t)d_poses % 16) throw ArgError("mi_scene_set_poses_device: poses must be 16-byte aligned");
+    HIP_CHECK(hipSetDevice(scene->device));
+    poseScene(*scene, (const mi_pose*)d_poses, nullptr, (hipStream_t)hip_stream, "mi_scene_set_poses_device");
+  });
+}
+
+int mi_scene_set_poses(mi_scene* scene, const mi_pose* poses, uint32_t num_geometry) {
+  return guarded([&] {
+    poseArgs("mi_scene_set_poses", scene, poses, num_geometry);
+    if (!num_geometry) return;
+    // (the host can name the pose before a device is touched; the device entry's rule is the same function)
+    for (uint32_t g = 0; g < num_geometry; ++g) {
+      mi_pose p;
+      memcpy(&p, &poses[g], sizeof p);
+      if (!pose_valid(p.quat, p.translation, p.scale))
+        throw ArgError("mi_scene_set_poses: pose " + std::to_string(g) + " is not valid (eight finite floats, a quaternion whose squared norm and its "
+                       "reciprocal are finite and positive, scale > 0); the scene is unchanged");
+    }
+    HIP_CHECK(hipSetDevice(scene->device));
+    // the given poses to the device, then the device entry's work on the null stream
+    poseScene(*scene, nullptr, poses, nullptr, "mi_scene_set_poses");
+  });
+}
+
+int mi_scene_get_poses(mi_scene* scene, mi_pose* out, uint32_t capacity, uint32_t* num_geometry) {
+  if (!scene || !num_geometry) { g_err = "mi_scene_get_poses: null argument"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] {
+    const uint32_t G = (uint32_t)scene->refit.geometry.size();
+    *num_geometry = G;
+    if (!out || !G) return;
+    if (capacity < G) throw ArgError("mi_scene_get_poses: capacity is smaller than the scene's geometry count");
+    if (scene->poses.posed) {
+      HIP_CHECK(hipSetDevice(scene->device));
+      HIP_CHECK(hipMemcpy(out, scene->poses.d_poses, (size_t)G * sizeof(mi_pose), hipMemcpyDeviceToHost));
+    } else {
+      const mi_pose identity = {{0.f, 0.f, 0.f, 1.f}, {0.f, 0.f, 0.f}, 1.f};
+      for (uint32_t g = 0; g < G; ++g) out[g] = identity;
+    }
+  });
+}
+
+int mi_scene_bake_poses(mi_scene* scene) {
+  if (!scene) { g_err = "mi_scene_bake_poses: null scene"; return MI_ERR_INVALID_ARG; }
+  poseInvalidate(*scene);
+  g_err.clear();
+  return MI_OK;
+}
+
+int mi_get_pose_timing(mi_scene* scene, double out[2]) {
+  if (!scene || !out) { g_err = "mi_get_pose_timing: null argument"; return MI_ERR_INVALID_ARG; }
+  for (int i = 0; i < 2; ++i) out[i] = scene->poses.ms[i];
+  g_err.clear();
+  return MI_OK;
 }
 
 int mi_scene_rebuild(mi_scene* scene, void* hip_stream, uint32_t* max_leaf_depth) {

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import RAY, POINT, POINT_HIT, BOX, TRI, OBOX, INVALID_PRIM      # noqa: F401  (the record dtypes of ray and point queries, side by side)
+from . import RAY, POINT, POINT_HIT, BOX, TRI, OBOX, POSE, INVALID_PRIM     # noqa: F401  (the record dtypes of ray and point queries, side by side)
 
 RAY_EPSILON = np.float32(5.9604644775390625e-08 * 1500.0)       # ray_math.h kRayEpsilon (precision_utils.hpp)
 LIGHT = np.array([18.0, 257.0, -1060.0], np.float32)            # the reference's shadow-trace light (trace.cpp:247)
@@ -95,6 +95,26 @@ def make_oboxes(centre: np.ndarray, half: np.ndarray, quat: np.ndarray | None = 
     b["half"] = half
     b["quat"] = matrix_to_quat(matrix) if quat is None else quat
     return b
+
+
+def make_poses(n: int, quat: np.ndarray | None = None, translation: np.ndarray | None = None, scale=None, matrix: np.ndarray | None = None) -> np.ndarray:
+    """A POSE array of n poses (rigid poses: IpuScene.set_poses) from [n, 4] quaternions x, y, z, w (they need not be unit) OR [n, 3, 3]
+    rotation matrices (converted by matrix_to_quat, as make_oboxes does), [n, 3] translations and a scale (a number or [n]). Missing
+    parts are the identity's: quaternion (0, 0, 0, 1), translation 0, scale 1."""
+    if quat is not None and matrix is not None:
+        raise ValueError("make_poses: at most one of quat and matrix may be given")
+    p = np.zeros(n, POSE)
+    p["quat"] = (0.0, 0.0, 0.0, 1.0)
+    p["scale"] = 1.0
+    if matrix is not None:
+        p["quat"] = matrix_to_quat(matrix)
+    elif quat is not None:
+        p["quat"] = quat
+    if translation is not None:
+        p["translation"] = translation
+    if scale is not None:
+        p["scale"] = scale
+    return p
 
 
 def primary_rays(host_scene) -> np.ndarray:
