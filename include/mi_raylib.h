@@ -602,6 +602,98 @@ int mi_obox_fill_device(mi_scene* scene, const void* d_oboxes, const uint64_t* d
 int mi_obox_offsets(mi_scene* scene, const mi_obox* oboxes, uint64_t* offsets /* n + 1 */, size_t n);
 int mi_obox_fill(mi_scene* scene, const mi_obox* oboxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n);
 
+/* Capsule queries: the primitives of the scene's CURRENT BVH within `radius` of each of n caller-supplied SEGMENTS [a, b] - a robot
+ * link, a limb, a character's body (FCL's, Bullet's and PhysX's capsule, URDF's collision cylinder with rounded ends). A capsule is
+ * also the volume a ball of that radius sweeps on a straight move from a to b: "does the ball hit anything on its way" is
+ * MI_CAPSULE_ANY. a == b is a closed ball, radius == 0 a bare segment. Whether there is a primitive (MI_CAPSULE_ANY), how many
+ * (MI_CAPSULE_COUNT), or which: two steps as for the box lists - the offsets of the capsules' segments, then the fill of a buffer
+ * the caller sized from them.
+ * Meaning: a primitive touches the capsule when the distance between the segment [a, b] and the primitive's SURFACE is at most
+ * radius. Touching is CLOSED: contact counts. Queries see SURFACES, as everywhere in this library. `reserved` is not read. The record
+ * is mi_overlap: the ids as mi_point_hit carries them, flags = 0 or MI_OVERLAP_CONTAINED, box = the index of the query the record
+ * belongs to, reserved = 0. The empty record is {MI_INVALID_PRIM, MI_INVALID_GEOM, MI_FLAG_ESCAPED, box, 0}.
+ * Arithmetic: binary32, one rounding per operation in the order written below, no contraction, correctly rounded divide and sqrt;
+ * dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, cross(a, v) = (a.y v.z - a.z v.y, a.z v.x - a.x v.z, a.x v.y - a.y v.x),
+ * dist2(p, q) = dot(p - q, p - q); sel_min(x, y) = x < y ? x : y, sel_max(x, y) = x > y ? x : y. Every rejection is a strict
+ * compare that a NaN fails: a NaN never rejects, and a query so large that its products overflow errs towards listing. One
+ * definition (ipu_ray_lib_amd/csrc/capsule_math.hpp, over point_math.hpp and box_math.hpp) serves the kernels and the host twins
+ * (mi_scene_host.h), which return the same bytes.
+ * Validity: a query is valid when all seven floats are finite and radius >= 0; -0 is legal. Any other query is not walked and finds
+ *   nothing; so does an empty scene.
+ * The query: d = b - a, r2 = radius radius, dd = dot(d, d); world bounds qmn_k = sel_min(a_k, b_k) - radius,
+ *   qmx_k = sel_max(a_k, b_k) + radius; the lateral axes X0 = (0, d.z, -d.y), X1 = (-d.z, 0, d.x), X2 = (d.y, -d.x, 0) (cross(d, e_k)),
+ *   R0 = width(d.z d.z + d.y d.y), R1 = width(d.z d.z + d.x d.x), R2 = width(d.y d.y + d.x d.x), Rd = width(dd), where
+ *   width(ll) = ll >= 2^-126 ? radius sqrtf(ll) : +inf. 2^-126 is the smallest normal binary32: an axis whose squared length has
+ *   underflowed (a == b, or a segment shorter than about 1e-19) separates nothing, since radius sqrtf(ll) would be 0, or short of its
+ *   bits, while the products X_k dh_k below are not, and would part the ball from boxes that it reaches. Such a query is decided at
+ *   the nodes by its world bounds, and errs towards listing like an overflowing one.
+ * The bounds test capsule_meets_bounds(mn, mx), used at every node and, unchanged, as the first step at every leaf on the primitive's
+ *   own bounds: first the six closed compares of mi_box_* against [qmn, qmx] (mn <= qmx && mx >= qmn on all axes). Then dl = mn - a,
+ *   dh = mx - a. For each lateral axis X_i, over its two non-zero components k (lower index first): up = t + t' with
+ *   t_k = X_k > 0 ? X_k dh_k : X_k dl_k; dn the same with dl and dh exchanged; the axis separates when dn > R_i || up < -R_i (relative
+ *   to a the segment projects onto 0, the ball widens that to +-R_i). For the axis d: up = (t0 + t1) + t2 and dn likewise over the three
+ *   components of d; it separates when dn > dd + Rd || up < -Rd. The bounds are met when the six compares hold and none of the four
+ *   axes separates. The test has no other arithmetic. For radius == 0 these are the six axes of the complete segment-against-box
+ *   separating-axis test; for a == b every width is +inf and the world bounds alone decide.
+ * point_seg_dist2(p): t = dot(p - a, d); t <= 0: dist2(p, a); t >= dd: dist2(p, b); else dist2(p, a + d (t / dd)).
+ * seg_seg_dist2(a, b, P, Q), Ericson, Real-Time Collision Detection 5.1.9 without its epsilon: d2 = Q - P, r = a - P, e = dot(d2, d2),
+ *   f = dot(d2, r). dd <= 0 && e <= 0: dot(r, r). dd <= 0: s = 0, t = clamp(f / e). Else c = dot(d, r); e <= 0: t = 0,
+ *   s = clamp(-c / dd). Else bb = dot(d, d2), denom = dd e - bb bb, s = denom != 0 ? clamp((bb f - c e) / denom) : 0,
+ *   t = (bb s + f) / e; t < 0: t = 0, s = clamp(-c / dd); else t > 1: t = 1, s = clamp((bb - c) / dd). c1 = a + d s, c2 = P + d2 t,
+ *   the result is dot(c1 - c2, c1 - c2). clamp(x) = x < 0 ? 0 : (x > 1 ? 1 : x): a NaN stays a NaN.
+ * The walk is the stackless preorder walk of the box queries. A node is entered when capsule_meets_bounds of its box holds, else
+ * passed. At a leaf so reached the primitive is tested; MI_CAPSULE_ANY stops at the first one that touches.
+ * Primitive test. First capsule_meets_bounds on the primitive's OWN bounds - those mi_box_* defines for that kind of primitive. Then:
+ *   Triangle (A, B, C) touches when any of these holds, tried in this order. 1, an end is near it: !(tri_point_dist2(A, B, C, a) > r2),
+ *     then the same for b - the closest point of the triangle as mi_point_query finds it, q, and dist2(p, q). 2, the segment is near an
+ *     edge: !(seg_seg_dist2(a, b, P, Q) > r2) for the edges AB, BC, CA in this order. 3, the segment pierces the face:
+ *     n = cross(B - A, C - A), sa = dot(n, a - A), sb = dot(n, b - A), !(sa > 0 && sb > 0) && !(sa < 0 && sb < 0) && !(sa == 0 && sb == 0),
+ *     and with u0 = A - a, u1 = B - a, u2 = C - a, w0 = dot(d, cross(u0, u1)), w1 = dot(d, cross(u1, u2)), w2 = dot(d, cross(u2, u0)): all
+ *     three >= 0 or all three <= 0. A coplanar segment has w0 = w1 = w2 = 0; the both-in-plane exclusion keeps one far from the triangle
+ *     from being listed, and coplanar pairs are decided by 1 and 2. MI_OVERLAP_CONTAINED: point_seg_dist2(V) <= r2 for all three
+ *     vertices; the capsule is convex, so this is exact.
+ *   Sphere (centre c, radius R): dmin2 = point_seg_dist2(c), dmax2 = sel_max(dist2(a, c), dist2(b, c)), s = R + radius, m = R - radius;
+ *     it touches when !(dmin2 > s s) && !(m > 0 && dmax2 < m m): the shell is reached from outside and from inside; a capsule wholly
+ *     inside the ball, away from the shell, touches nothing. CONTAINED: sqrtf(dmin2) + R <= radius.
+ *   Disc (normal n as given, centre c, r2' the squared radius as the scene holds it, r' = sqrtf(r2')): CONSERVATIVE as everywhere - three
+ *     necessary conditions. Its tight bounds pass the bounds test (the common first step); the segment reaches the plane's slab:
+ *     sa = dot(n, a - c), sb = dot(n, b - c), rn = radius sqrtf(dot(n, n)), !(sa > rn && sb > rn) && !(sa < -rn && sb < -rn); the capsule
+ *     reaches the ball: s = r' + radius, !(point_seg_dist2(c) > s s). No touching disc is missed, up to rounding; one whose rim the
+ *     capsule passes may be listed although it is not touched. CONTAINED is the sufficient sqrtf(dmin2) + r' <= radius: never set
+ *     wrongly, possibly absent for a thin disc.
+ * Order: records are sorted by the key (geom_id, prim_id), ascending; keys are unique within a query. This IS the definition: a
+ * segment shorter than the capsule's count holds the len smallest keys, and a list is the same bytes after a refit, a rebuild or
+ * mi_scene_set_geometry of the same contents. The node test has arithmetic, so this needs an argument: fl(a - c), fl(x a) for a fixed
+ * x and fl(a + b) are monotone in a and b, so for bounds A that contain bounds B every t_k of up is no smaller and every t_k of dn no
+ * larger for A than for B, and so are the sums as computed: up(A) >= up(B), dn(A) <= dn(B) on each of the four axes; R_i, Rd and
+ * dd + Rd do not depend on the bounds. Whatever B does not separate, A does not, and the six compares nest likewise. A node's device
+ * box contains its primitives' bounds as those functions compute them - the fact the box family rests on -, so a primitive whose own
+ * bounds pass has every ancestor's box pass, whatever tree is walked: what is listed is decided by the primitive and the query alone.
+ * mi_capsule_query_device: d_capsules = n mi_capsule, d_out = n uint8_t, 1 = a primitive touches the capsule (MI_CAPSULE_ANY; the
+ *   bytes need no alignment) or n uint32_t counts (MI_CAPSULE_COUNT), DEVICE memory.
+ * mi_capsule_offsets_device / mi_capsule_fill_device: offsets, segments, the cut at capacity (NO record at an index >= capacity is ever
+ *   written and none outside the segment), a decreasing pair = an empty segment, which is not walked, caller-made offsets (K i = the K
+ *   smallest keys of every capsule, padded), overlapping segments (unspecified records inside them) and the form (a max-heap inside the
+ *   segment, heap-sorted in place) are mi_box_offsets_device's and mi_box_fill_device's, with d_hits = `capacity` mi_overlap.
+ * Host entries: the same on HOST buffers, synchronous, in batches of mi_scene_set_ray_batch capsules; offsets and the `box` field
+ *   are global across batches (`box` is the index modulo 2^32). The fill shares mi_list_fill's device staging.
+ * Asynchrony, ordering against update / rebuild / set-geometry / set-poses, destruction, groups, batches and stream rules: those of
+ *   mi_box_*.
+ * n == 0 is a no-op. MI_ERR_INVALID_ARG, before any device work and without reading the scene: a null scene or buffer, an unknown kind
+ * ("unknown capsule kind"), capsules or hits that are not 16-byte aligned ("capsules must be 16-byte aligned"), counts that are not
+ * 4-byte aligned, offsets that are not 8-byte aligned, or more capsules in one launch (host entries: in one batch) than the 32-bit work
+ * index allows (0xFFBFFFFF).
+ * Options: none apply (one kernel, one arithmetic). Counters: nothing is added to casts or paths; under full_stats the box tests are
+ * added to "nodes visited" and the primitive tests to "leaf tests". */
+typedef struct { float a[3]; float radius; float b[3]; uint32_t reserved; } mi_capsule;   /* 32 B, two 16-byte loads */
+enum { MI_CAPSULE_ANY = 0, MI_CAPSULE_COUNT = 1 };
+int mi_capsule_query_device(mi_scene* scene, int kind, const void* d_capsules, void* d_out, size_t n, void* hip_stream);
+int mi_capsule_query(mi_scene* scene, int kind, const mi_capsule* capsules, void* out, size_t n);
+int mi_capsule_offsets_device(mi_scene* scene, const void* d_capsules, uint64_t* d_offsets /* n + 1 */, size_t n, void* hip_stream);
+int mi_capsule_fill_device(mi_scene* scene, const void* d_capsules, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream);
+int mi_capsule_offsets(mi_scene* scene, const mi_capsule* capsules, uint64_t* offsets /* n + 1 */, size_t n);
+int mi_capsule_fill(mi_scene* scene, const mi_capsule* capsules, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n);
+
 /* Geometry updates: new positions for the primitives of a live scene, the topology kept - triangles, geometry list, materials and
  * the BVH's shape - and every BVH box recomputed on the device (a refit: Embree's RTC_BUILD_QUALITY_REFIT commit, OptiX's
  * OPTIX_BUILD_OPERATION_UPDATE). Any pointer may be NULL = keep; a non-NULL array must have exactly the scene's count (a NULL array

@@ -67,12 +67,16 @@ CONTACT = np.dtype([("primID", "<u4"), ("geomID", "<u2"), ("flags", "<u2"), ("tr
 # (IpuScene.obox_touches / count_obox_overlaps / list_obox_overlaps / obox_fill_device)
 OBOX = np.dtype([("centre", "<f4", (3,)), ("reserved0", "<u4"), ("half", "<f4", (3,)), ("reserved1", "<u4"), ("quat", "<f4", (4,))])
 
+# mi_capsule: a capsule query - the segment [a, b] and a radius; its list holds OVERLAP records
+# (IpuScene.capsule_touches / count_capsule_overlaps / list_capsule_overlaps / capsule_fill_device)
+CAPSULE = np.dtype([("a", "<f4", (3,)), ("radius", "<f4"), ("b", "<f4", (3,)), ("reserved", "<u4")])
+
 # mi_pose: the rigid pose of one geometry - a quaternion x, y, z, w that need not be unit, a translation, a uniform scale
 # (IpuScene.set_poses / poses / pose; query_batches.make_poses)
 POSE = np.dtype([("quat", "<f4", (4,)), ("translation", "<f4", (3,)), ("scale", "<f4")])
 
 assert CROSSING.itemsize == 16 and NEIGHBOUR.itemsize == 16
-assert OBOX.itemsize == 48 and POSE.itemsize == 32
+assert OBOX.itemsize == 48 and POSE.itemsize == 32 and CAPSULE.itemsize == 32
 assert TRI.itemsize == 36 and CONTACT.itemsize == 16
 assert BOX.itemsize == 32 and OVERLAP.itemsize == 16
 assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
@@ -88,6 +92,7 @@ POINT_CLOSEST, POINT_WITHIN = 0, 1
 BOX_ANY, BOX_COUNT = 0, 1
 TRI_ANY, TRI_COUNT = 0, 1
 OBOX_ANY, OBOX_COUNT = 0, 1
+CAPSULE_ANY, CAPSULE_COUNT = 0, 1
 OVERLAP_CONTAINED = 16      # MI_OVERLAP_CONTAINED: the primitive's own bounds lie inside the box
 SIGN_INSIDE, SIGN_DISTANCE = 0, 1
 # the ray direction of an inside test when none is given (mi_point_sign: no zero component, off the diagonals of axis-aligned boxes)
@@ -225,6 +230,10 @@ def host_lib() -> C.CDLL:
         lib.mi_obox_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_obox_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_obox_meets_bounds_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mi_capsule_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_capsule_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_capsule_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_capsule_meets_bounds_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mi_pose_geometry_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
@@ -350,6 +359,12 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_obox_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_obox_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         lib.mi_obox_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        lib.mi_capsule_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_capsule_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_capsule_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_capsule_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_capsule_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        lib.mi_capsule_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         lib.mi_scene_set_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         lib.mi_scene_set_poses_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.mi_scene_get_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -691,6 +706,57 @@ def obox_meets_bounds_host(obox: np.ndarray, mn, mx) -> bool:
     q = np.ascontiguousarray(obox, OBOX).reshape(1)
     lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
     return bool(host_lib().mi_obox_meets_bounds_host(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
+
+
+def capsule_query_host(desc: SceneDesc, kind: int, capsules: np.ndarray):
+    """mi_capsule_query_host: the host twin of IpuScene.capsule_touches / .count_capsule_overlaps on desc's arrays and nodes - the same bytes. Returns
+    (out, visits): a bool array (CAPSULE_ANY) or a uint32 array (CAPSULE_COUNT), and {"box_tests", "prim_evals"} summed over the capsules (what
+    the device counts as nodes visited / leaf tests under option full_stats)."""
+    assert capsules.dtype == CAPSULE and capsules.ndim == 1
+    src = np.ascontiguousarray(capsules)
+    out = np.zeros(src.size, np.uint8 if kind == CAPSULE_ANY else np.uint32)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_capsule_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
+                                             out.ctypes.data if src.size else None, src.size, visits))
+    return (out.view(np.bool_) if kind == CAPSULE_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def capsule_offsets_host(desc: SceneDesc, capsules: np.ndarray):
+    """mi_capsule_offsets_host: the host twin of IpuScene.capsule_offsets - the same uint64 offsets. Returns (offsets, visits)."""
+    assert capsules.dtype == CAPSULE and capsules.ndim == 1
+    src = np.ascontiguousarray(capsules)
+    offsets = np.zeros(src.size + 1, np.uint64)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_capsule_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
+    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def capsule_fill_host(desc: SceneDesc, capsules: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
+    """mi_capsule_fill_host: the host twin of IpuScene.capsule_fill - the same bytes. Returns (recs, visits): recs is `hits` (an OVERLAP
+    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
+    nothing at or past `capacity` (None: recs.size) is written."""
+    assert capsules.dtype == CAPSULE and capsules.ndim == 1
+    src = np.ascontiguousarray(capsules)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    assert offsets.ndim == 1 and offsets.size == src.size + 1
+    if hits is None:
+        size = int(offsets.max()) if capacity is None else int(capacity)
+        hits = np.zeros(max(size, 1), OVERLAP)[:size]
+    assert hits.dtype == OVERLAP and hits.flags["C_CONTIGUOUS"]
+    capacity = hits.size if capacity is None else int(capacity)
+    assert 0 <= capacity <= hits.size
+    visits = (C.c_uint64 * 2)()
+    base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
+    _check_host(host_lib().mi_capsule_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
+    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def capsule_meets_bounds_host(capsule: np.ndarray, mn, mx) -> bool:
+    """mi_capsule_meets_bounds_host: capsule_meets_bounds of the capsule queries on its own - whether the bounds [mn, mx] (three floats
+    each) meet the one CAPSULE record `capsule`; False for a query that is not valid."""
+    q = np.ascontiguousarray(capsule, CAPSULE).reshape(1)
+    lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
+    return bool(host_lib().mi_capsule_meets_bounds_host(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
 
 
 def pose_geometry_host(desc: SceneDesc, poses: np.ndarray) -> dict:
@@ -1442,6 +1508,95 @@ class IpuScene:
         offsets, reads the total with one .item() (the one synchronisation), then allocates and fills."""
         oboxes, n = self._torch_oboxes("obox_list", centre, half, quat)
         return self._torch_all_lists(self.obox_offsets_device, self.obox_fill_device, oboxes, n, sync_when_empty=False)
+
+    # -- capsule queries (mi_capsule_query*, mi_capsule_offsets*, mi_capsule_fill*): every primitive that touches each capsule, by (geomID, primID) --
+    def _capsule_query_host(self, kind: int, capsules: np.ndarray, out: np.ndarray) -> np.ndarray:
+        src = self._source(capsules, CAPSULE)
+        self._check(self._lib.mi_capsule_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
+        return out
+
+    def capsule_touches(self, capsules: np.ndarray) -> np.ndarray:
+        """Whether some primitive touches each capsule (a CAPSULE array, host memory; contact counts): a bool array. Synchronous; batched
+        by setRayBatch."""
+        return self._capsule_query_host(CAPSULE_ANY, capsules, aligned_bytes(capsules.size)).view(np.bool_)
+
+    def count_capsule_overlaps(self, capsules: np.ndarray) -> np.ndarray:
+        """How many primitives touch each capsule (a CAPSULE array, host memory): a uint32 array."""
+        return self._capsule_query_host(CAPSULE_COUNT, capsules, np.zeros(capsules.size, np.uint32))
+
+    def capsule_offsets(self, capsules: np.ndarray) -> np.ndarray:
+        """mi_capsule_offsets: a uint64 array of capsules.size + 1 offsets - 0, then the running total of count_capsule_overlaps(capsules)."""
+        return self._offsets_host(self._lib.mi_capsule_offsets, self._source(capsules, CAPSULE))
+
+    def capsule_fill(self, capsules: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
+        """mi_capsule_fill: the primitives touching capsule i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (an
+        OVERLAP array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
+        (None: hits.size) is written."""
+        return self._fill_host(self._lib.mi_capsule_fill, OVERLAP, self._source(capsules, CAPSULE), offsets, hits, capacity)
+
+    def list_capsule_overlaps(self, capsules: np.ndarray):
+        """Every primitive that touches each capsule (a CAPSULE array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs an
+        OVERLAP array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are capsule i's primitives in ascending order of (geomID,
+        primID), flags = OVERLAP_CONTAINED where the primitive lies inside the capsule (a triangle: exactly; mi_raylib.h). Synchronous; batched by setRayBatch."""
+        return self._all_lists(self.capsule_offsets, self.capsule_fill, OVERLAP, capsules)
+
+    def first_capsule_overlaps(self, capsules: np.ndarray, k: int) -> np.ndarray:
+        """The k smallest (geomID, primID) of the primitives touching each capsule: an OVERLAP array [n, k]; capsules with fewer are padded
+        with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
+        return self._first_k(self.capsule_fill, OVERLAP, capsules, k)
+
+    def capsule_query_device(self, kind: int, d_capsules: int, d_out: int, n: int, stream: int = 0):
+        """mi_capsule_query_device on device pointers (n CAPSULE records in, n bytes or n uint32 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_capsule_query_device(self._h, int(kind), C.c_void_p(d_capsules), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
+
+    def capsule_offsets_device(self, d_capsules: int, d_offsets: int, n: int, stream: int = 0):
+        """mi_capsule_offsets_device on device pointers (n CAPSULE records in, n + 1 uint64 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_capsule_offsets_device(self._h, C.c_void_p(d_capsules), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
+
+    def capsule_fill_device(self, d_capsules: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
+        """mi_capsule_fill_device on device pointers (n CAPSULE records and n + 1 uint64 in, `capacity` OVERLAP records out), asynchronous
+        on `stream`."""
+        self._check(self._lib.mi_capsule_fill_device(self._h, C.c_void_p(d_capsules), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
+                                                 int(n), C.c_void_p(stream)))
+
+    @staticmethod
+    def _torch_capsules(what, a, b, radius):
+        import torch
+        a, b = a.to(torch.float32), b.to(torch.float32)
+        if a.ndim != 2 or a.shape[1] != 3 or b.shape != a.shape or not a.is_cuda or b.device != a.device:
+            raise ValueError(f"{what}: a and b must be [N, 3] tensors on one GPU")
+        n = a.shape[0]
+        if isinstance(radius, torch.Tensor):
+            r = radius.to(torch.float32)
+            if r.device != a.device or r.numel() not in (1, n):
+                raise ValueError(f"{what}: radius must be a number or an [N] tensor on the same GPU")
+            r = r.reshape(-1, 1).expand(n, 1)
+        else:
+            r = torch.full((n, 1), float(radius), dtype=torch.float32, device=a.device)
+        pad = torch.zeros((n, 1), dtype=torch.float32, device=a.device)
+        return torch.cat([a, r, b, pad], dim=1).contiguous(), n      # [N, 8] = n mi_capsule
+
+    def capsule_any(self, a, b, radius):
+        """Torch convenience over mi_capsule_query_device (CAPSULE_ANY): float32 device tensors a, b [N, 3] and radius (a number or
+        an [N] tensor), packed on the device and enqueued on torch.cuda.current_stream(). Returns an [N] bool device tensor: a
+        primitive lies within the radius of the segment - a ball of that radius moving from a to b hits something."""
+        capsules, n = self._torch_capsules("capsule_any", a, b, radius)
+        return self._torch_flags(capsules, n, self.capsule_query_device, CAPSULE_ANY)
+
+    def capsule_count(self, a, b, radius):
+        """The same for CAPSULE_COUNT: an [N] int32 device tensor, the number of primitives touching each capsule."""
+        import torch
+        capsules, n = self._torch_capsules("capsule_count", a, b, radius)
+        out = torch.empty(n, dtype=torch.int32, device=capsules.device)
+        self.capsule_query_device(CAPSULE_COUNT, capsules.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(capsules.device).cuda_stream)
+        return out
+
+    def capsule_list(self, a, b, radius):
+        """Torch convenience over mi_capsule_offsets_device + mi_capsule_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 -
+        the words of the OVERLAP records: primID, geomID | flags << 16, capsule, 0), capsule by capsule in ascending (geomID, primID).
+        It runs the offsets, reads the total with one .item() (the one synchronisation), then allocates and fills."""
+        capsules, n = self._torch_capsules("capsule_list", a, b, radius)
+        return self._torch_all_lists(self.capsule_offsets_device, self.capsule_fill_device, capsules, n, sync_when_empty=False)
 
     # -- triangle queries (mi_tri_query*, mi_tri_offsets*, mi_tri_fill*): every primitive that touches each triangle, by (geomID, primID) --
     def _tri_query_host(self, kind: int, tris: np.ndarray, out: np.ndarray) -> np.ndarray:

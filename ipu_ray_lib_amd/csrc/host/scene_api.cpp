@@ -258,6 +258,33 @@ int mi_obox_meets_bounds_host(const mi_obox* obox, const float mn[3], const floa
   return oboxMeetsBoundsHost(q, mn, mx) ? 1 : 0;
 }
 
+// Capsule queries: the host twins of mi_capsule_query* / mi_capsule_offsets* / mi_capsule_fill* (capsule_query_host.cpp)
+int mi_capsule_query_host(const mi_scene_desc* desc, int kind, const mi_capsule* capsules, void* out, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_capsule_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (kind != MI_CAPSULE_ANY && kind != MI_CAPSULE_COUNT) { g_err = "mi_capsule_query_host: unknown capsule kind"; return MI_ERR_INVALID_ARG; }
+  if (n && (!capsules || !out)) { g_err = "mi_capsule_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { capsuleQueryHost(*desc, kind, capsules, out, n, visits); });
+}
+
+int mi_capsule_offsets_host(const mi_scene_desc* desc, const mi_capsule* capsules, uint64_t* offsets, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_capsule_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!capsules || !offsets)) { g_err = "mi_capsule_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { capsuleOffsetsHost(*desc, capsules, offsets, n, visits); });
+}
+
+int mi_capsule_fill_host(const mi_scene_desc* desc, const mi_capsule* capsules, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_capsule_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!capsules || !offsets || !hits)) { g_err = "mi_capsule_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { capsuleFillHost(*desc, capsules, offsets, hits, capacity, n, visits); });
+}
+
+int mi_capsule_meets_bounds_host(const mi_capsule* capsule, const float mn[3], const float mx[3]) {
+  if (!capsule || !mn || !mx) return 0;
+  mi_capsule q;
+  memcpy(&q, capsule, sizeof q);
+  return capsuleMeetsBoundsHost(q, mn, mx) ? 1 : 0;
+}
+
 // The canonical primitive table of desc's arrays: the host twin of canon_prim_kernel (canon_kernels.hpp, mi_scene_set_geometry*) -
 // the same prefix, the same search and record per canonical index (canon_prims.hpp), the same checks with mi_scene_create's words
 int mi_canonical_prims(const mi_scene_desc* desc, void* out, uint32_t capacity, uint32_t* count) {

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import RAY, POINT, POINT_HIT, BOX, TRI, OBOX, POSE, INVALID_PRIM     # noqa: F401  (the record dtypes of ray and point queries, side by side)
+from . import RAY, POINT, POINT_HIT, BOX, TRI, OBOX, CAPSULE, POSE, INVALID_PRIM     # noqa: F401  (the record dtypes of ray and point queries, side by side)
 
 RAY_EPSILON = np.float32(5.9604644775390625e-08 * 1500.0)       # ray_math.h kRayEpsilon (precision_utils.hpp)
 LIGHT = np.array([18.0, 257.0, -1060.0], np.float32)            # the reference's shadow-trace light (trace.cpp:247)
@@ -95,6 +95,22 @@ def make_oboxes(centre: np.ndarray, half: np.ndarray, quat: np.ndarray | None = 
     b["half"] = half
     b["quat"] = matrix_to_quat(matrix) if quat is None else quat
     return b
+
+
+def make_capsules(a: np.ndarray, b: np.ndarray, radius) -> np.ndarray:
+    """A CAPSULE array (capsule queries: IpuScene.capsule_touches / count_capsule_overlaps / list_capsule_overlaps) from [N, 3] ends a
+    and b and a radius (a number or [N]). A ball of that radius moving straight from p0 to p1 is the capsule (p0, p1, radius)."""
+    a, b = np.asarray(a, np.float32).reshape(-1, 3), np.asarray(b, np.float32).reshape(-1, 3)
+    if a.shape != b.shape:
+        raise ValueError("make_capsules: a and b must have the same shape [N, 3]")
+    radius = np.asarray(radius, np.float32)
+    if radius.ndim > 1 or (radius.ndim == 1 and radius.size != len(a)):
+        raise ValueError("make_capsules: radius must be a number or an array of length N")
+    c = np.zeros(len(a), CAPSULE)
+    c["a"] = a
+    c["b"] = b
+    c["radius"] = radius
+    return c
 
 
 def make_poses(n: int, quat: np.ndarray | None = None, translation: np.ndarray | None = None, scale=None, matrix: np.ndarray | None = None) -> np.ndarray:
