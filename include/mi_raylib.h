@@ -694,6 +694,88 @@ int mi_capsule_fill_device(mi_scene* scene, const void* d_capsules, const uint64
 int mi_capsule_offsets(mi_scene* scene, const mi_capsule* capsules, uint64_t* offsets /* n + 1 */, size_t n);
 int mi_capsule_fill(mi_scene* scene, const mi_capsule* capsules, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n);
 
+/* Frustum queries: the primitives of the scene's CURRENT BVH inside or touching each of n caller-supplied REGIONS BOUNDED BY SIX
+ * PLANES - a camera's view volume, a screen tile's sub-frustum (tiled or clustered light lists), a marquee selection, a shadow
+ * cascade, a portal, a half-space, a slab. Whether there is a primitive (MI_FRUSTUM_ANY), how many (MI_FRUSTUM_COUNT), or which: two
+ * steps as for the box lists - the offsets of the frusta's segments, then the fill of a buffer the caller sized from them.
+ * Layout: mi_frustum is six planes nx, ny, nz, d: 96 bytes, six 16-byte loads, 16-byte aligned.
+ * Region: a point p is in the region when n_k.p + d_k >= 0 for all six planes. Normals point INWARD and need not be unit; the
+ *   region is whatever convex set the six half-spaces leave. The order of the planes means nothing.
+ * Absent planes: a plane of four zeros is absent: it holds everywhere. This gives half-spaces, slabs, wedges and a frustum without
+ *   a far plane; six absent planes list the whole scene.
+ * Validity and emptiness: an item is valid when its 24 floats are finite. Any other item is not walked and finds nothing; so does
+ *   an empty scene. A zero normal with d < 0 and contradictory planes are valid: the first lists nothing, the second no triangle -
+ *   that falls out of the arithmetic below and is not a special case (a zero normal with d = -0 is an absent plane). A sphere or a
+ *   disc wider than the gap between two contradictory planes is listed all the same: see their conservative test.
+ * Meaning: a primitive is listed when its SURFACE and the region share a point. Touching is CLOSED: contact counts. The record is
+ * mi_overlap: the ids as mi_point_hit carries them, flags = 0 or MI_OVERLAP_CONTAINED, box = the index of the query the record
+ * belongs to, reserved = 0. The empty record is {MI_INVALID_PRIM, MI_INVALID_GEOM, MI_FLAG_ESCAPED, box, 0}.
+ * Arithmetic: binary32, one rounding per operation in the order written below, no contraction, correctly rounded divide and sqrt;
+ * dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z, cross(a, v) = (a.y v.z - a.z v.y, a.z v.x - a.x v.z, a.x v.y - a.y v.x),
+ * at(k, p) = dot(n_k, p) + d_k, sel_min(x, y) = x < y ? x : y, sel_max(x, y) = x > y ? x : y. One definition
+ * (ipu_ray_lib_amd/csrc/frustum_math.hpp, over box_math.hpp) serves the kernels and the host twins (mi_scene_host.h), which return
+ * the same bytes.
+ * The bounds test frustum_meets_bounds(mn, mx), used at every node and, unchanged, as the first step at every leaf on the primitive's
+ *   own bounds, runs per plane on the corner of the bounds farthest along n: t_k = n_k > 0 ? n_k mx_k : n_k mn_k over the three axes,
+ *   up = ((t0 + t1) + t2) + d; the plane separates when up < 0, and the bounds are met when no plane separates. A NaN separates
+ *   nothing. The test has no other arithmetic: the region has no finite world bounds, so the planes are all there is. A box that
+ *   misses the region only past one of its edges or corners is entered.
+ * The walk is the stackless preorder walk of the box queries. A node is entered when frustum_meets_bounds of its box holds, else
+ * passed. At a leaf so reached the primitive is tested; MI_FRUSTUM_ANY stops at the first one that touches.
+ * Primitive test. First frustum_meets_bounds on the primitive's OWN bounds - those mi_box_* defines for that kind of primitive. Then:
+ *   Triangle (A, B, C): EXACT, three stages tried in this order over s[v][k] = at(k, V_v), 18 values.
+ *     1, a vertex in the region: some v has s[v][k] >= 0 for all k. MI_OVERLAP_CONTAINED when all three vertices have; the region is
+ *     convex, so this is exact.
+ *     2, an edge through the region: for AB, BC, CA in this order, [t0, t1] = [0, 1] is cut by the six planes in order from the
+ *     values sP, sQ of the edge's two ends: both < 0, the edge misses; else sP < 0: t0 = sel_max(t0, sP / (sP - sQ)); else sQ < 0:
+ *     t1 = sel_min(t1, sP / (sP - sQ)). The edge touches when it was not missed and t0 <= t1.
+ *     3, the region through the face (the floor under the camera): no vertex lies in the region and no edge meets it, so the
+ *     region's cross-section with the triangle's plane lies wholly inside the triangle or wholly outside; if not empty it is bounded
+ *     and has a corner where two of the planes meet the triangle's plane. m = cross(B - A, C - A), mA = dot(m, A); for the 15 pairs
+ *     i < j in order: c = cross(n_i, n_j), det = dot(c, m), the pair is skipped unless det != 0; u = cross(n_j, m), w = cross(m, n_i),
+ *     x_a = (((-d_i) u_a - d_j w_a) + mA c_a) / det on each axis a; the triangle touches when at(k, x) >= 0 for the other four planes
+ *     and dot(m, cross(B - A, x - A)) >= 0, dot(m, cross(C - B, x - B)) >= 0, dot(m, cross(A - C, x - C)) >= 0. A triangle with
+ *     m = 0 (a segment, a point) ends at stage 2, which is exact for it.
+ *   Sphere (centre c, radius R), CONSERVATIVE: with s = at(k, c), nn = dot(n_k, n_k), R2 = R R it is rejected only when some plane has
+ *     the whole ball behind it: s < 0 && s s > R2 nn. CONTAINED: s >= 0 && s s >= R2 nn for all six planes (exact for the ball).
+ *   Disc (normal n as given, centre c, r2 the squared radius as the scene holds it), CONSERVATIVE: its tight bounds pass the bounds
+ *     test (the common first step), then the sphere's test on the ball (c, R2 = r2); CONTAINED likewise (sufficient, never wrong).
+ *   Neither is ever missed, up to rounding. Each may be listed although it is not touched in two situations: it lies just outside
+ *   an edge or a corner of the region - no single plane has all of it behind it -, or the region lies strictly inside a sphere,
+ *   away from its shell.
+ * Order: records are sorted by the key (geom_id, prim_id), ascending; keys are unique within a query. This IS the definition: a
+ * segment shorter than the frustum's count holds the len smallest keys, and a list is the same bytes after a refit, a rebuild or
+ * mi_scene_set_geometry of the same contents. The node test has arithmetic, so this needs an argument: fl(x a) for a fixed x and
+ * fl(a + b) are monotone in a and b, so for bounds A that contain bounds B every t_k is no smaller for A than for B - n_k > 0 takes
+ * mx_k, which is no smaller, any other n_k takes mn_k, which is no larger, times a factor that is not positive -, and so is up as
+ * computed. Whatever plane does not separate B does not separate A. A node's device box contains its primitives' bounds as those
+ * functions compute them - the fact the box family rests on -, so a primitive whose own bounds pass has every ancestor's box pass,
+ * whatever tree is walked: what is listed is decided by the primitive and the query alone.
+ * mi_frustum_query_device: d_frusta = n mi_frustum, d_out = n uint8_t, 1 = a primitive touches the region (MI_FRUSTUM_ANY; the
+ *   bytes need no alignment) or n uint32_t counts (MI_FRUSTUM_COUNT), DEVICE memory.
+ * mi_frustum_offsets_device / mi_frustum_fill_device: offsets, segments, the cut at capacity (NO record at an index >= capacity is ever
+ *   written and none outside the segment), a decreasing pair = an empty segment, which is not walked, caller-made offsets (K i = the K
+ *   smallest keys of every frustum, padded), overlapping segments (unspecified records inside them) and the form (a max-heap inside the
+ *   segment, heap-sorted in place) are mi_box_offsets_device's and mi_box_fill_device's, with d_hits = `capacity` mi_overlap.
+ * Host entries: the same on HOST buffers, synchronous, in batches of mi_scene_set_ray_batch frusta; offsets and the `box` field
+ *   are global across batches (`box` is the index modulo 2^32). The fill shares mi_list_fill's device staging.
+ * Asynchrony, ordering against update / rebuild / set-geometry / set-poses, destruction, groups, batches and stream rules: those of
+ *   mi_box_*.
+ * n == 0 is a no-op. MI_ERR_INVALID_ARG, before any device work and without reading the scene: a null scene or buffer, an unknown kind
+ * ("unknown frustum kind"), frusta or hits that are not 16-byte aligned ("frusta must be 16-byte aligned"), counts that are not
+ * 4-byte aligned, offsets that are not 8-byte aligned, or more frusta in one launch (host entries: in one batch) than the 32-bit work
+ * index allows (0xFFBFFFFF).
+ * Options: none apply (one kernel, one arithmetic). Counters: nothing is added to casts or paths; under full_stats the box tests are
+ * added to "nodes visited" and the primitive tests to "leaf tests". */
+typedef struct { float planes[6][4]; } mi_frustum;   /* 96 B, six 16-byte loads: nx, ny, nz, d per plane */
+enum { MI_FRUSTUM_ANY = 0, MI_FRUSTUM_COUNT = 1 };
+int mi_frustum_query_device(mi_scene* scene, int kind, const void* d_frusta, void* d_out, size_t n, void* hip_stream);
+int mi_frustum_query(mi_scene* scene, int kind, const mi_frustum* frusta, void* out, size_t n);
+int mi_frustum_offsets_device(mi_scene* scene, const void* d_frusta, uint64_t* d_offsets /* n + 1 */, size_t n, void* hip_stream);
+int mi_frustum_fill_device(mi_scene* scene, const void* d_frusta, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream);
+int mi_frustum_offsets(mi_scene* scene, const mi_frustum* frusta, uint64_t* offsets /* n + 1 */, size_t n);
+int mi_frustum_fill(mi_scene* scene, const mi_frustum* frusta, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n);
+
 /* Geometry updates: new positions for the primitives of a live scene, the topology kept - triangles, geometry list, materials and
  * the BVH's shape - and every BVH box recomputed on the device (a refit: Embree's RTC_BUILD_QUALITY_REFIT commit, OptiX's
  * OPTIX_BUILD_OPERATION_UPDATE). Any pointer may be NULL = keep; a non-NULL array must have exactly the scene's count (a NULL array

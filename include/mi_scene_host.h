@@ -198,6 +198,26 @@ int mi_capsule_fill_host(const mi_scene_desc* desc, const mi_capsule* capsules, 
  * pointer gives 0. */
 int mi_capsule_meets_bounds_host(const mi_capsule* capsule, const float mn[3], const float mx[3]);
 
+/* Frustum queries on the host: the twins of mi_frustum_query* / mi_frustum_offsets* / mi_frustum_fill* (mi_raylib.h, where the contract
+ * is written), over desc->bvh_nodes and desc's arrays as mi_point_query_host reads them, boxes and primitives tested through the code
+ * the kernels run (ipu_ray_lib_amd/csrc/frustum_math.hpp). out: n uint8_t (MI_FRUSTUM_ANY) or n uint32_t (MI_FRUSTUM_COUNT); offsets:
+ * n + 1 uint64_t, written by mi_frustum_offsets_host (0, then the running total of the frusta's counts) and read by
+ * mi_frustum_fill_host, which writes `hits` as the device writes it - the len smallest keys (geom_id, prim_id) of each frustum
+ * ascending, then the empty record; nothing at or past `capacity`, nothing outside a segment, a frustum with an empty segment not
+ * walked. No alignment asked. They return the bytes the device returns; visits (may be NULL) receives {box tests, primitive tests}
+ * summed over the n frusta, what the device adds to "nodes visited" and "leaf tests" under option full_stats.
+ * MI_ERR_INVALID_ARG, with the function's name in mi_host_last_error: a null desc, an unknown kind, a null buffer with n > 0, nodes
+ * that are not a depth-first BVH2, a leaf whose geometry, primitive or vertex index is out of range. */
+int mi_frustum_query_host(const mi_scene_desc* desc, int kind, const mi_frustum* frusta, void* out, size_t n, uint64_t visits[2]);
+int mi_frustum_offsets_host(const mi_scene_desc* desc, const mi_frustum* frusta, uint64_t* offsets /* n + 1 */, size_t n, uint64_t visits[2]);
+int mi_frustum_fill_host(const mi_scene_desc* desc, const mi_frustum* frusta, const uint64_t* offsets, mi_overlap* hits, size_t capacity,
+                         size_t n, uint64_t visits[2]);
+
+/* frustum_meets_bounds of mi_frustum_* (mi_raylib.h) on its own: 1 when the bounds [mn, mx] meet the region, 0 when they do not or
+ * the query is not valid, from the function the kernels and the twins run. What the tests pin the test's monotonicity with. A null
+ * pointer gives 0. */
+int mi_frustum_meets_bounds_host(const mi_frustum* frustum, const float mn[3], const float mx[3]);
+
 /* Rigid poses on the host: the twin of the pose pass of mi_scene_set_poses* (mi_raylib.h, where the contract is written). `rest`
  * holds the rest geometry - its geometry list, mesh_info, vertices, normals, spheres and discs are read, nothing else -, poses one
  * mi_pose per geometry entry. Writes the posed arrays - rest->num_verts vertices, as many normals (normals_out may be NULL when the

@@ -75,8 +75,13 @@ CAPSULE = np.dtype([("a", "<f4", (3,)), ("radius", "<f4"), ("b", "<f4", (3,)), (
 # (IpuScene.set_poses / poses / pose; query_batches.make_poses)
 POSE = np.dtype([("quat", "<f4", (4,)), ("translation", "<f4", (3,)), ("scale", "<f4")])
 
+# mi_frustum: a frustum query - six planes nx, ny, nz, d, normals inward, a plane of four zeros absent; its list holds OVERLAP records
+# (IpuScene.frustum_touches / count_frustum_overlaps / list_frustum_overlaps / frustum_fill_device; query_batches.make_frusta)
+FRUSTUM = np.dtype([("planes", "<f4", (6, 4))])
+
 assert CROSSING.itemsize == 16 and NEIGHBOUR.itemsize == 16
 assert OBOX.itemsize == 48 and POSE.itemsize == 32 and CAPSULE.itemsize == 32
+assert FRUSTUM.itemsize == 96
 assert TRI.itemsize == 36 and CONTACT.itemsize == 16
 assert BOX.itemsize == 32 and OVERLAP.itemsize == 16
 assert TRACE_RESULT.itemsize == 84 and HIT.itemsize == 64 and RAY.itemsize == 32 and QUERY_HIT.itemsize == 32
@@ -93,6 +98,7 @@ BOX_ANY, BOX_COUNT = 0, 1
 TRI_ANY, TRI_COUNT = 0, 1
 OBOX_ANY, OBOX_COUNT = 0, 1
 CAPSULE_ANY, CAPSULE_COUNT = 0, 1
+FRUSTUM_ANY, FRUSTUM_COUNT = 0, 1
 OVERLAP_CONTAINED = 16      # MI_OVERLAP_CONTAINED: the primitive's own bounds lie inside the box
 SIGN_INSIDE, SIGN_DISTANCE = 0, 1
 # the ray direction of an inside test when none is given (mi_point_sign: no zero component, off the diagonals of axis-aligned boxes)
@@ -234,6 +240,10 @@ def host_lib() -> C.CDLL:
         lib.mi_capsule_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_capsule_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_capsule_meets_bounds_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.mi_frustum_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_frustum_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_frustum_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+        lib.mi_frustum_meets_bounds_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mi_pose_geometry_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
@@ -365,6 +375,12 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_capsule_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_capsule_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         lib.mi_capsule_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        lib.mi_frustum_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_frustum_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_frustum_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+        lib.mi_frustum_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.mi_frustum_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+        lib.mi_frustum_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         lib.mi_scene_set_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         lib.mi_scene_set_poses_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.mi_scene_get_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -757,6 +773,57 @@ def capsule_meets_bounds_host(capsule: np.ndarray, mn, mx) -> bool:
     q = np.ascontiguousarray(capsule, CAPSULE).reshape(1)
     lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
     return bool(host_lib().mi_capsule_meets_bounds_host(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
+
+
+def frustum_query_host(desc: SceneDesc, kind: int, frusta: np.ndarray):
+    """mi_frustum_query_host: the host twin of IpuScene.frustum_touches / .count_frustum_overlaps on desc's arrays and nodes - the same bytes. Returns
+    (out, visits): a bool array (FRUSTUM_ANY) or a uint32 array (FRUSTUM_COUNT), and {"box_tests", "prim_evals"} summed over the frusta (what
+    the device counts as nodes visited / leaf tests under option full_stats)."""
+    assert frusta.dtype == FRUSTUM and frusta.ndim == 1
+    src = np.ascontiguousarray(frusta)
+    out = np.zeros(src.size, np.uint8 if kind == FRUSTUM_ANY else np.uint32)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_frustum_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
+                                             out.ctypes.data if src.size else None, src.size, visits))
+    return (out.view(np.bool_) if kind == FRUSTUM_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def frustum_offsets_host(desc: SceneDesc, frusta: np.ndarray):
+    """mi_frustum_offsets_host: the host twin of IpuScene.frustum_offsets - the same uint64 offsets. Returns (offsets, visits)."""
+    assert frusta.dtype == FRUSTUM and frusta.ndim == 1
+    src = np.ascontiguousarray(frusta)
+    offsets = np.zeros(src.size + 1, np.uint64)
+    visits = (C.c_uint64 * 2)()
+    _check_host(host_lib().mi_frustum_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
+    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def frustum_fill_host(desc: SceneDesc, frusta: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
+    """mi_frustum_fill_host: the host twin of IpuScene.frustum_fill - the same bytes. Returns (recs, visits): recs is `hits` (an OVERLAP
+    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
+    nothing at or past `capacity` (None: recs.size) is written."""
+    assert frusta.dtype == FRUSTUM and frusta.ndim == 1
+    src = np.ascontiguousarray(frusta)
+    offsets = np.ascontiguousarray(offsets, np.uint64)
+    assert offsets.ndim == 1 and offsets.size == src.size + 1
+    if hits is None:
+        size = int(offsets.max()) if capacity is None else int(capacity)
+        hits = np.zeros(max(size, 1), OVERLAP)[:size]
+    assert hits.dtype == OVERLAP and hits.flags["C_CONTIGUOUS"]
+    capacity = hits.size if capacity is None else int(capacity)
+    assert 0 <= capacity <= hits.size
+    visits = (C.c_uint64 * 2)()
+    base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
+    _check_host(host_lib().mi_frustum_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
+    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def frustum_meets_bounds_host(frustum: np.ndarray, mn, mx) -> bool:
+    """mi_frustum_meets_bounds_host: frustum_meets_bounds of the frustum queries on its own - whether the bounds [mn, mx] (three floats
+    each) meet the one FRUSTUM record `frustum`; False for a query that is not valid."""
+    q = np.ascontiguousarray(frustum, FRUSTUM).reshape(1)
+    lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
+    return bool(host_lib().mi_frustum_meets_bounds_host(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
 
 
 def pose_geometry_host(desc: SceneDesc, poses: np.ndarray) -> dict:
@@ -1597,6 +1664,95 @@ class IpuScene:
         It runs the offsets, reads the total with one .item() (the one synchronisation), then allocates and fills."""
         capsules, n = self._torch_capsules("capsule_list", a, b, radius)
         return self._torch_all_lists(self.capsule_offsets_device, self.capsule_fill_device, capsules, n, sync_when_empty=False)
+
+    # -- frustum queries (mi_frustum_query*, mi_frustum_offsets*, mi_frustum_fill*): every primitive that touches each frustum, by (geomID, primID) --
+    def _frustum_query_host(self, kind: int, frusta: np.ndarray, out: np.ndarray) -> np.ndarray:
+        src = self._source(frusta, FRUSTUM)
+        self._check(self._lib.mi_frustum_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
+        return out
+
+    def frustum_touches(self, frusta: np.ndarray) -> np.ndarray:
+        """Whether some primitive touches each frustum (a FRUSTUM array, host memory; contact counts): a bool array. Synchronous; batched
+        by setRayBatch."""
+        return self._frustum_query_host(FRUSTUM_ANY, frusta, aligned_bytes(frusta.size)).view(np.bool_)
+
+    def count_frustum_overlaps(self, frusta: np.ndarray) -> np.ndarray:
+        """How many primitives touch each frustum (a FRUSTUM array, host memory): a uint32 array."""
+        return self._frustum_query_host(FRUSTUM_COUNT, frusta, np.zeros(frusta.size, np.uint32))
+
+    def frustum_offsets(self, frusta: np.ndarray) -> np.ndarray:
+        """mi_frustum_offsets: a uint64 array of frusta.size + 1 offsets - 0, then the running total of count_frustum_overlaps(frusta)."""
+        return self._offsets_host(self._lib.mi_frustum_offsets, self._source(frusta, FRUSTUM))
+
+    def frustum_fill(self, frusta: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
+        """mi_frustum_fill: the primitives touching frustum i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (an
+        OVERLAP array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
+        (None: hits.size) is written."""
+        return self._fill_host(self._lib.mi_frustum_fill, OVERLAP, self._source(frusta, FRUSTUM), offsets, hits, capacity)
+
+    def list_frustum_overlaps(self, frusta: np.ndarray):
+        """Every primitive that touches each frustum (a FRUSTUM array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs an
+        OVERLAP array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are frustum i's primitives in ascending order of (geomID,
+        primID), flags = OVERLAP_CONTAINED where the primitive lies inside the frustum (a triangle: exactly; mi_raylib.h). Synchronous; batched by setRayBatch."""
+        return self._all_lists(self.frustum_offsets, self.frustum_fill, OVERLAP, frusta)
+
+    def first_frustum_overlaps(self, frusta: np.ndarray, k: int) -> np.ndarray:
+        """The k smallest (geomID, primID) of the primitives touching each frustum: an OVERLAP array [n, k]; frusta with fewer are padded
+        with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
+        return self._first_k(self.frustum_fill, OVERLAP, frusta, k)
+
+    def frustum_query_device(self, kind: int, d_frusta: int, d_out: int, n: int, stream: int = 0):
+        """mi_frustum_query_device on device pointers (n FRUSTUM records in, n bytes or n uint32 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_frustum_query_device(self._h, int(kind), C.c_void_p(d_frusta), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
+
+    def frustum_offsets_device(self, d_frusta: int, d_offsets: int, n: int, stream: int = 0):
+        """mi_frustum_offsets_device on device pointers (n FRUSTUM records in, n + 1 uint64 out), asynchronous on `stream`."""
+        self._check(self._lib.mi_frustum_offsets_device(self._h, C.c_void_p(d_frusta), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
+
+    def frustum_fill_device(self, d_frusta: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
+        """mi_frustum_fill_device on device pointers (n FRUSTUM records and n + 1 uint64 in, `capacity` OVERLAP records out), asynchronous
+        on `stream`."""
+        self._check(self._lib.mi_frustum_fill_device(self._h, C.c_void_p(d_frusta), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
+                                                 int(n), C.c_void_p(stream)))
+
+    @staticmethod
+    def _torch_frusta(what, planes):
+        import torch
+        f = planes.to(torch.float32)
+        if f.ndim != 3 or f.shape[1:] != (6, 4) or not f.is_cuda:
+            raise ValueError(f"{what}: planes must be an [N, 6, 4] tensor on a GPU")
+        return f.contiguous(), f.shape[0]      # [N, 6, 4] = n mi_frustum
+
+    def frustum_any(self, planes):
+        """Torch convenience over mi_frustum_query_device (FRUSTUM_ANY): a float32 device tensor planes [N, 6, 4] (nx, ny, nz, d per
+        plane, normals inward, a plane of four zeros absent), enqueued on torch.cuda.current_stream(). Returns an [N] bool device
+        tensor: a primitive lies inside or touches the region."""
+        frusta, n = self._torch_frusta("frustum_any", planes)
+        return self._torch_flags(frusta, n, self.frustum_query_device, FRUSTUM_ANY)
+
+    def frustum_count(self, planes):
+        """The same for FRUSTUM_COUNT: an [N] int32 device tensor, the number of primitives touching each frustum."""
+        import torch
+        frusta, n = self._torch_frusta("frustum_count", planes)
+        out = torch.empty(n, dtype=torch.int32, device=frusta.device)
+        self.frustum_query_device(FRUSTUM_COUNT, frusta.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(frusta.device).cuda_stream)
+        return out
+
+    def frustum_list(self, planes):
+        """Torch convenience over mi_frustum_offsets_device + mi_frustum_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 -
+        the words of the OVERLAP records: primID, geomID | flags << 16, frustum, 0), frustum by frustum in ascending (geomID, primID).
+        It runs the offsets, reads the total with one .item() (the one synchronisation), then allocates and fills."""
+        frusta, n = self._torch_frusta("frustum_list", planes)
+        return self._torch_all_lists(self.frustum_offsets_device, self.frustum_fill_device, frusta, n, sync_when_empty=False)
+
+    def cull(self, view_proj, depth: str = "zo") -> np.ndarray:
+        """What a camera sees, occlusion aside: the list of the one frustum query_batches.make_frusta(view_proj=view_proj, depth=depth)
+        makes of a [4, 4] view-projection matrix acting on column vectors ("zo": clip z in [0, w]; "no": in [-w, w]), as int64 rows
+        (geomID, primID) [m, 2], ascending. list_frustum_overlaps on one frustum: synchronous, host memory."""
+        from . import query_batches as qb
+        frusta = qb.make_frusta(view_proj=np.asarray(view_proj, np.float64).reshape(4, 4), depth=depth)
+        _, recs = self.list_frustum_overlaps(frusta)
+        return np.stack([recs["geomID"].astype(np.int64), recs["primID"].astype(np.int64)], axis=1).reshape(-1, 2)
 
     # -- triangle queries (mi_tri_query*, mi_tri_offsets*, mi_tri_fill*): every primitive that touches each triangle, by (geomID, primID) --
     def _tri_query_host(self, kind: int, tris: np.ndarray, out: np.ndarray) -> np.ndarray:

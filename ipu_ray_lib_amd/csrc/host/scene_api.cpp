@@ -285,6 +285,33 @@ int mi_capsule_meets_bounds_host(const mi_capsule* capsule, const float mn[3], c
   return capsuleMeetsBoundsHost(q, mn, mx) ? 1 : 0;
 }
 
+// Frustum queries: the host twins of mi_frustum_query* / mi_frustum_offsets* / mi_frustum_fill* (frustum_query_host.cpp)
+int mi_frustum_query_host(const mi_scene_desc* desc, int kind, const mi_frustum* frusta, void* out, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_frustum_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (kind != MI_FRUSTUM_ANY && kind != MI_FRUSTUM_COUNT) { g_err = "mi_frustum_query_host: unknown frustum kind"; return MI_ERR_INVALID_ARG; }
+  if (n && (!frusta || !out)) { g_err = "mi_frustum_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { frustumQueryHost(*desc, kind, frusta, out, n, visits); });
+}
+
+int mi_frustum_offsets_host(const mi_scene_desc* desc, const mi_frustum* frusta, uint64_t* offsets, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_frustum_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!frusta || !offsets)) { g_err = "mi_frustum_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { frustumOffsetsHost(*desc, frusta, offsets, n, visits); });
+}
+
+int mi_frustum_fill_host(const mi_scene_desc* desc, const mi_frustum* frusta, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t visits[2]) {
+  if (!desc) { g_err = "mi_frustum_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
+  if (n && (!frusta || !offsets || !hits)) { g_err = "mi_frustum_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
+  return guarded([&] { frustumFillHost(*desc, frusta, offsets, hits, capacity, n, visits); });
+}
+
+int mi_frustum_meets_bounds_host(const mi_frustum* frustum, const float mn[3], const float mx[3]) {
+  if (!frustum || !mn || !mx) return 0;
+  mi_frustum q;
+  memcpy(&q, frustum, sizeof q);
+  return frustumMeetsBoundsHost(q, mn, mx) ? 1 : 0;
+}
+
 // The canonical primitive table of desc's arrays: the host twin of canon_prim_kernel (canon_kernels.hpp, mi_scene_set_geometry*) -
 // the same prefix, the same search and record per canonical index (canon_prims.hpp), the same checks with mi_scene_create's words
 int mi_canonical_prims(const mi_scene_desc* desc, void* out, uint32_t capacity, uint32_t* count) {

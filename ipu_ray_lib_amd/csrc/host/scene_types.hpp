@@ -141,6 +141,11 @@ void capsuleQueryHost(const mi_scene_desc& desc, int kind, const mi_capsule* cap
 void capsuleOffsetsHost(const mi_scene_desc& desc, const mi_capsule* capsules, uint64_t* offsets, size_t n, uint64_t* visits);
 void capsuleFillHost(const mi_scene_desc& desc, const mi_capsule* capsules, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t* visits);
 bool capsuleMeetsBoundsHost(const mi_capsule& capsule, const float mn[3], const float mx[3]);
+// frustum_query_host.cpp: the host twins of mi_frustum_query / mi_frustum_offsets / mi_frustum_fill (the same visits), and the bounds test alone
+void frustumQueryHost(const mi_scene_desc& desc, int kind, const mi_frustum* frusta, void* out, size_t n, uint64_t* visits);
+void frustumOffsetsHost(const mi_scene_desc& desc, const mi_frustum* frusta, uint64_t* offsets, size_t n, uint64_t* visits);
+void frustumFillHost(const mi_scene_desc& desc, const mi_frustum* frusta, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t* visits);
+bool frustumMeetsBoundsHost(const mi_frustum& frustum, const float mn[3], const float mx[3]);
 // pose_host.cpp: the host twin of the pose pass of mi_scene_set_poses* (normalsOut may be null for a scene without normals)
 void poseGeometryHost(const mi_scene_desc& rest, const mi_pose* poses, uint32_t numGeometry, mi_vec3* vertsOut, mi_vec3* normalsOut, mi_sphere* spheresOut,
                       mi_disc* discsOut);

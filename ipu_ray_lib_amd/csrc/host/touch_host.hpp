@@ -1,7 +1,7 @@
 // touch_host.hpp — the host twins of the touch family's kernels (touch_kernels.hpp), written once: query, offsets and fill over
 // caller buffers that need not be aligned. A family describes itself as on the device, by a struct Q:
 //
-//   Q::Item, Q::Record                          mi_box / mi_overlap, mi_tri / mi_contact, mi_obox / mi_overlap, mi_capsule / mi_overlap
+//   Q::Item, Q::Record                          mi_box / mi_overlap, mi_tri / mi_contact, mi_obox / mi_overlap, mi_capsule / mi_overlap, mi_frustum / mi_overlap
 //   Q::kQuery, Q::kOffsets, Q::kFill            the entries' names, for the message of what walkTable refuses
 //   Q::walk(nodes, item, boxTests, primTests, accept)
 //                                               the item's walk over walkHost (walk_host.hpp): accept(node index, flags) for each
@@ -20,7 +20,7 @@
 
 namespace mi::host {
 
-// kind 0 (MI_BOX_ANY, MI_TRI_ANY, MI_OBOX_ANY, MI_CAPSULE_ANY): n bytes, the walk stops at the first accept; kind 1: n uint32_t counts
+// kind 0 (MI_BOX_ANY, MI_TRI_ANY, MI_OBOX_ANY, MI_CAPSULE_ANY, MI_FRUSTUM_ANY): n bytes, the walk stops at the first accept; kind 1: n uint32_t counts
 template <class Q>
 void touchQueryHost(const mi_scene_desc& d, int kind, const typename Q::Item* items, void* out, size_t n, uint64_t* visits) {
   static_assert((int)MI_BOX_ANY == (int)MI_TRI_ANY, "any touch family's kind");

@@ -1,6 +1,7 @@
 // The host side of the eight query families - ray queries (mi_query*), point queries (mi_point_query*), crossing counts and
 // signs (mi_count_query*, mi_point_sign*), crossing lists (mi_list_*), neighbour lists (mi_near_*), box queries (mi_box_*),
-// triangle queries (mi_tri_*), oriented-box queries (mi_obox_*) and capsule queries (mi_capsule_*): one launch frame, one
+// triangle queries (mi_tri_*), oriented-box queries (mi_obox_*), capsule queries (mi_capsule_*) and frustum queries
+// (mi_frustum_*): one launch frame, one
 // build selection, one argument checker, one two-slot host pipeline, and the extern "C" entries on top of them. Included by
 // raylib.hip, in its translation unit, once mi_scene, LaunchSlot, guarded, HIP_CHECK and kMaxWorkItems are defined
 // (group_render.hpp is included the same way). A new family supplies a kernel header, a launcher body inside launchFrame, its
@@ -179,13 +180,14 @@ void launchNearFill(mi_scene& S, const mi_point* d_points, const uint64_t* d_off
 }
 
 // Touch queries - the box queries (Q = BoxTouch, box_kernels.hpp), the triangle queries (Q = TriTouch, contact_kernels.hpp) and the
-// oriented-box queries (Q = OBoxTouch, obox_kernels.hpp) and the capsule queries (Q = CapsuleTouch, capsule_kernels.hpp), whose
-// entries mirror the box queries'; the entry's name and the items' noun
+// oriented-box queries (Q = OBoxTouch, obox_kernels.hpp), the capsule queries (Q = CapsuleTouch, capsule_kernels.hpp) and the frustum
+// queries (Q = FrustumTouch, frustum_kernels.hpp), whose entries mirror the box queries'; the entry's name and the items' noun
 // for what launchFrame refuses come from Q. full_stats picks the instrumented build; no other option applies.
-// mi_box_query_device / mi_tri_query_device / mi_obox_query_device / mi_capsule_query_device: whether a primitive touches each item
-// (kind 0, MI_BOX_ANY = MI_TRI_ANY = MI_OBOX_ANY = MI_CAPSULE_ANY: n bytes) or how many do (kind 1, MI_*_COUNT: n uint32_t), one
-// thread per item (touch_query_kernel).
-static_assert((int)MI_BOX_COUNT == (int)MI_TRI_COUNT && (int)MI_BOX_COUNT == (int)MI_OBOX_COUNT && (int)MI_BOX_COUNT == (int)MI_CAPSULE_COUNT,
+// mi_box_query_device / mi_tri_query_device / mi_obox_query_device / mi_capsule_query_device / mi_frustum_query_device: whether a
+// primitive touches each item (kind 0, MI_BOX_ANY = MI_TRI_ANY = MI_OBOX_ANY = MI_CAPSULE_ANY = MI_FRUSTUM_ANY: n bytes) or how many do
+// (kind 1, MI_*_COUNT: n uint32_t), one thread per item (touch_query_kernel).
+static_assert((int)MI_BOX_COUNT == (int)MI_TRI_COUNT && (int)MI_BOX_COUNT == (int)MI_OBOX_COUNT && (int)MI_BOX_COUNT == (int)MI_CAPSULE_COUNT &&
+              (int)MI_BOX_COUNT == (int)MI_FRUSTUM_COUNT,
               "launchTouchQuery takes any touch family's kind");
 template <class Q>
 void launchTouchQuery(mi_scene& S, int kind, const typename Q::Item* d_items, void* d_out, size_t n, hipStream_t stream) {
@@ -235,6 +237,7 @@ constexpr const char* kBoxes16 = "boxes must be 16-byte aligned";
 constexpr const char* kTris4 = "triangles must be 4-byte aligned";
 constexpr const char* kOBoxes16 = "oriented boxes must be 16-byte aligned";
 constexpr const char* kCapsules16 = "capsules must be 16-byte aligned";
+constexpr const char* kFrusta16 = "frusta must be 16-byte aligned";
 constexpr size_t kNoLimit = ~(size_t)0;      // (a host entry: its limit is per batch, hostBatch)
 
 // The argument rules of every query entry, in the order the entries have always applied them: the scene, the kind (kindBad: the
@@ -292,9 +295,13 @@ bool capsuleQueryBad(const char* fn, const mi_scene* scene, int kind, const void
   return queryArgsBad(fn, scene, kind != MI_CAPSULE_ANY && kind != MI_CAPSULE_COUNT ? "unknown capsule kind" : nullptr, nullptr, n, limit, "capsules",
                       {{capsules, 16, kCapsules16}, {out, kind == MI_CAPSULE_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
 }
-// (the entries of the crossing lists, the neighbour lists, the box lists, the contact lists, the oriented-box lists and the capsule
-// lists: `in` the rays, the points, the boxes, the oriented boxes, the capsules - 16-byte aligned - or the triangles - inAlign = 4;
-// hits: only the fill's)
+bool frustumQueryBad(const char* fn, const mi_scene* scene, int kind, const void* frusta, const void* out, size_t n, size_t limit) {
+  return queryArgsBad(fn, scene, kind != MI_FRUSTUM_ANY && kind != MI_FRUSTUM_COUNT ? "unknown frustum kind" : nullptr, nullptr, n, limit, "frusta",
+                      {{frusta, 16, kFrusta16}, {out, kind == MI_FRUSTUM_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
+}
+// (the entries of the crossing lists, the neighbour lists, the box lists, the contact lists, the oriented-box lists, the capsule
+// lists and the frustum lists: `in` the rays, the points, the boxes, the oriented boxes, the capsules, the frusta - 16-byte aligned -
+// or the triangles - inAlign = 4; hits: only the fill's)
 bool listQueryBad(const char* fn, const mi_scene* scene, const char* noun, const char* inWhy, const void* in, const void* offsets, const void* hits, bool fill, size_t n, size_t limit,
                   size_t inAlign = 16) {
   return queryArgsBad(fn, scene, nullptr, nullptr, n, limit, noun,
@@ -322,9 +329,11 @@ size_t hostBatch(const char* fn, const char* noun, const mi_scene* scene, size_t
 }
 
 // The device buffers and streams of the pipeline's slots: kept by the scene between calls, regrown when a batch is larger than
-// any before. A slot holds `batch` items in - sized for the largest, the 48-byte oriented box; a triangle is 36 bytes, rays, points,
-// boxes and capsules are 32 - and `batch` 32-byte records out: room for any of the results, or batch + 1 offsets.
-constexpr size_t kQueryItemBytes = std::max({sizeof(mi_ray), sizeof(mi_point), sizeof(mi_box), sizeof(mi_tri), sizeof(mi_obox), sizeof(mi_capsule)});
+// any before. A slot holds `batch` items in - sized for the largest, the 96-byte frustum; an oriented box is 48 bytes, a triangle 36,
+// rays, points, boxes and capsules are 32 - and `batch` 32-byte records out: room for any of the results, or batch + 1 offsets.
+// kQueryItemBytes sizes these input slots and nothing else.
+constexpr size_t kQueryItemBytes = std::max({sizeof(mi_ray), sizeof(mi_point), sizeof(mi_box), sizeof(mi_tri), sizeof(mi_obox), sizeof(mi_capsule), sizeof(mi_frustum)});
+static_assert(kQueryItemBytes == 96, "the pipeline's input slots hold the largest item, mi_frustum");
 void ensureQuerySlots(mi_scene* scene, size_t batch, int slots) {
   for (int i = 0; i < slots; ++i) {
     if (scene->qCap[i] < batch) {
@@ -360,7 +369,7 @@ void pipelinedQuery(mi_scene* scene, const void* in, size_t inSize, void* out, s
   } catch (...) { (void)hipDeviceSynchronize(); throw; }
 }
 
-// mi_list_offsets, mi_near_offsets, mi_box_offsets, mi_tri_offsets, mi_obox_offsets and mi_capsule_offsets on host buffers: every batch's prefix sum starts at 0 on the device; what precedes the
+// mi_list_offsets, mi_near_offsets, mi_box_offsets, mi_tri_offsets, mi_obox_offsets, mi_capsule_offsets and mi_frustum_offsets on host buffers: every batch's prefix sum starts at 0 on the device; what precedes the
 // batch is added here, batch by batch.
 template <class Launch>
 void offsetsHost(mi_scene* scene, const void* in, size_t inSize, uint64_t* offsets, size_t n, size_t batch, const Launch& launch) {
@@ -373,7 +382,7 @@ void offsetsHost(mi_scene* scene, const void* in, size_t inSize, uint64_t* offse
   }
 }
 
-// mi_list_fill, mi_near_fill, mi_box_fill, mi_tri_fill, mi_obox_fill and mi_capsule_fill on host buffers (in: rays, points, boxes, triangles, oriented boxes or capsules of inSize bytes; hits: 16-byte records of any of the kinds;
+// mi_list_fill, mi_near_fill, mi_box_fill, mi_tri_fill, mi_obox_fill, mi_capsule_fill and mi_frustum_fill on host buffers (in: rays, points, boxes, triangles, oriented boxes, capsules or frusta of inSize bytes; hits: 16-byte records of any of the kinds;
 // launch(d_in, d_offsets, d_hits, capacity, base, cnt, stream) enqueues one batch's fill): the pipeline's slots - the result buffer
 // carries a batch's offsets in - plus a staging buffer of records per slot. A batch's segments are packed from 0 in the staging -
 // the device sees offsets of its own, cut at `capacity` here already - and copied to where the caller's offsets put them: in one
@@ -813,6 +822,63 @@ int mi_capsule_fill(mi_scene* scene, const mi_capsule* capsules, const uint64_t*
   return guarded([&] {
     listFillHost(scene, capsules, sizeof(mi_capsule), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_overlap* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
       launchTouchFill<CapsuleTouch>(*scene, static_cast<const mi_capsule*>(d_in), d_off, d_hits, cap, base, cnt, st);
+    });
+  });
+}
+
+int mi_frustum_query_device(mi_scene* scene, int kind, const void* d_frusta, void* d_out, size_t n, void* hip_stream) {
+  if (frustumQueryBad("mi_frustum_query_device", scene, kind, d_frusta, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] { launchTouchQuery<FrustumTouch>(*scene, kind, static_cast<const mi_frustum*>(d_frusta), d_out, n, (hipStream_t)hip_stream); });
+}
+
+int mi_frustum_query(mi_scene* scene, int kind, const mi_frustum* frusta, void* out, size_t n) {
+  if (frustumQueryBad("mi_frustum_query", scene, kind, frusta, out, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch("mi_frustum_query", "frusta", scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    pipelinedQuery(scene, frusta, sizeof(mi_frustum), out, kind == MI_FRUSTUM_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchTouchQuery<FrustumTouch>(*scene, kind, static_cast<const mi_frustum*>(d_in), d_out, cnt, st);
+    });
+  });
+}
+
+int mi_frustum_offsets_device(mi_scene* scene, const void* d_frusta, uint64_t* d_offsets, size_t n, void* hip_stream) {
+  if (listQueryBad("mi_frustum_offsets_device", scene, "frusta", kFrusta16, d_frusta, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] {
+    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
+    launchTouchOffsets<FrustumTouch>(*scene, static_cast<const mi_frustum*>(d_frusta), d_offsets + 1, n, (hipStream_t)hip_stream);
+  });
+}
+
+int mi_frustum_fill_device(mi_scene* scene, const void* d_frusta, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream) {
+  if (listQueryBad("mi_frustum_fill_device", scene, "frusta", kFrusta16, d_frusta, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] { launchTouchFill<FrustumTouch>(*scene, static_cast<const mi_frustum*>(d_frusta), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
+}
+
+int mi_frustum_offsets(mi_scene* scene, const mi_frustum* frusta, uint64_t* offsets, size_t n) {
+  if (listQueryBad("mi_frustum_offsets", scene, "frusta", kFrusta16, frusta, offsets, nullptr, false, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch("mi_frustum_offsets", "frusta", scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    offsetsHost(scene, frusta, sizeof(mi_frustum), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchTouchOffsets<FrustumTouch>(*scene, static_cast<const mi_frustum*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
+    });
+  });
+}
+
+int mi_frustum_fill(mi_scene* scene, const mi_frustum* frusta, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n) {
+  if (listQueryBad("mi_frustum_fill", scene, "frusta", kFrusta16, frusta, offsets, hits, true, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch("mi_frustum_fill", "frusta", scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    listFillHost(scene, frusta, sizeof(mi_frustum), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_overlap* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
+      launchTouchFill<FrustumTouch>(*scene, static_cast<const mi_frustum*>(d_in), d_off, d_hits, cap, base, cnt, st);
     });
   });
 }

@@ -26,6 +26,7 @@
 #include "contact_kernels.hpp"       // triangle queries: every primitive that touches a caller's triangle
 #include "obox_kernels.hpp"          // oriented-box queries: every primitive that touches a caller's rotated box (these eight: launched and entered in query_drivers.hpp, included below)
 #include "capsule_kernels.hpp"       // capsule queries: every primitive within a radius of a caller's segment (these eight: launched and entered in query_drivers.hpp, included below)
+#include "frustum_kernels.hpp"       // frustum queries: every primitive inside or touching the region six caller-supplied planes leave (these eight: launched and entered in query_drivers.hpp, included below)
 #include "refit_kernels.hpp"         // geometry updates: the BVH refit and the record rewrite (mi_scene_update / mi_scene_update_device)
 #include "rebuild_kernels.hpp"       // topology rebuild of a live scene: an LBVH from its current geometry (mi_scene_rebuild)
 #include "pose_kernels.hpp"          // rigid poses: the posed geometry from a rest copy and one pose per geometry (mi_scene_set_poses*)

@@ -1,9 +1,10 @@
 // touch_kernels.hpp — the kernels of a "touch query": every primitive that TOUCHES a caller-supplied item, with no distance and
 // no order among the touching primitives but their key (geomID, primID). The box queries (box_kernels.hpp, Q = BoxTouch), the
-// triangle queries (contact_kernels.hpp, Q = TriTouch), the oriented-box queries (obox_kernels.hpp, Q = OBoxTouch) and the capsule
-// queries (capsule_kernels.hpp, Q = CapsuleTouch) are the four there are; a family describes itself by a struct Q:
+// triangle queries (contact_kernels.hpp, Q = TriTouch), the oriented-box queries (obox_kernels.hpp, Q = OBoxTouch), the capsule
+// queries (capsule_kernels.hpp, Q = CapsuleTouch) and the frustum queries (frustum_kernels.hpp, Q = FrustumTouch) are the five
+// there are; a family describes itself by a struct Q:
 //
-//   Q::Item, Q::Record                      what a batch holds (mi_box, mi_tri, mi_obox, mi_capsule) and what a list holds (mi_overlap, mi_contact: 16
+//   Q::Item, Q::Record                      what a batch holds (mi_box, mi_tri, mi_obox, mi_capsule, mi_frustum) and what a list holds (mi_overlap, mi_contact: 16
 //                                           bytes, {primID, geomID | flags << 16, item, 0})
 //   Q::Loaded, Q::load(items, idx)          item idx as the walk wants it, and its loads
 //   Q::walk<STATS>(sc, item, cs, accept)    the item's walk over walk_preorder (bvh_walk.hpp): accept(leaf index, geomID, flags) is

@@ -5,7 +5,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import RAY, POINT, POINT_HIT, BOX, TRI, OBOX, CAPSULE, POSE, INVALID_PRIM     # noqa: F401  (the record dtypes of ray and point queries, side by side)
+from . import RAY, POINT, POINT_HIT, BOX, TRI, OBOX, CAPSULE, FRUSTUM, POSE, INVALID_PRIM     # noqa: F401  (the record dtypes of ray and point queries, side by side)
 
 RAY_EPSILON = np.float32(5.9604644775390625e-08 * 1500.0)       # ray_math.h kRayEpsilon (precision_utils.hpp)
 LIGHT = np.array([18.0, 257.0, -1060.0], np.float32)            # the reference's shadow-trace light (trace.cpp:247)
@@ -111,6 +111,96 @@ def make_capsules(a: np.ndarray, b: np.ndarray, radius) -> np.ndarray:
     c["b"] = b
     c["radius"] = radius
     return c
+
+
+def camera_view_proj(eye, forward, up, fovy: float, aspect: float, near: float, far: float = np.inf, depth: str = "zo") -> np.ndarray:
+    """The [4, 4] float64 view-projection matrix, acting on column vectors, of a perspective camera at `eye` looking along `forward`
+    with `up` roughly upward, a vertical field of view of `fovy` RADIANS and width : height = `aspect`: right = forward x up,
+    clip w = the depth along forward, clip x = right.(p - eye) / (aspect tan(fovy / 2)), clip y = up'.(p - eye) / tan(fovy / 2), and
+    clip z / w running from 0 ("zo") or -1 ("no") at `near` to 1 at `far` (far = inf: the limit). What make_frusta(eye=...) makes
+    its planes from."""
+    if depth not in ("zo", "no"):
+        raise ValueError('camera_view_proj: depth must be "zo" or "no"')
+    eye, f, u = (np.asarray(v, np.float64).reshape(3) for v in (eye, forward, up))
+    f = f / np.linalg.norm(f)
+    r = np.cross(f, u)
+    r = r / np.linalg.norm(r)
+    u = np.cross(r, f)
+    t = np.tan(0.5 * float(fovy))
+    n, fa = float(near), float(far)
+    view = np.zeros((4, 4))
+    view[0, :3], view[1, :3], view[2, :3] = r, u, f
+    view[:3, 3] = -view[:3, :3] @ eye
+    view[3, 3] = 1.0
+    proj = np.zeros((4, 4))
+    proj[0, 0], proj[1, 1], proj[3, 2] = 1.0 / (float(aspect) * t), 1.0 / t, 1.0
+    if depth == "zo":
+        proj[2, 2], proj[2, 3] = (1.0, -n) if np.isinf(fa) else (fa / (fa - n), -fa * n / (fa - n))
+    else:
+        proj[2, 2], proj[2, 3] = (1.0, -2.0 * n) if np.isinf(fa) else ((fa + n) / (fa - n), -2.0 * fa * n / (fa - n))
+    return proj @ view
+
+
+def make_frusta(planes: np.ndarray | None = None, *, view_proj: np.ndarray | None = None, depth: str = "zo", eye=None, forward=None, up=None,
+                fovy: float | None = None, aspect: float = 1.0, near: float | None = None, far: float = np.inf, tiles=None) -> np.ndarray:
+    """A FRUSTUM array (frustum queries: IpuScene.frustum_touches / count_frustum_overlaps / list_frustum_overlaps), from one of
+      planes=[n, 6, 4]: the planes nx, ny, nz, d themselves - normals inward, not necessarily unit, a plane of four zeros absent;
+      view_proj=[4, 4] or [n, 4, 4]: view-projection matrices acting on column vectors. With rows r0..r3 the planes are, in this
+        order, r3 + r0, r3 - r0, r3 + r1, r3 - r1 (the sides), near - r2 for depth="zo" (clip z in [0, w]), r3 + r2 for "no" (clip z
+        in [-w, w]) - and far, r3 - r2; computed in float64, not normalised, rounded once;
+      eye=, forward=, up=, fovy= (radians), aspect=, near=, far=: one camera, through camera_view_proj; far=inf makes the far plane
+        absent.
+    tiles=(tx, ty) splits each frustum of the last two forms into tx ty sub-frusta, those of frustum i at [i tx ty, (i + 1) tx ty) in
+    row-major order - tile (column c, row r) at r tx + c, rows from clip y = -w upward, columns from clip x = -w: its sides are
+    r0 - x0 r3, x1 r3 - r0, r1 - y0 r3, y1 r3 - r1 with x0 = -1 + 2 c / tx, x1 = -1 + 2 (c + 1) / tx and y likewise. Neighbouring
+    tiles share their plane bit for bit up to the sign, and the outer tiles' outer planes are the parent's."""
+    if planes is not None:
+        if view_proj is not None or eye is not None or tiles is not None:
+            raise ValueError("make_frusta: planes= stands alone")
+        pl = np.asarray(planes, np.float32)
+        if pl.ndim == 2:
+            pl = pl[None]
+        if pl.ndim != 3 or pl.shape[1:] != (6, 4):
+            raise ValueError("make_frusta: planes must be [n, 6, 4]")
+        out = np.zeros(len(pl), FRUSTUM)
+        out["planes"] = pl
+        return out
+    if depth not in ("zo", "no"):
+        raise ValueError('make_frusta: depth must be "zo" or "no"')
+    no_far = False
+    if view_proj is None:
+        if eye is None or forward is None or up is None or fovy is None or near is None:
+            raise ValueError("make_frusta: give planes=, view_proj= or eye=, forward=, up=, fovy=, near=")
+        view_proj = camera_view_proj(eye, forward, up, fovy, aspect, near, far, depth)
+        no_far = bool(np.isinf(far))
+    elif eye is not None:
+        raise ValueError("make_frusta: view_proj= and eye= exclude each other")
+    m = np.asarray(view_proj, np.float64)
+    if m.ndim == 2:
+        m = m[None]
+    if m.ndim != 3 or m.shape[1:] != (4, 4):
+        raise ValueError("make_frusta: view_proj must be [4, 4] or [n, 4, 4]")
+    r0, r1, r2, r3 = m[:, 0], m[:, 1], m[:, 2], m[:, 3]
+    near_plane = r2 if depth == "zo" else r3 + r2
+    far_plane = np.zeros_like(r2) if no_far else r3 - r2
+    if tiles is None:
+        pl = np.stack([r3 + r0, r3 - r0, r3 + r1, r3 - r1, near_plane, far_plane], axis=1)
+    else:
+        tx, ty = (int(t) for t in tiles)
+        if tx < 1 or ty < 1:
+            raise ValueError("make_frusta: tiles must be two positive counts")
+        col, row = np.tile(np.arange(tx), ty), np.repeat(np.arange(ty), tx)                 # row-major: tile r tx + c
+        x0, x1 = -1.0 + 2.0 * col / tx, -1.0 + 2.0 * (col + 1) / tx
+        y0, y1 = -1.0 + 2.0 * row / ty, -1.0 + 2.0 * (row + 1) / ty
+        a = lambda v: v[:, None, :]                                                         # noqa: E731  [n, 1, 4] against [1, tiles, 1]
+        b = lambda v: v[None, :, None]                                                      # noqa: E731
+        k = tx * ty
+        sides = [a(r0) - b(x0) * a(r3), b(x1) * a(r3) - a(r0), a(r1) - b(y0) * a(r3), b(y1) * a(r3) - a(r1)]
+        rest = [np.broadcast_to(a(near_plane), (len(m), k, 4)), np.broadcast_to(a(far_plane), (len(m), k, 4))]
+        pl = np.stack(sides + rest, axis=2).reshape(len(m) * k, 6, 4)
+    out = np.zeros(len(pl), FRUSTUM)
+    out["planes"] = pl.astype(np.float32)
+    return out
 
 
 def make_poses(n: int, quat: np.ndarray | None = None, translation: np.ndarray | None = None, scale=None, matrix: np.ndarray | None = None) -> np.ndarray:
