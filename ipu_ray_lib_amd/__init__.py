@@ -12,6 +12,8 @@ There is NO CPU fallback for the device library: :func:`device_lib` raises if it
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
+import inspect
 import os
 import sys
 from pathlib import Path
@@ -226,24 +228,12 @@ def host_lib() -> C.CDLL:
         lib.mi_point_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_near_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
         lib.mi_near_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_box_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_box_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_box_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_tri_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_tri_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_tri_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_obox_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_obox_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_obox_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_obox_meets_bounds_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.mi_capsule_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_capsule_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_capsule_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_capsule_meets_bounds_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.mi_frustum_query_host.argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_frustum_offsets_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_frustum_fill_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
-        lib.mi_frustum_meets_bounds_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        for fam in _TOUCH_FAMILIES:
+            getattr(lib, fam.c("query_host")).argtypes = [C.POINTER(SceneDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+            getattr(lib, fam.c("offsets_host")).argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]
+            getattr(lib, fam.c("fill_host")).argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+            if fam.bounds_twin:
+                getattr(lib, fam.c("meets_bounds_host")).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mi_pose_geometry_host.argtypes = [C.POINTER(SceneDesc), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.mi_sphere_crossings_host.argtypes = [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float]
         lib.mi_sphere_crossings_host.restype = C.c_uint32
@@ -351,36 +341,13 @@ def device_lib(variants: bool = False) -> C.CDLL:
         lib.mi_near_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.mi_near_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
         lib.mi_near_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        lib.mi_box_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_box_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_box_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_box_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_box_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
-        lib.mi_box_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        lib.mi_tri_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_tri_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_tri_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_tri_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_tri_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
-        lib.mi_tri_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        lib.mi_obox_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_obox_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_obox_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_obox_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_obox_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
-        lib.mi_obox_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        lib.mi_capsule_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_capsule_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_capsule_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_capsule_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_capsule_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
-        lib.mi_capsule_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
-        lib.mi_frustum_query.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_frustum_query_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_frustum_offsets.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
-        lib.mi_frustum_offsets_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-        lib.mi_frustum_fill.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
-        lib.mi_frustum_fill_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
+        for fam in _TOUCH_FAMILIES:
+            getattr(lib, fam.c("query")).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+            getattr(lib, fam.c("query_device")).argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            getattr(lib, fam.c("offsets")).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+            getattr(lib, fam.c("offsets_device")).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+            getattr(lib, fam.c("fill")).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t]
+            getattr(lib, fam.c("fill_device")).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]
         lib.mi_scene_set_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         lib.mi_scene_set_poses_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
         lib.mi_scene_get_poses.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -630,200 +597,136 @@ def near_fill_host(desc: SceneDesc, points: np.ndarray, offsets: np.ndarray, cap
     return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
 
 
-def box_query_host(desc: SceneDesc, kind: int, boxes: np.ndarray):
-    """mi_box_query_host: the host twin of IpuScene.touches / .count_overlaps on desc's arrays and nodes - the same bytes. Returns
-    (out, visits): a bool array (BOX_ANY) or a uint32 array (BOX_COUNT), and {"box_tests", "prim_evals"} summed over the boxes (what
-    the device counts as nodes visited / leaf tests under option full_stats)."""
-    assert boxes.dtype == BOX and boxes.ndim == 1
-    src = np.ascontiguousarray(boxes)
-    out = np.zeros(src.size, np.uint8 if kind == BOX_ANY else np.uint32)
+# --------------------------------------------------------------------------------------------
+# The touch families (every primitive that touches a caller-supplied item - the rows below say which items): one row each. From
+# the rows come the argtypes of both libraries, the module-level host twins and the nine IpuScene methods of a family - one
+# implementation per kind of method, bound under the family's public names, which are not regular, with a docstring from one
+# template. The same list on the C side is TouchFamilies of csrc/query_drivers.hpp.
+# --------------------------------------------------------------------------------------------
+@dataclasses.dataclass(frozen=True)
+class _TouchFamily:
+    prefix: str           # the C entries are mi_<prefix>_query, mi_<prefix>_offsets_device, ...; <PREFIX> is the item's dtype here
+    item: np.dtype
+    record: np.dtype      # OVERLAP or CONTACT
+    arg: str              # what the Python entries call a batch: boxes, tris, ...
+    one: str              # the nouns of messages and docstrings
+    noun: str
+    any: str              # the public method names
+    count: str
+    list: str
+    first: str
+    contained: str = ""   # what a list's docstring says of the records' flags
+    bounds_twin: bool = False
+
+    def c(self, entry: str) -> str:
+        return f"mi_{self.prefix}_{entry}"
+
+    def words(self) -> dict:
+        """What the docstring templates are formatted with."""
+        ITEM, REC = self.prefix.upper(), "CONTACT" if self.record is CONTACT else "OVERLAP"
+        a = lambda w: ("an " if w[0] in "AEIOU" else "a ") + w      # noqa: E731
+        return dict(dataclasses.asdict(self), p=self.prefix, ITEM=ITEM, REC=REC, a_ITEM=a(ITEM), a_REC=a(REC), adj=self.one.replace(" ", "-"))
+
+
+_INSIDE = ", flags = OVERLAP_CONTAINED where the primitive lies inside the {one} (a triangle: exactly; mi_raylib.h)"
+_TOUCH_FAMILIES = (
+    _TouchFamily("box", BOX, OVERLAP, "boxes", "box", "boxes", "touches", "count_overlaps", "list_overlaps", "first_overlaps",
+                 contained=", flags = OVERLAP_CONTAINED where the primitive's own bounds lie inside the box"),
+    _TouchFamily("tri", TRI, CONTACT, "tris", "triangle", "triangles", "tri_touches", "count_contacts", "list_contacts", "first_contacts"),
+    _TouchFamily("obox", OBOX, OVERLAP, "oboxes", "oriented box", "oriented boxes", "obox_touches", "count_obox_overlaps", "list_obox_overlaps",
+                 "first_obox_overlaps", contained=_INSIDE.format(one="oriented box"), bounds_twin=True),
+    _TouchFamily("capsule", CAPSULE, OVERLAP, "capsules", "capsule", "capsules", "capsule_touches", "count_capsule_overlaps", "list_capsule_overlaps",
+                 "first_capsule_overlaps", contained=_INSIDE.format(one="capsule"), bounds_twin=True),
+    _TouchFamily("frustum", FRUSTUM, OVERLAP, "frusta", "frustum", "frusta", "frustum_touches", "count_frustum_overlaps", "list_frustum_overlaps",
+                 "first_frustum_overlaps", contained=_INSIDE.format(one="frustum"), bounds_twin=True),
+)
+assert all((globals()[f.prefix.upper() + "_ANY"], globals()[f.prefix.upper() + "_COUNT"]) == (0, 1) for f in _TOUCH_FAMILIES), "one kind numbering"
+_TOUCH_ANY, _TOUCH_COUNT = 0, 1
+
+
+def _bound(impl, fam: _TouchFamily, name: str, doc: str, qualname: str = ""):
+    """impl(fam, ...) as the public function `name`: impl's signature without `fam` and with its arguments `items`, `d_items` and
+    `item` under the family's own names (boxes, d_frusta, capsule), by which a caller may also pass them; `doc` is formatted with
+    the family's words."""
+    own = {"items": fam.arg, "d_items": "d_" + fam.arg, "item": fam.prefix}
+    sig = inspect.signature(impl)
+    sig = sig.replace(parameters=[q.replace(name=own.get(q.name, q.name)) for q in list(sig.parameters.values())[1:]])
+
+    def call(*args, **kwargs):
+        if kwargs:                                   # (the family's names are the signature's, not impl's)
+            bound = sig.bind(*args, **kwargs)
+            args, kwargs = bound.args, bound.kwargs
+        return impl(fam, *args, **kwargs)
+
+    call.__name__, call.__qualname__, call.__signature__, call.__doc__ = name, qualname + name, sig, doc.format(**fam.words())
+    return call
+
+
+def _visits(visits) -> dict:
+    return {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+
+
+def _touch_query_host(fam, desc: SceneDesc, kind: int, items: np.ndarray):
+    assert items.dtype == fam.item and items.ndim == 1
+    src = np.ascontiguousarray(items)
+    out = np.zeros(src.size, np.uint8 if kind == _TOUCH_ANY else np.uint32)
     visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_box_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
-                                             out.ctypes.data if src.size else None, src.size, visits))
-    return (out.view(np.bool_) if kind == BOX_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+    _check_host(getattr(host_lib(), fam.c("query_host"))(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
+                                                         out.ctypes.data if src.size else None, src.size, visits))
+    return (out.view(np.bool_) if kind == _TOUCH_ANY else out), _visits(visits)
 
 
-def box_offsets_host(desc: SceneDesc, boxes: np.ndarray):
-    """mi_box_offsets_host: the host twin of IpuScene.box_offsets - the same uint64 offsets. Returns (offsets, visits)."""
-    assert boxes.dtype == BOX and boxes.ndim == 1
-    src = np.ascontiguousarray(boxes)
+def _touch_offsets_host(fam, desc: SceneDesc, items: np.ndarray):
+    assert items.dtype == fam.item and items.ndim == 1
+    src = np.ascontiguousarray(items)
     offsets = np.zeros(src.size + 1, np.uint64)
     visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_box_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
-    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+    _check_host(getattr(host_lib(), fam.c("offsets_host"))(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
+    return offsets, _visits(visits)
 
 
-def box_fill_host(desc: SceneDesc, boxes: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
-    """mi_box_fill_host: the host twin of IpuScene.box_fill - the same bytes. Returns (recs, visits): recs is `hits` (an OVERLAP
-    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
-    nothing at or past `capacity` (None: recs.size) is written."""
-    assert boxes.dtype == BOX and boxes.ndim == 1
-    src = np.ascontiguousarray(boxes)
+def _touch_fill_host(fam, desc: SceneDesc, items: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
+    assert items.dtype == fam.item and items.ndim == 1
+    src = np.ascontiguousarray(items)
     offsets = np.ascontiguousarray(offsets, np.uint64)
     assert offsets.ndim == 1 and offsets.size == src.size + 1
     if hits is None:
         size = int(offsets.max()) if capacity is None else int(capacity)
-        hits = np.zeros(max(size, 1), OVERLAP)[:size]
-    assert hits.dtype == OVERLAP and hits.flags["C_CONTIGUOUS"]
+        hits = np.zeros(max(size, 1), fam.record)[:size]
+    assert hits.dtype == fam.record and hits.flags["C_CONTIGUOUS"]
     capacity = hits.size if capacity is None else int(capacity)
     assert 0 <= capacity <= hits.size
     visits = (C.c_uint64 * 2)()
-    base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
-    _check_host(host_lib().mi_box_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
-    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
+    base = hits.ctypes.data if hits.size else np.zeros(1, fam.record).ctypes.data
+    _check_host(getattr(host_lib(), fam.c("fill_host"))(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
+    return hits, _visits(visits)
 
 
-def obox_query_host(desc: SceneDesc, kind: int, oboxes: np.ndarray):
-    """mi_obox_query_host: the host twin of IpuScene.obox_touches / .count_obox_overlaps on desc's arrays and nodes - the same bytes. Returns
-    (out, visits): a bool array (OBOX_ANY) or a uint32 array (OBOX_COUNT), and {"box_tests", "prim_evals"} summed over the oriented boxes (what
-    the device counts as nodes visited / leaf tests under option full_stats)."""
-    assert oboxes.dtype == OBOX and oboxes.ndim == 1
-    src = np.ascontiguousarray(oboxes)
-    out = np.zeros(src.size, np.uint8 if kind == OBOX_ANY else np.uint32)
-    visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_obox_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
-                                             out.ctypes.data if src.size else None, src.size, visits))
-    return (out.view(np.bool_) if kind == OBOX_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def obox_offsets_host(desc: SceneDesc, oboxes: np.ndarray):
-    """mi_obox_offsets_host: the host twin of IpuScene.obox_offsets - the same uint64 offsets. Returns (offsets, visits)."""
-    assert oboxes.dtype == OBOX and oboxes.ndim == 1
-    src = np.ascontiguousarray(oboxes)
-    offsets = np.zeros(src.size + 1, np.uint64)
-    visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_obox_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
-    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def obox_fill_host(desc: SceneDesc, oboxes: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
-    """mi_obox_fill_host: the host twin of IpuScene.obox_fill - the same bytes. Returns (recs, visits): recs is `hits` (an OVERLAP
-    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
-    nothing at or past `capacity` (None: recs.size) is written."""
-    assert oboxes.dtype == OBOX and oboxes.ndim == 1
-    src = np.ascontiguousarray(oboxes)
-    offsets = np.ascontiguousarray(offsets, np.uint64)
-    assert offsets.ndim == 1 and offsets.size == src.size + 1
-    if hits is None:
-        size = int(offsets.max()) if capacity is None else int(capacity)
-        hits = np.zeros(max(size, 1), OVERLAP)[:size]
-    assert hits.dtype == OVERLAP and hits.flags["C_CONTIGUOUS"]
-    capacity = hits.size if capacity is None else int(capacity)
-    assert 0 <= capacity <= hits.size
-    visits = (C.c_uint64 * 2)()
-    base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
-    _check_host(host_lib().mi_obox_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
-    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def obox_meets_bounds_host(obox: np.ndarray, mn, mx) -> bool:
-    """mi_obox_meets_bounds_host: obox_meets_bounds of the oriented-box queries on its own - whether the bounds [mn, mx] (three floats
-    each) meet the one OBOX record `obox`; False for a query that is not valid."""
-    q = np.ascontiguousarray(obox, OBOX).reshape(1)
+def _touch_meets_bounds_host(fam, item: np.ndarray, mn, mx) -> bool:
+    q = np.ascontiguousarray(item, fam.item).reshape(1)
     lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
-    return bool(host_lib().mi_obox_meets_bounds_host(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
+    return bool(getattr(host_lib(), fam.c("meets_bounds_host"))(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
 
 
-def capsule_query_host(desc: SceneDesc, kind: int, capsules: np.ndarray):
-    """mi_capsule_query_host: the host twin of IpuScene.capsule_touches / .count_capsule_overlaps on desc's arrays and nodes - the same bytes. Returns
-    (out, visits): a bool array (CAPSULE_ANY) or a uint32 array (CAPSULE_COUNT), and {"box_tests", "prim_evals"} summed over the capsules (what
-    the device counts as nodes visited / leaf tests under option full_stats)."""
-    assert capsules.dtype == CAPSULE and capsules.ndim == 1
-    src = np.ascontiguousarray(capsules)
-    out = np.zeros(src.size, np.uint8 if kind == CAPSULE_ANY else np.uint32)
-    visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_capsule_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
-                                             out.ctypes.data if src.size else None, src.size, visits))
-    return (out.view(np.bool_) if kind == CAPSULE_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def capsule_offsets_host(desc: SceneDesc, capsules: np.ndarray):
-    """mi_capsule_offsets_host: the host twin of IpuScene.capsule_offsets - the same uint64 offsets. Returns (offsets, visits)."""
-    assert capsules.dtype == CAPSULE and capsules.ndim == 1
-    src = np.ascontiguousarray(capsules)
-    offsets = np.zeros(src.size + 1, np.uint64)
-    visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_capsule_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
-    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def capsule_fill_host(desc: SceneDesc, capsules: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
-    """mi_capsule_fill_host: the host twin of IpuScene.capsule_fill - the same bytes. Returns (recs, visits): recs is `hits` (an OVERLAP
+_TOUCH_TWINS = (        # suffix of the public name, implementation, docstring
+    ("query_host", _touch_query_host,
+     """mi_{p}_query_host: the host twin of IpuScene.{any} / .{count} on desc's arrays and nodes - the same bytes. Returns
+    (out, visits): a bool array ({ITEM}_ANY) or a uint32 array ({ITEM}_COUNT), and {{"box_tests", "prim_evals"}} summed over the
+    {noun} (what the device counts as nodes visited / leaf tests under option full_stats)."""),
+    ("offsets_host", _touch_offsets_host,
+     """mi_{p}_offsets_host: the host twin of IpuScene.{p}_offsets - the same uint64 offsets. Returns (offsets, visits)."""),
+    ("fill_host", _touch_fill_host,
+     """mi_{p}_fill_host: the host twin of IpuScene.{p}_fill - the same bytes. Returns (recs, visits): recs is `hits` ({a_REC}
     array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
-    nothing at or past `capacity` (None: recs.size) is written."""
-    assert capsules.dtype == CAPSULE and capsules.ndim == 1
-    src = np.ascontiguousarray(capsules)
-    offsets = np.ascontiguousarray(offsets, np.uint64)
-    assert offsets.ndim == 1 and offsets.size == src.size + 1
-    if hits is None:
-        size = int(offsets.max()) if capacity is None else int(capacity)
-        hits = np.zeros(max(size, 1), OVERLAP)[:size]
-    assert hits.dtype == OVERLAP and hits.flags["C_CONTIGUOUS"]
-    capacity = hits.size if capacity is None else int(capacity)
-    assert 0 <= capacity <= hits.size
-    visits = (C.c_uint64 * 2)()
-    base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
-    _check_host(host_lib().mi_capsule_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
-    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def capsule_meets_bounds_host(capsule: np.ndarray, mn, mx) -> bool:
-    """mi_capsule_meets_bounds_host: capsule_meets_bounds of the capsule queries on its own - whether the bounds [mn, mx] (three floats
-    each) meet the one CAPSULE record `capsule`; False for a query that is not valid."""
-    q = np.ascontiguousarray(capsule, CAPSULE).reshape(1)
-    lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
-    return bool(host_lib().mi_capsule_meets_bounds_host(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
-
-
-def frustum_query_host(desc: SceneDesc, kind: int, frusta: np.ndarray):
-    """mi_frustum_query_host: the host twin of IpuScene.frustum_touches / .count_frustum_overlaps on desc's arrays and nodes - the same bytes. Returns
-    (out, visits): a bool array (FRUSTUM_ANY) or a uint32 array (FRUSTUM_COUNT), and {"box_tests", "prim_evals"} summed over the frusta (what
-    the device counts as nodes visited / leaf tests under option full_stats)."""
-    assert frusta.dtype == FRUSTUM and frusta.ndim == 1
-    src = np.ascontiguousarray(frusta)
-    out = np.zeros(src.size, np.uint8 if kind == FRUSTUM_ANY else np.uint32)
-    visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_frustum_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
-                                             out.ctypes.data if src.size else None, src.size, visits))
-    return (out.view(np.bool_) if kind == FRUSTUM_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def frustum_offsets_host(desc: SceneDesc, frusta: np.ndarray):
-    """mi_frustum_offsets_host: the host twin of IpuScene.frustum_offsets - the same uint64 offsets. Returns (offsets, visits)."""
-    assert frusta.dtype == FRUSTUM and frusta.ndim == 1
-    src = np.ascontiguousarray(frusta)
-    offsets = np.zeros(src.size + 1, np.uint64)
-    visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_frustum_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
-    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def frustum_fill_host(desc: SceneDesc, frusta: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
-    """mi_frustum_fill_host: the host twin of IpuScene.frustum_fill - the same bytes. Returns (recs, visits): recs is `hits` (an OVERLAP
-    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
-    nothing at or past `capacity` (None: recs.size) is written."""
-    assert frusta.dtype == FRUSTUM and frusta.ndim == 1
-    src = np.ascontiguousarray(frusta)
-    offsets = np.ascontiguousarray(offsets, np.uint64)
-    assert offsets.ndim == 1 and offsets.size == src.size + 1
-    if hits is None:
-        size = int(offsets.max()) if capacity is None else int(capacity)
-        hits = np.zeros(max(size, 1), OVERLAP)[:size]
-    assert hits.dtype == OVERLAP and hits.flags["C_CONTIGUOUS"]
-    capacity = hits.size if capacity is None else int(capacity)
-    assert 0 <= capacity <= hits.size
-    visits = (C.c_uint64 * 2)()
-    base = hits.ctypes.data if hits.size else np.zeros(1, OVERLAP).ctypes.data
-    _check_host(host_lib().mi_frustum_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
-    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def frustum_meets_bounds_host(frustum: np.ndarray, mn, mx) -> bool:
-    """mi_frustum_meets_bounds_host: frustum_meets_bounds of the frustum queries on its own - whether the bounds [mn, mx] (three floats
-    each) meet the one FRUSTUM record `frustum`; False for a query that is not valid."""
-    q = np.ascontiguousarray(frustum, FRUSTUM).reshape(1)
-    lo, hi = np.ascontiguousarray(mn, np.float32).reshape(3), np.ascontiguousarray(mx, np.float32).reshape(3)
-    return bool(host_lib().mi_frustum_meets_bounds_host(q.ctypes.data, lo.ctypes.data, hi.ctypes.data))
+    nothing at or past `capacity` (None: recs.size) is written."""),
+    ("meets_bounds_host", _touch_meets_bounds_host,
+     """mi_{p}_meets_bounds_host: {p}_meets_bounds of the {adj} queries on its own - whether the bounds [mn, mx] (three floats
+    each) meet the one {ITEM} record `{p}`; False for a query that is not valid."""),
+)
+for _fam in _TOUCH_FAMILIES:
+    for _suffix, _impl, _doc in _TOUCH_TWINS:
+        if _impl is not _touch_meets_bounds_host or _fam.bounds_twin:
+            globals()[f"{_fam.prefix}_{_suffix}"] = _bound(_impl, _fam, f"{_fam.prefix}_{_suffix}", _doc)
 
 
 def pose_geometry_host(desc: SceneDesc, poses: np.ndarray) -> dict:
@@ -837,49 +740,6 @@ def pose_geometry_host(desc: SceneDesc, poses: np.ndarray) -> dict:
     ptr = [a.ctypes.data if a.size else None for a in out.values()]
     _check_host(host_lib().mi_pose_geometry_host(C.byref(desc), src.ctypes.data if src.size else None, src.size, *ptr))
     return out
-
-
-def tri_query_host(desc: SceneDesc, kind: int, tris: np.ndarray):
-    """mi_tri_query_host: the host twin of IpuScene.tri_touches / .count_contacts on desc's arrays and nodes - the same bytes. Returns
-    (out, visits): a bool array (TRI_ANY) or a uint32 array (TRI_COUNT), and {"box_tests", "prim_evals"} summed over the triangles
-    (what the device counts as nodes visited / leaf tests under option full_stats)."""
-    assert tris.dtype == TRI and tris.ndim == 1
-    src = np.ascontiguousarray(tris)
-    out = np.zeros(src.size, np.uint8 if kind == TRI_ANY else np.uint32)
-    visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_tri_query_host(C.byref(desc), int(kind), src.ctypes.data if src.size else None,
-                                             out.ctypes.data if src.size else None, src.size, visits))
-    return (out.view(np.bool_) if kind == TRI_ANY else out), {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def tri_offsets_host(desc: SceneDesc, tris: np.ndarray):
-    """mi_tri_offsets_host: the host twin of IpuScene.tri_offsets - the same uint64 offsets. Returns (offsets, visits)."""
-    assert tris.dtype == TRI and tris.ndim == 1
-    src = np.ascontiguousarray(tris)
-    offsets = np.zeros(src.size + 1, np.uint64)
-    visits = (C.c_uint64 * 2)()
-    _check_host(host_lib().mi_tri_offsets_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, src.size, visits))
-    return offsets, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
-
-
-def tri_fill_host(desc: SceneDesc, tris: np.ndarray, offsets: np.ndarray, capacity: int | None = None, hits: np.ndarray | None = None):
-    """mi_tri_fill_host: the host twin of IpuScene.tri_fill - the same bytes. Returns (recs, visits): recs is `hits` (a CONTACT
-    array the fill writes into, e.g. one of sentinels) or a fresh zeroed array as long as the offsets reach (at least `capacity`);
-    nothing at or past `capacity` (None: recs.size) is written."""
-    assert tris.dtype == TRI and tris.ndim == 1
-    src = np.ascontiguousarray(tris)
-    offsets = np.ascontiguousarray(offsets, np.uint64)
-    assert offsets.ndim == 1 and offsets.size == src.size + 1
-    if hits is None:
-        size = int(offsets.max()) if capacity is None else int(capacity)
-        hits = np.zeros(max(size, 1), CONTACT)[:size]
-    assert hits.dtype == CONTACT and hits.flags["C_CONTIGUOUS"]
-    capacity = hits.size if capacity is None else int(capacity)
-    assert 0 <= capacity <= hits.size
-    visits = (C.c_uint64 * 2)()
-    base = hits.ctypes.data if hits.size else np.zeros(1, CONTACT).ctypes.data
-    _check_host(host_lib().mi_tri_fill_host(C.byref(desc), src.ctypes.data if src.size else None, offsets.ctypes.data, base, capacity, src.size, visits))
-    return hits, {"box_tests": int(visits[0]), "prim_evals": int(visits[1])}
 
 
 DEVICE_NODE = np.dtype([("box", "<f4", (6,)), ("link", "<u4"), ("hit", "<u4")])     # the 32-byte device node: min/max per axis, two byte-offset successors
@@ -1219,6 +1079,14 @@ class IpuScene:
         return out.bool()
 
     @staticmethod
+    def _torch_counts(items, n, entry, *args):
+        """`_torch_flags` for an entry that writes a uint32 per item: an [N] int32 tensor."""
+        import torch
+        out = torch.empty(n, dtype=torch.int32, device=items.device)
+        entry(*args, items.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(items.device).cuda_stream)
+        return out
+
+    @staticmethod
     def _hit_columns(raw, first, vector):
         """The fields of [N, 8] float32 hit records (mi_query_hit, mi_point_hit) as tensors; `first`, `vector`: what the record's
         first float and its three floats are called."""
@@ -1398,56 +1266,8 @@ class IpuScene:
         offsets, raw = self._torch_first_k(self.near_fill_device, pts, n, k)
         return {**self._neighbour_columns(raw), "offsets": offsets}
 
-    # -- box queries (mi_box_query*, mi_box_offsets*, mi_box_fill*): every primitive that touches each box, by (geomID, primID) ------
-    def _box_query_host(self, kind: int, boxes: np.ndarray, out: np.ndarray) -> np.ndarray:
-        src = self._source(boxes, BOX)
-        self._check(self._lib.mi_box_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
-        return out
-
-    def touches(self, boxes: np.ndarray) -> np.ndarray:
-        """Whether some primitive touches each box (a BOX array, host memory; contact counts): a bool array. Synchronous; batched
-        by setRayBatch."""
-        return self._box_query_host(BOX_ANY, boxes, aligned_bytes(boxes.size)).view(np.bool_)
-
-    def count_overlaps(self, boxes: np.ndarray) -> np.ndarray:
-        """How many primitives touch each box (a BOX array, host memory): a uint32 array."""
-        return self._box_query_host(BOX_COUNT, boxes, np.zeros(boxes.size, np.uint32))
-
-    def box_offsets(self, boxes: np.ndarray) -> np.ndarray:
-        """mi_box_offsets: a uint64 array of boxes.size + 1 offsets - 0, then the running total of count_overlaps(boxes)."""
-        return self._offsets_host(self._lib.mi_box_offsets, self._source(boxes, BOX))
-
-    def box_fill(self, boxes: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
-        """mi_box_fill: the primitives touching box i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (an
-        OVERLAP array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
-        (None: hits.size) is written."""
-        return self._fill_host(self._lib.mi_box_fill, OVERLAP, self._source(boxes, BOX), offsets, hits, capacity)
-
-    def list_overlaps(self, boxes: np.ndarray):
-        """Every primitive that touches each box (a BOX array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs an
-        OVERLAP array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are box i's primitives in ascending order of (geomID,
-        primID), flags = OVERLAP_CONTAINED where the primitive's own bounds lie inside the box. Synchronous; batched by setRayBatch."""
-        return self._all_lists(self.box_offsets, self.box_fill, OVERLAP, boxes)
-
-    def first_overlaps(self, boxes: np.ndarray, k: int) -> np.ndarray:
-        """The k smallest (geomID, primID) of the primitives touching each box: an OVERLAP array [n, k]; boxes with fewer are padded
-        with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
-        return self._first_k(self.box_fill, OVERLAP, boxes, k)
-
-    def box_query_device(self, kind: int, d_boxes: int, d_out: int, n: int, stream: int = 0):
-        """mi_box_query_device on device pointers (n BOX records in, n bytes or n uint32 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_box_query_device(self._h, int(kind), C.c_void_p(d_boxes), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
-
-    def box_offsets_device(self, d_boxes: int, d_offsets: int, n: int, stream: int = 0):
-        """mi_box_offsets_device on device pointers (n BOX records in, n + 1 uint64 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_box_offsets_device(self._h, C.c_void_p(d_boxes), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
-
-    def box_fill_device(self, d_boxes: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
-        """mi_box_fill_device on device pointers (n BOX records and n + 1 uint64 in, `capacity` OVERLAP records out), asynchronous
-        on `stream`."""
-        self._check(self._lib.mi_box_fill_device(self._h, C.c_void_p(d_boxes), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
-                                                 int(n), C.c_void_p(stream)))
-
+    # -- the touch families (_TOUCH_FAMILIES): their host and device-pointer methods are bound below the class (_TOUCH_METHODS); here are
+    # -- the torch conveniences, whose argument lists differ per family, each over its packer --------------------------------------
     @staticmethod
     def _torch_boxes(what, lo, hi):
         import torch
@@ -1465,12 +1285,9 @@ class IpuScene:
         return self._torch_flags(boxes, n, self.box_query_device, BOX_ANY)
 
     def box_count(self, lo, hi):
-        """The same for BOX_COUNT: an [N] int32 device tensor, the number of primitives touching each box."""
-        import torch
+        """The same over mi_box_query_device for BOX_COUNT: an [N] int32 device tensor, the number of primitives touching each box."""
         boxes, n = self._torch_boxes("box_count", lo, hi)
-        out = torch.empty(n, dtype=torch.int32, device=boxes.device)
-        self.box_query_device(BOX_COUNT, boxes.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(boxes.device).cuda_stream)
-        return out
+        return self._torch_counts(boxes, n, self.box_query_device, BOX_COUNT)
 
     def box_list(self, lo, hi):
         """Torch convenience over mi_box_offsets_device + mi_box_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 - the
@@ -1494,56 +1311,6 @@ class IpuScene:
         hi = torch.stack(torch.meshgrid(axes[0][1:], axes[1][1:], axes[2][1:], indexing="ij"), dim=-1).reshape(-1, 3)
         return self.box_any(lo, hi).reshape(nx, ny, nz)
 
-    # -- oriented-box queries (mi_obox_query*, mi_obox_offsets*, mi_obox_fill*): every primitive that touches each rotated box, by (geomID, primID) --
-    def _obox_query_host(self, kind: int, oboxes: np.ndarray, out: np.ndarray) -> np.ndarray:
-        src = self._source(oboxes, OBOX)
-        self._check(self._lib.mi_obox_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
-        return out
-
-    def obox_touches(self, oboxes: np.ndarray) -> np.ndarray:
-        """Whether some primitive touches each box (an OBOX array, host memory; contact counts): a bool array. Synchronous; batched
-        by setRayBatch."""
-        return self._obox_query_host(OBOX_ANY, oboxes, aligned_bytes(oboxes.size)).view(np.bool_)
-
-    def count_obox_overlaps(self, oboxes: np.ndarray) -> np.ndarray:
-        """How many primitives touch each box (an OBOX array, host memory): a uint32 array."""
-        return self._obox_query_host(OBOX_COUNT, oboxes, np.zeros(oboxes.size, np.uint32))
-
-    def obox_offsets(self, oboxes: np.ndarray) -> np.ndarray:
-        """mi_obox_offsets: a uint64 array of oboxes.size + 1 offsets - 0, then the running total of count_obox_overlaps(oboxes)."""
-        return self._offsets_host(self._lib.mi_obox_offsets, self._source(oboxes, OBOX))
-
-    def obox_fill(self, oboxes: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
-        """mi_obox_fill: the primitives touching box i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (an
-        OVERLAP array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
-        (None: hits.size) is written."""
-        return self._fill_host(self._lib.mi_obox_fill, OVERLAP, self._source(oboxes, OBOX), offsets, hits, capacity)
-
-    def list_obox_overlaps(self, oboxes: np.ndarray):
-        """Every primitive that touches each box (an OBOX array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs an
-        OVERLAP array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are box i's primitives in ascending order of (geomID,
-        primID), flags = OVERLAP_CONTAINED where the primitive lies inside the box (a triangle: exactly; mi_raylib.h). Synchronous; batched by setRayBatch."""
-        return self._all_lists(self.obox_offsets, self.obox_fill, OVERLAP, oboxes)
-
-    def first_obox_overlaps(self, oboxes: np.ndarray, k: int) -> np.ndarray:
-        """The k smallest (geomID, primID) of the primitives touching each box: an OVERLAP array [n, k]; boxes with fewer are padded
-        with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
-        return self._first_k(self.obox_fill, OVERLAP, oboxes, k)
-
-    def obox_query_device(self, kind: int, d_oboxes: int, d_out: int, n: int, stream: int = 0):
-        """mi_obox_query_device on device pointers (n OBOX records in, n bytes or n uint32 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_obox_query_device(self._h, int(kind), C.c_void_p(d_oboxes), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
-
-    def obox_offsets_device(self, d_oboxes: int, d_offsets: int, n: int, stream: int = 0):
-        """mi_obox_offsets_device on device pointers (n OBOX records in, n + 1 uint64 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_obox_offsets_device(self._h, C.c_void_p(d_oboxes), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
-
-    def obox_fill_device(self, d_oboxes: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
-        """mi_obox_fill_device on device pointers (n OBOX records and n + 1 uint64 in, `capacity` OVERLAP records out), asynchronous
-        on `stream`."""
-        self._check(self._lib.mi_obox_fill_device(self._h, C.c_void_p(d_oboxes), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
-                                                 int(n), C.c_void_p(stream)))
-
     @staticmethod
     def _torch_oboxes(what, centre, half, quat):
         import torch
@@ -1562,12 +1329,9 @@ class IpuScene:
         return self._torch_flags(oboxes, n, self.obox_query_device, OBOX_ANY)
 
     def obox_count(self, centre, half, quat):
-        """The same for OBOX_COUNT: an [N] int32 device tensor, the number of primitives touching each oriented box."""
-        import torch
+        """The same over mi_obox_query_device for OBOX_COUNT: an [N] int32 device tensor, the number of primitives touching each oriented box."""
         oboxes, n = self._torch_oboxes("obox_count", centre, half, quat)
-        out = torch.empty(n, dtype=torch.int32, device=oboxes.device)
-        self.obox_query_device(OBOX_COUNT, oboxes.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(oboxes.device).cuda_stream)
-        return out
+        return self._torch_counts(oboxes, n, self.obox_query_device, OBOX_COUNT)
 
     def obox_list(self, centre, half, quat):
         """Torch convenience over mi_obox_offsets_device + mi_obox_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 - the
@@ -1575,56 +1339,6 @@ class IpuScene:
         offsets, reads the total with one .item() (the one synchronisation), then allocates and fills."""
         oboxes, n = self._torch_oboxes("obox_list", centre, half, quat)
         return self._torch_all_lists(self.obox_offsets_device, self.obox_fill_device, oboxes, n, sync_when_empty=False)
-
-    # -- capsule queries (mi_capsule_query*, mi_capsule_offsets*, mi_capsule_fill*): every primitive that touches each capsule, by (geomID, primID) --
-    def _capsule_query_host(self, kind: int, capsules: np.ndarray, out: np.ndarray) -> np.ndarray:
-        src = self._source(capsules, CAPSULE)
-        self._check(self._lib.mi_capsule_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
-        return out
-
-    def capsule_touches(self, capsules: np.ndarray) -> np.ndarray:
-        """Whether some primitive touches each capsule (a CAPSULE array, host memory; contact counts): a bool array. Synchronous; batched
-        by setRayBatch."""
-        return self._capsule_query_host(CAPSULE_ANY, capsules, aligned_bytes(capsules.size)).view(np.bool_)
-
-    def count_capsule_overlaps(self, capsules: np.ndarray) -> np.ndarray:
-        """How many primitives touch each capsule (a CAPSULE array, host memory): a uint32 array."""
-        return self._capsule_query_host(CAPSULE_COUNT, capsules, np.zeros(capsules.size, np.uint32))
-
-    def capsule_offsets(self, capsules: np.ndarray) -> np.ndarray:
-        """mi_capsule_offsets: a uint64 array of capsules.size + 1 offsets - 0, then the running total of count_capsule_overlaps(capsules)."""
-        return self._offsets_host(self._lib.mi_capsule_offsets, self._source(capsules, CAPSULE))
-
-    def capsule_fill(self, capsules: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
-        """mi_capsule_fill: the primitives touching capsule i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (an
-        OVERLAP array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
-        (None: hits.size) is written."""
-        return self._fill_host(self._lib.mi_capsule_fill, OVERLAP, self._source(capsules, CAPSULE), offsets, hits, capacity)
-
-    def list_capsule_overlaps(self, capsules: np.ndarray):
-        """Every primitive that touches each capsule (a CAPSULE array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs an
-        OVERLAP array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are capsule i's primitives in ascending order of (geomID,
-        primID), flags = OVERLAP_CONTAINED where the primitive lies inside the capsule (a triangle: exactly; mi_raylib.h). Synchronous; batched by setRayBatch."""
-        return self._all_lists(self.capsule_offsets, self.capsule_fill, OVERLAP, capsules)
-
-    def first_capsule_overlaps(self, capsules: np.ndarray, k: int) -> np.ndarray:
-        """The k smallest (geomID, primID) of the primitives touching each capsule: an OVERLAP array [n, k]; capsules with fewer are padded
-        with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
-        return self._first_k(self.capsule_fill, OVERLAP, capsules, k)
-
-    def capsule_query_device(self, kind: int, d_capsules: int, d_out: int, n: int, stream: int = 0):
-        """mi_capsule_query_device on device pointers (n CAPSULE records in, n bytes or n uint32 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_capsule_query_device(self._h, int(kind), C.c_void_p(d_capsules), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
-
-    def capsule_offsets_device(self, d_capsules: int, d_offsets: int, n: int, stream: int = 0):
-        """mi_capsule_offsets_device on device pointers (n CAPSULE records in, n + 1 uint64 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_capsule_offsets_device(self._h, C.c_void_p(d_capsules), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
-
-    def capsule_fill_device(self, d_capsules: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
-        """mi_capsule_fill_device on device pointers (n CAPSULE records and n + 1 uint64 in, `capacity` OVERLAP records out), asynchronous
-        on `stream`."""
-        self._check(self._lib.mi_capsule_fill_device(self._h, C.c_void_p(d_capsules), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
-                                                 int(n), C.c_void_p(stream)))
 
     @staticmethod
     def _torch_capsules(what, a, b, radius):
@@ -1651,12 +1365,9 @@ class IpuScene:
         return self._torch_flags(capsules, n, self.capsule_query_device, CAPSULE_ANY)
 
     def capsule_count(self, a, b, radius):
-        """The same for CAPSULE_COUNT: an [N] int32 device tensor, the number of primitives touching each capsule."""
-        import torch
+        """The same over mi_capsule_query_device for CAPSULE_COUNT: an [N] int32 device tensor, the number of primitives touching each capsule."""
         capsules, n = self._torch_capsules("capsule_count", a, b, radius)
-        out = torch.empty(n, dtype=torch.int32, device=capsules.device)
-        self.capsule_query_device(CAPSULE_COUNT, capsules.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(capsules.device).cuda_stream)
-        return out
+        return self._torch_counts(capsules, n, self.capsule_query_device, CAPSULE_COUNT)
 
     def capsule_list(self, a, b, radius):
         """Torch convenience over mi_capsule_offsets_device + mi_capsule_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 -
@@ -1664,56 +1375,6 @@ class IpuScene:
         It runs the offsets, reads the total with one .item() (the one synchronisation), then allocates and fills."""
         capsules, n = self._torch_capsules("capsule_list", a, b, radius)
         return self._torch_all_lists(self.capsule_offsets_device, self.capsule_fill_device, capsules, n, sync_when_empty=False)
-
-    # -- frustum queries (mi_frustum_query*, mi_frustum_offsets*, mi_frustum_fill*): every primitive that touches each frustum, by (geomID, primID) --
-    def _frustum_query_host(self, kind: int, frusta: np.ndarray, out: np.ndarray) -> np.ndarray:
-        src = self._source(frusta, FRUSTUM)
-        self._check(self._lib.mi_frustum_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
-        return out
-
-    def frustum_touches(self, frusta: np.ndarray) -> np.ndarray:
-        """Whether some primitive touches each frustum (a FRUSTUM array, host memory; contact counts): a bool array. Synchronous; batched
-        by setRayBatch."""
-        return self._frustum_query_host(FRUSTUM_ANY, frusta, aligned_bytes(frusta.size)).view(np.bool_)
-
-    def count_frustum_overlaps(self, frusta: np.ndarray) -> np.ndarray:
-        """How many primitives touch each frustum (a FRUSTUM array, host memory): a uint32 array."""
-        return self._frustum_query_host(FRUSTUM_COUNT, frusta, np.zeros(frusta.size, np.uint32))
-
-    def frustum_offsets(self, frusta: np.ndarray) -> np.ndarray:
-        """mi_frustum_offsets: a uint64 array of frusta.size + 1 offsets - 0, then the running total of count_frustum_overlaps(frusta)."""
-        return self._offsets_host(self._lib.mi_frustum_offsets, self._source(frusta, FRUSTUM))
-
-    def frustum_fill(self, frusta: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
-        """mi_frustum_fill: the primitives touching frustum i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (an
-        OVERLAP array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
-        (None: hits.size) is written."""
-        return self._fill_host(self._lib.mi_frustum_fill, OVERLAP, self._source(frusta, FRUSTUM), offsets, hits, capacity)
-
-    def list_frustum_overlaps(self, frusta: np.ndarray):
-        """Every primitive that touches each frustum (a FRUSTUM array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs an
-        OVERLAP array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are frustum i's primitives in ascending order of (geomID,
-        primID), flags = OVERLAP_CONTAINED where the primitive lies inside the frustum (a triangle: exactly; mi_raylib.h). Synchronous; batched by setRayBatch."""
-        return self._all_lists(self.frustum_offsets, self.frustum_fill, OVERLAP, frusta)
-
-    def first_frustum_overlaps(self, frusta: np.ndarray, k: int) -> np.ndarray:
-        """The k smallest (geomID, primID) of the primitives touching each frustum: an OVERLAP array [n, k]; frusta with fewer are padded
-        with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
-        return self._first_k(self.frustum_fill, OVERLAP, frusta, k)
-
-    def frustum_query_device(self, kind: int, d_frusta: int, d_out: int, n: int, stream: int = 0):
-        """mi_frustum_query_device on device pointers (n FRUSTUM records in, n bytes or n uint32 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_frustum_query_device(self._h, int(kind), C.c_void_p(d_frusta), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
-
-    def frustum_offsets_device(self, d_frusta: int, d_offsets: int, n: int, stream: int = 0):
-        """mi_frustum_offsets_device on device pointers (n FRUSTUM records in, n + 1 uint64 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_frustum_offsets_device(self._h, C.c_void_p(d_frusta), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
-
-    def frustum_fill_device(self, d_frusta: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
-        """mi_frustum_fill_device on device pointers (n FRUSTUM records and n + 1 uint64 in, `capacity` OVERLAP records out), asynchronous
-        on `stream`."""
-        self._check(self._lib.mi_frustum_fill_device(self._h, C.c_void_p(d_frusta), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
-                                                 int(n), C.c_void_p(stream)))
 
     @staticmethod
     def _torch_frusta(what, planes):
@@ -1731,12 +1392,9 @@ class IpuScene:
         return self._torch_flags(frusta, n, self.frustum_query_device, FRUSTUM_ANY)
 
     def frustum_count(self, planes):
-        """The same for FRUSTUM_COUNT: an [N] int32 device tensor, the number of primitives touching each frustum."""
-        import torch
+        """The same over mi_frustum_query_device for FRUSTUM_COUNT: an [N] int32 device tensor, the number of primitives touching each frustum."""
         frusta, n = self._torch_frusta("frustum_count", planes)
-        out = torch.empty(n, dtype=torch.int32, device=frusta.device)
-        self.frustum_query_device(FRUSTUM_COUNT, frusta.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(frusta.device).cuda_stream)
-        return out
+        return self._torch_counts(frusta, n, self.frustum_query_device, FRUSTUM_COUNT)
 
     def frustum_list(self, planes):
         """Torch convenience over mi_frustum_offsets_device + mi_frustum_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 -
@@ -1753,56 +1411,6 @@ class IpuScene:
         frusta = qb.make_frusta(view_proj=np.asarray(view_proj, np.float64).reshape(4, 4), depth=depth)
         _, recs = self.list_frustum_overlaps(frusta)
         return np.stack([recs["geomID"].astype(np.int64), recs["primID"].astype(np.int64)], axis=1).reshape(-1, 2)
-
-    # -- triangle queries (mi_tri_query*, mi_tri_offsets*, mi_tri_fill*): every primitive that touches each triangle, by (geomID, primID) --
-    def _tri_query_host(self, kind: int, tris: np.ndarray, out: np.ndarray) -> np.ndarray:
-        src = self._source(tris, TRI)
-        self._check(self._lib.mi_tri_query(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
-        return out
-
-    def tri_touches(self, tris: np.ndarray) -> np.ndarray:
-        """Whether some primitive touches each triangle (a TRI array, host memory; contact counts): a bool array. Synchronous;
-        batched by setRayBatch."""
-        return self._tri_query_host(TRI_ANY, tris, aligned_bytes(tris.size)).view(np.bool_)
-
-    def count_contacts(self, tris: np.ndarray) -> np.ndarray:
-        """How many primitives touch each triangle (a TRI array, host memory): a uint32 array."""
-        return self._tri_query_host(TRI_COUNT, tris, np.zeros(tris.size, np.uint32))
-
-    def tri_offsets(self, tris: np.ndarray) -> np.ndarray:
-        """mi_tri_offsets: a uint64 array of tris.size + 1 offsets - 0, then the running total of count_contacts(tris)."""
-        return self._offsets_host(self._lib.mi_tri_offsets, self._source(tris, TRI))
-
-    def tri_fill(self, tris: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
-        """mi_tri_fill: the primitives touching triangle i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] (a
-        CONTACT array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
-        (None: hits.size) is written."""
-        return self._fill_host(self._lib.mi_tri_fill, CONTACT, self._source(tris, TRI), offsets, hits, capacity)
-
-    def list_contacts(self, tris: np.ndarray):
-        """Every primitive that touches each triangle (a TRI array, host memory), as (offsets, recs): offsets uint64 [n + 1], recs a
-        CONTACT array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are triangle i's primitives in ascending order of
-        (geomID, primID). Synchronous; batched by setRayBatch."""
-        return self._all_lists(self.tri_offsets, self.tri_fill, CONTACT, tris)
-
-    def first_contacts(self, tris: np.ndarray, k: int) -> np.ndarray:
-        """The k smallest (geomID, primID) of the primitives touching each triangle: a CONTACT array [n, k]; triangles with fewer
-        are padded with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""
-        return self._first_k(self.tri_fill, CONTACT, tris, k)
-
-    def tri_query_device(self, kind: int, d_tris: int, d_out: int, n: int, stream: int = 0):
-        """mi_tri_query_device on device pointers (n TRI records in, n bytes or n uint32 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_tri_query_device(self._h, int(kind), C.c_void_p(d_tris), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
-
-    def tri_offsets_device(self, d_tris: int, d_offsets: int, n: int, stream: int = 0):
-        """mi_tri_offsets_device on device pointers (n TRI records in, n + 1 uint64 out), asynchronous on `stream`."""
-        self._check(self._lib.mi_tri_offsets_device(self._h, C.c_void_p(d_tris), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
-
-    def tri_fill_device(self, d_tris: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
-        """mi_tri_fill_device on device pointers (n TRI records and n + 1 uint64 in, `capacity` CONTACT records out), asynchronous
-        on `stream`."""
-        self._check(self._lib.mi_tri_fill_device(self._h, C.c_void_p(d_tris), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity),
-                                                 int(n), C.c_void_p(stream)))
 
     @staticmethod
     def _torch_tris(what, tris):
@@ -1826,12 +1434,9 @@ class IpuScene:
         return self._torch_flags(t, n, self.tri_query_device, TRI_ANY)
 
     def tri_count(self, tris):
-        """The same for TRI_COUNT: an [N] int32 device tensor, the number of primitives touching each triangle."""
-        import torch
+        """The same over mi_tri_query_device for TRI_COUNT: an [N] int32 device tensor, the number of primitives touching each triangle."""
         t, n = self._torch_tris("tri_count", tris)
-        out = torch.empty(n, dtype=torch.int32, device=t.device)
-        self.tri_query_device(TRI_COUNT, t.data_ptr(), out.data_ptr(), n, stream=torch.cuda.current_stream(t.device).cuda_stream)
-        return out
+        return self._torch_counts(t, n, self.tri_query_device, TRI_COUNT)
 
     def tri_list(self, tris):
         """Torch convenience over mi_tri_offsets_device + mi_tri_fill_device: (offsets [N + 1] int64, recs [total, 4] int32 - the
@@ -2187,6 +1792,83 @@ class IpuScene:
             self.close()
         except Exception:
             pass
+
+
+# The touch families' IpuScene methods: one implementation per kind, bound under each family's names (_TOUCH_FAMILIES).
+def _touch_query(fam, self, kind: int, items: np.ndarray, out: np.ndarray) -> np.ndarray:
+    src = self._source(items, fam.item)
+    self._check(getattr(self._lib, fam.c("query"))(self._h, kind, src.ctypes.data, out.ctypes.data, src.size))
+    return out
+
+
+def _touch_any(fam, self, items: np.ndarray) -> np.ndarray:
+    return _touch_query(fam, self, _TOUCH_ANY, items, aligned_bytes(items.size)).view(np.bool_)
+
+
+def _touch_count(fam, self, items: np.ndarray) -> np.ndarray:
+    return _touch_query(fam, self, _TOUCH_COUNT, items, np.zeros(items.size, np.uint32))
+
+
+def _touch_offsets(fam, self, items: np.ndarray) -> np.ndarray:
+    return self._offsets_host(getattr(self._lib, fam.c("offsets")), self._source(items, fam.item))
+
+
+def _touch_fill(fam, self, items: np.ndarray, offsets: np.ndarray, hits: np.ndarray, capacity: int | None = None) -> np.ndarray:
+    return self._fill_host(getattr(self._lib, fam.c("fill")), fam.record, self._source(items, fam.item), offsets, hits, capacity)
+
+
+def _touch_list(fam, self, items: np.ndarray):
+    return self._all_lists(lambda i: _touch_offsets(fam, self, i), lambda *a: _touch_fill(fam, self, *a), fam.record, items)
+
+
+def _touch_first(fam, self, items: np.ndarray, k: int) -> np.ndarray:
+    return self._first_k(lambda *a: _touch_fill(fam, self, *a), fam.record, items, k)
+
+
+def _touch_query_device(fam, self, kind: int, d_items: int, d_out: int, n: int, stream: int = 0):
+    self._check(getattr(self._lib, fam.c("query_device"))(self._h, int(kind), C.c_void_p(d_items), C.c_void_p(d_out), int(n), C.c_void_p(stream)))
+
+
+def _touch_offsets_device(fam, self, d_items: int, d_offsets: int, n: int, stream: int = 0):
+    self._check(getattr(self._lib, fam.c("offsets_device"))(self._h, C.c_void_p(d_items), C.c_void_p(d_offsets), int(n), C.c_void_p(stream)))
+
+
+def _touch_fill_device(fam, self, d_items: int, d_offsets: int, d_hits: int, capacity: int, n: int, stream: int = 0):
+    self._check(getattr(self._lib, fam.c("fill_device"))(self._h, C.c_void_p(d_items), C.c_void_p(d_offsets), C.c_void_p(d_hits), int(capacity), int(n),
+                                                         C.c_void_p(stream)))
+
+
+_TOUCH_METHODS = (      # the public name ({p}: the prefix; a bare word: the row's field), implementation, docstring
+    ("any", _touch_any,
+     """mi_{p}_query ({ITEM}_ANY): whether some primitive touches each {one} ({a_ITEM} array, host memory; contact counts): a bool
+        array. Synchronous; batched by setRayBatch."""),
+    ("count", _touch_count,
+     """mi_{p}_query ({ITEM}_COUNT): how many primitives touch each {one} ({a_ITEM} array, host memory): a uint32 array."""),
+    ("{p}_offsets", _touch_offsets,
+     """mi_{p}_offsets: a uint64 array of {arg}.size + 1 offsets - 0, then the running total of {count}({arg})."""),
+    ("{p}_fill", _touch_fill,
+     """mi_{p}_fill: the primitives touching {one} i, ascending in (geomID, primID), into hits[offsets[i]:offsets[i + 1]] ({a_REC}
+        array at a 16-byte aligned address, see aligned_bytes), cut or padded to that length; nothing at or past `capacity`
+        (None: hits.size) is written."""),
+    ("list", _touch_list,
+     """mi_{p}_offsets, then mi_{p}_fill: every primitive that touches each {one} ({a_ITEM} array, host memory), as (offsets, recs):
+        offsets uint64 [n + 1], recs {a_REC} array of offsets[n] records; recs[offsets[i]:offsets[i + 1]] are {one} i's primitives in
+        ascending order of (geomID, primID){contained}. Synchronous; batched by setRayBatch."""),
+    ("first", _touch_first,
+     """mi_{p}_fill alone: the k smallest (geomID, primID) of the primitives touching each {one}: {a_REC} array [n, k]; {noun} with
+        fewer are padded with the empty record (INVALID_PRIM, INVALID_GEOM, FLAG_ESCAPED). One fill, no count pass."""),
+    ("{p}_query_device", _touch_query_device,
+     """mi_{p}_query_device on device pointers (n {ITEM} records in, n bytes or n uint32 out), asynchronous on `stream`."""),
+    ("{p}_offsets_device", _touch_offsets_device,
+     """mi_{p}_offsets_device on device pointers (n {ITEM} records in, n + 1 uint64 out), asynchronous on `stream`."""),
+    ("{p}_fill_device", _touch_fill_device,
+     """mi_{p}_fill_device on device pointers (n {ITEM} records and n + 1 uint64 in, `capacity` {REC} records out), asynchronous
+        on `stream`."""),
+)
+for _fam in _TOUCH_FAMILIES:
+    for _name, _impl, _doc in _TOUCH_METHODS:
+        _name = _name.format(p=_fam.prefix) if "{" in _name else getattr(_fam, _name)
+        setattr(IpuScene, _name, _bound(_impl, _fam, _name, _doc, "IpuScene."))
 
 
 class _BorrowedScene(IpuScene):

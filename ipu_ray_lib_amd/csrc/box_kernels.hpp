@@ -4,13 +4,12 @@
 // lists (near_kernels.hpp): any / count, or count -> prefix sum -> fill. The kernels are the touch family's
 // (touch_kernels.hpp: touch_query_kernel, touch_count_kernel, touch_fill_kernel over BoxTouch); what is the boxes' own is here:
 //
-//   box_walk             walk_preorder (bvh_walk.hpp) with a box-box compare at the nodes (box_meets_bounds: closed, no arithmetic)
-//                        and box_touches_prim (box_math.hpp: the primitive's own bounds, then for a triangle the separating-axis
-//                        test) at a reached leaf. accept(leaf index, geomID, contained) is called for each touching primitive;
-//                        returning true ends the walk.
+//   BoxShape             (box_math.hpp) what touch_walk runs: a box-box compare at the nodes (box_meets_bounds: closed, no
+//                        arithmetic) and box_touches_prim (the primitive's own bounds, then for a triangle the separating-axis
+//                        test) at a reached leaf; a record's flags are MI_OVERLAP_CONTAINED or 0.
 //   load_box             a box's two 16-byte loads.
-//   BoxTouch             the two as the touch family takes them; a record's flags are MI_OVERLAP_CONTAINED or 0.
-// The host twin (host/box_query_host.cpp) returns the same bytes and the same visit totals.
+//   BoxTouch             the shape, the loads and the entries' names, as the touch kernels take them.
+// The host twin (host/touch_host.hpp over the same BoxShape) returns the same bytes and the same visit totals.
 #pragma once
 
 #include "touch_kernels.hpp"
@@ -20,16 +19,6 @@ namespace mi {
 static_assert(sizeof(mi_box) == 32, "mi_box must stay 32 bytes (two 16-byte loads)");
 static_assert(sizeof(mi_overlap) == 16, "mi_overlap must stay 16 bytes (one 16-byte load or store)");
 
-template <bool STATS, class Accept>
-__device__ __forceinline__ void box_walk(const DeviceScene& sc, f3 lo, f3 hi, CastStats& cs, const Accept& accept) {
-  walk_preorder<STATS>(sc, box_query_valid(lo, hi), cs,
-    [&](const GNode& nd) { return box_meets_bounds(mk(nd.minx, nd.miny, nd.minz), mk(nd.maxx, nd.maxy, nd.maxz), lo, hi); },
-    [&](uint32_t at, uint32_t type, const float (&f)[9]) {
-      bool contained;
-      return box_touches_prim(type & 0xFFFFu, f, lo, hi, &contained) && accept(at, type >> 16, contained);
-    });
-}
-
 // mi_box: lo[3], reserved0, hi[3], reserved1 - two 16-byte loads
 __device__ __forceinline__ void load_box(const mi_box* boxes, uint32_t idx, f3& lo, f3& hi) {
   const float4 a = reinterpret_cast<const float4*>(boxes)[2 * (size_t)idx], b = reinterpret_cast<const float4*>(boxes)[2 * (size_t)idx + 1];
@@ -37,19 +26,12 @@ __device__ __forceinline__ void load_box(const mi_box* boxes, uint32_t idx, f3& 
   hi = mk(b.x, b.y, b.z);
 }
 
-struct BoxTouch {
-  using Item = mi_box;
-  using Record = mi_overlap;
-  struct Loaded { f3 lo, hi; };
-  static constexpr const char *kQuery = "mi_box_query", *kOffsets = "mi_box_offsets", *kFill = "mi_box_fill", *kNoun = "boxes";
-  static __device__ __forceinline__ Loaded load(const mi_box* boxes, uint32_t idx) {
-    Loaded b;
+struct BoxTouch : SharedWalk<BoxShape> {
+  static constexpr const char *kQuery = "mi_box_query", *kOffsets = "mi_box_offsets", *kFill = "mi_box_fill";
+  static __device__ __forceinline__ Fields load(const mi_box* boxes, uint32_t idx) {
+    Fields b;
     load_box(boxes, idx, b.lo, b.hi);
     return b;
-  }
-  template <bool STATS, class Accept>
-  static __device__ __forceinline__ void walk(const DeviceScene& sc, const Loaded& b, CastStats& cs, const Accept& accept) {
-    box_walk<STATS>(sc, b.lo, b.hi, cs, [&](uint32_t at, uint32_t geomID, bool contained) { return accept(at, geomID, contained ? (uint32_t)MI_OVERLAP_CONTAINED : 0u); });
   }
 };
 

@@ -1,7 +1,7 @@
 // box_math.hpp — the arithmetic of box queries (mi_box_query* / mi_box_offsets* / mi_box_fill*, include/mi_raylib.h, where the
 // contract is written): whether a caller's axis-aligned box [lo, hi] touches a node's box, a triangle, a sphere's shell or a
 // disc. One definition, compiled by hipcc for the kernels (box_kernels.hpp) and by g++ for the host twin
-// (host/box_query_host.cpp): every function is a sequence of compares, selects and single binary32 operations in the order
+// (host/touch_host.hpp over BoxShape): every function is a sequence of compares, selects and single binary32 operations in the order
 // written (no contraction, correctly rounded sqrt and divide on both sides), so the two return the same bits. A dot product is
 // (x x' + y y') + z z' (ray_math.h dot). Minima and maxima are compare / select pairs, never fminf / fmaxf: what a NaN does
 // is then written here and not left to a library.
@@ -11,6 +11,7 @@
 #pragma once
 
 #include "point_math.hpp"
+#include "../../include/mi_raylib.h"
 
 namespace mi {
 
@@ -146,5 +147,25 @@ MI_HD bool box_touches_prim(uint32_t kind, const float* f, f3 lo, f3 hi, bool* c
 
 // The sort key of an overlap record: geomID, then primID. Unique within a box.
 MI_HD uint64_t overlap_key(uint32_t geomID, uint32_t primID) { return ((uint64_t)geomID << 32) | primID; }
+
+// What a record of a touching primitive carries when its family reports containment.
+MI_HD uint32_t overlap_flags(bool contained) { return contained ? (uint32_t)MI_OVERLAP_CONTAINED : 0u; }
+
+// The boxes as a touch family (the shape every family supplies is described in touch_kernels.hpp).
+struct BoxShape {
+  using Item = mi_box;
+  using Record = mi_overlap;
+  struct Fields { f3 lo, hi; };
+  using Carried = Fields;
+  static constexpr int kAny = MI_BOX_ANY, kCount = MI_BOX_COUNT;
+  static constexpr size_t kAlign = 16;
+  static constexpr const char *kNoun = "boxes", *kKindBad = "unknown box kind", *kAlignBad = "boxes must be 16-byte aligned";
+  static MI_HD Fields fields(const mi_box& b) { return {mk(b.lo[0], b.lo[1], b.lo[2]), mk(b.hi[0], b.hi[1], b.hi[2])}; }
+  static MI_HD bool valid(const Fields& b) { return box_query_valid(b.lo, b.hi); }
+  static MI_HD const Carried& carry(const Fields& b) { return b; }
+  static MI_HD bool meets_bounds(f3 mn, f3 mx, const Carried& q) { return box_meets_bounds(mn, mx, q.lo, q.hi); }
+  static MI_HD bool touches_prim(uint32_t kind, const float* f, const Carried& q, bool* contained) { return box_touches_prim(kind, f, q.lo, q.hi, contained); }
+  static MI_HD uint32_t flags(bool contained) { return overlap_flags(contained); }
+};
 
 }  // namespace mi

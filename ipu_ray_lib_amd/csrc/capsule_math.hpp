@@ -1,7 +1,7 @@
 // capsule_math.hpp — the arithmetic of capsule queries (mi_capsule_query* / mi_capsule_offsets* / mi_capsule_fill*,
 // include/mi_raylib.h, where the contract is written): whether a caller's capsule - the segment [a, b] widened by a radius, the
 // volume a ball sweeps on a straight move - touches a node's box, a triangle, a sphere's shell or a disc. One definition,
-// compiled by hipcc for the kernels (capsule_kernels.hpp) and by g++ for the host twin (host/capsule_query_host.cpp): every
+// compiled by hipcc for the kernels (capsule_kernels.hpp) and by g++ for the host twin (host/touch_host.hpp over CapsuleShape): every
 // function is a sequence of compares, selects and single binary32 operations in the order written (no contraction, correctly
 // rounded divide and sqrt on both sides), so the two return the same bits. The closest point of a triangle, the squared
 // distance of two points and the primitives' bounds are point_math.hpp's and box_math.hpp's: nothing of them is repeated here.
@@ -196,5 +196,22 @@ MI_HD bool capsule_touches_prim(uint32_t kind, const float* f, const Capsule& q,
   *contained = sqrtf(dmin2) + rp <= q.radius;
   return true;
 }
+
+// The capsules as a touch family (touch_kernels.hpp).
+struct CapsuleShape {
+  using Item = mi_capsule;
+  using Record = mi_overlap;
+  struct Fields { f3 a, b; float radius; };
+  using Carried = Capsule;
+  static constexpr int kAny = MI_CAPSULE_ANY, kCount = MI_CAPSULE_COUNT;
+  static constexpr size_t kAlign = 16;
+  static constexpr const char *kNoun = "capsules", *kKindBad = "unknown capsule kind", *kAlignBad = "capsules must be 16-byte aligned";
+  static MI_HD Fields fields(const mi_capsule& c) { return {mk(c.a[0], c.a[1], c.a[2]), mk(c.b[0], c.b[1], c.b[2]), c.radius}; }
+  static MI_HD bool valid(const Fields& c) { return capsule_query_valid(c.a, c.b, c.radius); }
+  static MI_HD Carried carry(const Fields& c) { return capsule_make(c.a, c.b, c.radius); }
+  static MI_HD bool meets_bounds(f3 mn, f3 mx, const Carried& q) { return capsule_meets_bounds(mn, mx, q); }
+  static MI_HD bool touches_prim(uint32_t kind, const float* f, const Carried& q, bool* contained) { return capsule_touches_prim(kind, f, q, contained); }
+  static MI_HD uint32_t flags(bool contained) { return overlap_flags(contained); }
+};
 
 }  // namespace mi

@@ -11,9 +11,12 @@
 //                        walk. A primitive's bounds are computed from the whole record (nine floats of a triangle, seven of a
 //                        disc), so there is no word whose load the bounds compare could spare.
 //   load_tri             a triangle's nine 4-byte loads.
-//   TriTouch             the two as the touch family takes them; a record's flags are 0.
+//   TriTouch             the two as the touch kernels take them, on top of the family's shape (TriShape, contact_math.hpp: item,
+//                        record and the argument rules' words); a record's flags are 0. The walk stays written out here: through
+//                        touch_walk over TriShape the same arithmetic compiles to other code - operands of additions change
+//                        places - and the device code is held fixed.
 // A lane carries the query's nine floats and its bounds; the axes of the separating-axis test are spelled out one by one
-// (contact_math.hpp). The host twin (host/tri_query_host.cpp) returns the same bytes and the same visit totals.
+// (contact_math.hpp). The host twin (host/touch_host.hpp over TriShape) returns the same bytes and the same visit totals.
 #pragma once
 
 #include "touch_kernels.hpp"
@@ -43,11 +46,9 @@ __device__ __forceinline__ void load_tri(const mi_tri* tris, uint32_t idx, f3& q
   q2 = mk(p[6], p[7], p[8]);
 }
 
-struct TriTouch {
-  using Item = mi_tri;
-  using Record = mi_contact;
+struct TriTouch : TriShape {
   struct Loaded { f3 q0, q1, q2; };
-  static constexpr const char *kQuery = "mi_tri_query", *kOffsets = "mi_tri_offsets", *kFill = "mi_tri_fill", *kNoun = "triangles";
+  static constexpr const char *kQuery = "mi_tri_query", *kOffsets = "mi_tri_offsets", *kFill = "mi_tri_fill";
   static __device__ __forceinline__ Loaded load(const mi_tri* tris, uint32_t idx) {
     Loaded t;
     load_tri(tris, idx, t.q0, t.q1, t.q2);

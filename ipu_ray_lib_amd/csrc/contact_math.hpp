@@ -1,6 +1,6 @@
 // contact_math.hpp — the arithmetic of triangle queries (mi_tri_query* / mi_tri_offsets* / mi_tri_fill*, include/mi_raylib.h, where
 // the contract is written): whether a caller's triangle (q0, q1, q2) touches a scene triangle, a sphere's shell or a disc. One
-// definition, compiled by hipcc for the kernels (contact_kernels.hpp) and by g++ for the host twin (host/tri_query_host.cpp):
+// definition, compiled by hipcc for the kernels (contact_kernels.hpp) and by g++ for the host twin (host/touch_host.hpp over TriShape):
 // compares, selects and single binary32 operations in the order written (no contraction, correctly rounded sqrt and divide on both
 // sides), so the two return the same bits. dot and cross are ray_math.h's; minima and maxima are sel_min / sel_max (box_math.hpp).
 //
@@ -102,5 +102,30 @@ MI_HD bool tri_touches_prim(uint32_t kind, const float* f, f3 q0, f3 q1, f3 q2, 
   if (kind == 1u) return tri_touches_sphere(mk(f[0], f[1], f[2]), f[3], f[4], q0, q1, q2, qmn, qmx);
   return tri_touches_disc(mk(f[0], f[1], f[2]), mk(f[3], f[4], f[5]), f[6], q0, q1, q2, qmn, qmx);
 }
+
+// The triangles as a touch family (touch_kernels.hpp): the walk carries the vertices and their bounds, a contact
+// record has no flags, and a batch is a float32 [n, 3, 3] array - 4-byte aligned.
+struct TriShape {
+  using Item = mi_tri;
+  using Record = mi_contact;
+  struct Fields { f3 q0, q1, q2; };
+  struct Carried { f3 q0, q1, q2, qmn, qmx; };
+  static constexpr int kAny = MI_TRI_ANY, kCount = MI_TRI_COUNT;
+  static constexpr size_t kAlign = 4;
+  static constexpr const char *kNoun = "triangles", *kKindBad = "unknown triangle kind", *kAlignBad = "triangles must be 4-byte aligned";
+  static MI_HD Fields fields(const mi_tri& t) { return {mk(t.a[0], t.a[1], t.a[2]), mk(t.b[0], t.b[1], t.b[2]), mk(t.c[0], t.c[1], t.c[2])}; }
+  static MI_HD bool valid(const Fields& t) { return tri_query_valid(t.q0, t.q1, t.q2); }
+  static MI_HD Carried carry(const Fields& t) {
+    Carried q = {t.q0, t.q1, t.q2, {}, {}};
+    tri_query_bounds(q.q0, q.q1, q.q2, q.qmn, q.qmx);
+    return q;
+  }
+  static MI_HD bool meets_bounds(f3 mn, f3 mx, const Carried& q) { return box_meets_bounds(mn, mx, q.qmn, q.qmx); }
+  static MI_HD bool touches_prim(uint32_t kind, const float* f, const Carried& q, bool* contained) {
+    *contained = false;
+    return tri_touches_prim(kind, f, q.q0, q.q1, q.q2, q.qmn, q.qmx);
+  }
+  static MI_HD uint32_t flags(bool) { return 0u; }
+};
 
 }  // namespace mi

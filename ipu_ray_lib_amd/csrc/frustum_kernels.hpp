@@ -5,17 +5,16 @@
 // (touch_kernels.hpp: touch_query_kernel, touch_count_kernel, touch_fill_kernel over FrustumTouch); what is the frusta's own is
 // here:
 //
-//   frustum_walk         walk_preorder (bvh_walk.hpp) with frustum_meets_bounds (frustum_math.hpp) at the nodes - per plane the
-//                        corner of the box farthest along the normal, nothing else: the region has no finite world bounds - and
+//   FrustumShape         (frustum_math.hpp) what touch_walk runs: frustum_meets_bounds at the nodes - per plane the corner of the
+//                        box farthest along the normal, nothing else: the region has no finite world bounds - and
 //                        frustum_touches_prim at a reached leaf: the same bounds test on the primitive's own bounds, then the
-//                        test of its kind. accept(leaf index, geomID, contained) is called for each touching primitive;
-//                        returning true ends the walk.
+//                        test of its kind; a record's flags are MI_OVERLAP_CONTAINED or 0.
 //   load_frustum         a frustum's six 16-byte loads.
-//   FrustumTouch         the two as the touch family takes them; a record's flags are MI_OVERLAP_CONTAINED or 0.
+//   FrustumTouch         the shape, the loads and the entries' names, as the touch kernels take them.
 // A lane carries the struct Frustum across the walk - six planes, 24 floats -, all in named registers: nothing is indexed, no
 // per-lane array, no LDS, no scratch. The node test is written with |, not ||: its result selects between nd.hit and nd.link, and
 // a short-circuit would have the compiler branch around that select (DESIGN.md §32 records the trap for near_walk). The host twin
-// (host/frustum_query_host.cpp) returns the same bytes and the same visit totals.
+// (host/touch_host.hpp over the same FrustumShape) returns the same bytes and the same visit totals.
 #pragma once
 
 #include "touch_kernels.hpp"
@@ -24,16 +23,6 @@
 namespace mi {
 
 static_assert(sizeof(mi_frustum) == 96, "mi_frustum must stay 96 bytes (six 16-byte loads)");
-
-template <bool STATS, class Accept>
-__device__ __forceinline__ void frustum_walk(const DeviceScene& sc, const Frustum& q, CastStats& cs, const Accept& accept) {
-  walk_preorder<STATS>(sc, frustum_query_valid(q), cs,
-    [&](const GNode& nd) { return frustum_meets_bounds(mk(nd.minx, nd.miny, nd.minz), mk(nd.maxx, nd.maxy, nd.maxz), q); },
-    [&](uint32_t at, uint32_t type, const float (&f)[9]) {
-      bool contained;
-      return frustum_touches_prim(type & 0xFFFFu, f, q, &contained) && accept(at, type >> 16, contained);
-    });
-}
 
 // mi_frustum: six planes nx, ny, nz, d - six 16-byte loads
 __device__ __forceinline__ FPlane frustum_plane_of(float4 v) {
@@ -55,19 +44,12 @@ __device__ __forceinline__ void load_frustum(const mi_frustum* frusta, uint32_t 
   q.p5 = frustum_plane_of(v5);
 }
 
-struct FrustumTouch {
-  using Item = mi_frustum;
-  using Record = mi_overlap;
-  using Loaded = Frustum;
-  static constexpr const char *kQuery = "mi_frustum_query", *kOffsets = "mi_frustum_offsets", *kFill = "mi_frustum_fill", *kNoun = "frusta";
-  static __device__ __forceinline__ Loaded load(const mi_frustum* frusta, uint32_t idx) {
-    Loaded q;
+struct FrustumTouch : SharedWalk<FrustumShape> {
+  static constexpr const char *kQuery = "mi_frustum_query", *kOffsets = "mi_frustum_offsets", *kFill = "mi_frustum_fill";
+  static __device__ __forceinline__ Fields load(const mi_frustum* frusta, uint32_t idx) {
+    Fields q;
     load_frustum(frusta, idx, q);
     return q;
-  }
-  template <bool STATS, class Accept>
-  static __device__ __forceinline__ void walk(const DeviceScene& sc, const Loaded& q, CastStats& cs, const Accept& accept) {
-    frustum_walk<STATS>(sc, q, cs, [&](uint32_t at, uint32_t geomID, bool contained) { return accept(at, geomID, contained ? (uint32_t)MI_OVERLAP_CONTAINED : 0u); });
   }
 };
 

@@ -2,7 +2,7 @@
 // include/mi_raylib.h, where the contract is written): whether the region that six caller-supplied planes leave - a camera's view
 // volume, a screen tile's sub-frustum, a half-space, a slab - touches a node's box, a triangle, a sphere or a disc. One
 // definition, compiled by hipcc for the kernels (frustum_kernels.hpp) and by g++ for the host twin
-// (host/frustum_query_host.cpp): every function is a sequence of compares, selects and single binary32 operations in the order
+// (host/touch_host.hpp over FrustumShape): every function is a sequence of compares, selects and single binary32 operations in the order
 // written (no contraction, correctly rounded divide and sqrt on both sides), so the two return the same bits. The primitives'
 // bounds are box_math.hpp's: nothing of them is repeated here.
 //
@@ -197,5 +197,25 @@ MI_HD bool frustum_touches_prim(uint32_t kind, const float* f, const Frustum& q,
   if (!frustum_meets_bounds(mn, mx, q)) return false;
   return frustum_touches_ball(q, c, f[6], contained);
 }
+
+// The frusta as a touch family (touch_kernels.hpp): the six planes are what the walk carries, as given.
+struct FrustumShape {
+  using Item = mi_frustum;
+  using Record = mi_overlap;
+  using Fields = Frustum;
+  using Carried = Frustum;
+  static constexpr int kAny = MI_FRUSTUM_ANY, kCount = MI_FRUSTUM_COUNT;
+  static constexpr size_t kAlign = 16;
+  static constexpr const char *kNoun = "frusta", *kKindBad = "unknown frustum kind", *kAlignBad = "frusta must be 16-byte aligned";
+  static MI_HD FPlane plane(const float p[4]) { return {p[0], p[1], p[2], p[3]}; }
+  static MI_HD Fields fields(const mi_frustum& f) {
+    return {plane(f.planes[0]), plane(f.planes[1]), plane(f.planes[2]), plane(f.planes[3]), plane(f.planes[4]), plane(f.planes[5])};
+  }
+  static MI_HD bool valid(const Fields& q) { return frustum_query_valid(q); }
+  static MI_HD const Carried& carry(const Fields& q) { return q; }
+  static MI_HD bool meets_bounds(f3 mn, f3 mx, const Carried& q) { return frustum_meets_bounds(mn, mx, q); }
+  static MI_HD bool touches_prim(uint32_t kind, const float* f, const Carried& q, bool* contained) { return frustum_touches_prim(kind, f, q, contained); }
+  static MI_HD uint32_t flags(bool contained) { return overlap_flags(contained); }
+};
 
 }  // namespace mi

@@ -12,6 +12,11 @@
 #include "../ray_shard.hpp"
 #include "../bvh_cost_host.hpp"
 #include "../canon_prims.hpp"
+#include "touch_host.hpp"
+#include "../contact_math.hpp"
+#include "../obox_math.hpp"
+#include "../capsule_math.hpp"
+#include "../frustum_math.hpp"
 
 using namespace mi;
 using namespace mi::host;
@@ -28,6 +33,37 @@ int guarded(F&& f) {
   try { f(); g_err.clear(); return MI_OK; }
   catch (const std::invalid_argument& e) { g_err = e.what(); return MI_ERR_INVALID_ARG; }
   catch (const std::exception& e) { g_err = e.what(); return MI_ERR_IO; }
+}
+
+// The entries of a touch family's twins (touch_host.hpp), one body each; S: the family's shape, fn: the C entry's name.
+bool twinArgsBad(const char* fn, const void* desc, const char* kindBad, bool nullBuffer) {
+  const char* why = !desc ? "null scene description" : kindBad ? kindBad : nullBuffer ? "null buffer" : nullptr;
+  if (why) g_err = std::string(fn) + ": " + why;
+  return why != nullptr;
+}
+template <class S>
+int touchQueryTwin(const char* fn, const mi_scene_desc* desc, int kind, const typename S::Item* items, void* out, size_t n, uint64_t* visits) {
+  if (twinArgsBad(fn, desc, kind != S::kAny && kind != S::kCount ? S::kKindBad : nullptr, n && (!items || !out))) return MI_ERR_INVALID_ARG;
+  return guarded([&] { touchQueryHost<S>(*desc, fn, kind, items, out, n, visits); });
+}
+template <class S>
+int touchOffsetsTwin(const char* fn, const mi_scene_desc* desc, const typename S::Item* items, uint64_t* offsets, size_t n, uint64_t* visits) {
+  if (twinArgsBad(fn, desc, nullptr, n && (!items || !offsets))) return MI_ERR_INVALID_ARG;
+  return guarded([&] { touchOffsetsHost<S>(*desc, fn, items, offsets, n, visits); });
+}
+template <class S>
+int touchFillTwin(const char* fn, const mi_scene_desc* desc, const typename S::Item* items, const uint64_t* offsets, typename S::Record* hits, size_t capacity, size_t n,
+                  uint64_t* visits) {
+  if (twinArgsBad(fn, desc, nullptr, n && (!items || !offsets || !hits))) return MI_ERR_INVALID_ARG;
+  return guarded([&] { touchFillHost<S>(*desc, fn, items, offsets, hits, capacity, n, visits); });
+}
+// (no error text: 0 for a null argument, as for an item that is not walked)
+template <class S>
+int touchMeetsBoundsTwin(const typename S::Item* item, const float mn[3], const float mx[3]) {
+  if (!item || !mn || !mx) return 0;
+  typename S::Item q;
+  memcpy(&q, item, sizeof q);
+  return touchMeetsBoundsHost<S>(q, mn, mx) ? 1 : 0;
 }
 }  // namespace
 
@@ -183,65 +219,28 @@ int mi_near_fill_host(const mi_scene_desc* desc, const mi_point* points, const u
   return guarded([&] { nearFillHost(*desc, points, offsets, hits, capacity, n, visits); });
 }
 
-// Box queries: the host twins of mi_box_query* / mi_box_offsets* / mi_box_fill* (box_query_host.cpp)
-int mi_box_query_host(const mi_scene_desc* desc, int kind, const mi_box* boxes, void* out, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_box_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (kind != MI_BOX_ANY && kind != MI_BOX_COUNT) { g_err = "mi_box_query_host: unknown box kind"; return MI_ERR_INVALID_ARG; }
-  if (n && (!boxes || !out)) { g_err = "mi_box_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { boxQueryHost(*desc, kind, boxes, out, n, visits); });
-}
-
-int mi_box_offsets_host(const mi_scene_desc* desc, const mi_box* boxes, uint64_t* offsets, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_box_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!boxes || !offsets)) { g_err = "mi_box_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { boxOffsetsHost(*desc, boxes, offsets, n, visits); });
-}
-
-int mi_box_fill_host(const mi_scene_desc* desc, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_box_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!boxes || !offsets || !hits)) { g_err = "mi_box_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { boxFillHost(*desc, boxes, offsets, hits, capacity, n, visits); });
-}
-
-// Triangle queries: the host twins of mi_tri_query* / mi_tri_offsets* / mi_tri_fill* (tri_query_host.cpp)
-int mi_tri_query_host(const mi_scene_desc* desc, int kind, const mi_tri* tris, void* out, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_tri_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (kind != MI_TRI_ANY && kind != MI_TRI_COUNT) { g_err = "mi_tri_query_host: unknown triangle kind"; return MI_ERR_INVALID_ARG; }
-  if (n && (!tris || !out)) { g_err = "mi_tri_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { triQueryHost(*desc, kind, tris, out, n, visits); });
-}
-
-int mi_tri_offsets_host(const mi_scene_desc* desc, const mi_tri* tris, uint64_t* offsets, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_tri_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!tris || !offsets)) { g_err = "mi_tri_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { triOffsetsHost(*desc, tris, offsets, n, visits); });
-}
-
-int mi_tri_fill_host(const mi_scene_desc* desc, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_tri_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!tris || !offsets || !hits)) { g_err = "mi_tri_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { triFillHost(*desc, tris, offsets, hits, capacity, n, visits); });
-}
-
-// Oriented-box queries: the host twins of mi_obox_query* / mi_obox_offsets* / mi_obox_fill* (obox_query_host.cpp)
-int mi_obox_query_host(const mi_scene_desc* desc, int kind, const mi_obox* oboxes, void* out, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_obox_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (kind != MI_OBOX_ANY && kind != MI_OBOX_COUNT) { g_err = "mi_obox_query_host: unknown oriented-box kind"; return MI_ERR_INVALID_ARG; }
-  if (n && (!oboxes || !out)) { g_err = "mi_obox_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { oboxQueryHost(*desc, kind, oboxes, out, n, visits); });
-}
-
-int mi_obox_offsets_host(const mi_scene_desc* desc, const mi_obox* oboxes, uint64_t* offsets, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_obox_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!oboxes || !offsets)) { g_err = "mi_obox_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { oboxOffsetsHost(*desc, oboxes, offsets, n, visits); });
-}
-
-int mi_obox_fill_host(const mi_scene_desc* desc, const mi_obox* oboxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_obox_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!oboxes || !offsets || !hits)) { g_err = "mi_obox_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { oboxFillHost(*desc, oboxes, offsets, hits, capacity, n, visits); });
-}
+// Touch queries: the host twins of mi_X_query* / mi_X_offsets* / mi_X_fill* and, where the family has one, the node test alone.
+// The bodies are the templates above; a family is its shape.
+#define MI_TOUCH_TWINS(X, S)                                                                                                                            \
+  int mi_##X##_query_host(const mi_scene_desc* desc, int kind, const S::Item* items, void* out, size_t n, uint64_t visits[2]) {                         \
+    return touchQueryTwin<S>("mi_" #X "_query_host", desc, kind, items, out, n, visits);                                                                \
+  }                                                                                                                                                     \
+  int mi_##X##_offsets_host(const mi_scene_desc* desc, const S::Item* items, uint64_t* offsets, size_t n, uint64_t visits[2]) {                         \
+    return touchOffsetsTwin<S>("mi_" #X "_offsets_host", desc, items, offsets, n, visits);                                                              \
+  }                                                                                                                                                     \
+  int mi_##X##_fill_host(const mi_scene_desc* desc, const S::Item* items, const uint64_t* offsets, S::Record* hits, size_t capacity, size_t n,          \
+                         uint64_t visits[2]) {                                                                                                          \
+    return touchFillTwin<S>("mi_" #X "_fill_host", desc, items, offsets, hits, capacity, n, visits);                                                    \
+  }
+MI_TOUCH_TWINS(box, BoxShape)
+MI_TOUCH_TWINS(tri, TriShape)
+MI_TOUCH_TWINS(obox, OBoxShape)
+MI_TOUCH_TWINS(capsule, CapsuleShape)
+MI_TOUCH_TWINS(frustum, FrustumShape)
+#undef MI_TOUCH_TWINS
+int mi_obox_meets_bounds_host(const mi_obox* obox, const float mn[3], const float mx[3]) { return touchMeetsBoundsTwin<OBoxShape>(obox, mn, mx); }
+int mi_capsule_meets_bounds_host(const mi_capsule* capsule, const float mn[3], const float mx[3]) { return touchMeetsBoundsTwin<CapsuleShape>(capsule, mn, mx); }
+int mi_frustum_meets_bounds_host(const mi_frustum* frustum, const float mn[3], const float mx[3]) { return touchMeetsBoundsTwin<FrustumShape>(frustum, mn, mx); }
 
 // Rigid poses: the host twin of the pose pass of mi_scene_set_poses* (pose_host.cpp)
 int mi_pose_geometry_host(const mi_scene_desc* rest, const mi_pose* poses, uint32_t num_geometry, mi_vec3* verts_out, mi_vec3* normals_out,
@@ -249,67 +248,6 @@ int mi_pose_geometry_host(const mi_scene_desc* rest, const mi_pose* poses, uint3
   if (!rest) { g_err = "mi_pose_geometry_host: null scene description"; return MI_ERR_INVALID_ARG; }
   if (num_geometry && !poses) { g_err = "mi_pose_geometry_host: null poses"; return MI_ERR_INVALID_ARG; }
   return guarded([&] { poseGeometryHost(*rest, poses, num_geometry, verts_out, normals_out, spheres_out, discs_out); });
-}
-
-int mi_obox_meets_bounds_host(const mi_obox* obox, const float mn[3], const float mx[3]) {
-  if (!obox || !mn || !mx) return 0;
-  mi_obox q;
-  memcpy(&q, obox, sizeof q);
-  return oboxMeetsBoundsHost(q, mn, mx) ? 1 : 0;
-}
-
-// Capsule queries: the host twins of mi_capsule_query* / mi_capsule_offsets* / mi_capsule_fill* (capsule_query_host.cpp)
-int mi_capsule_query_host(const mi_scene_desc* desc, int kind, const mi_capsule* capsules, void* out, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_capsule_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (kind != MI_CAPSULE_ANY && kind != MI_CAPSULE_COUNT) { g_err = "mi_capsule_query_host: unknown capsule kind"; return MI_ERR_INVALID_ARG; }
-  if (n && (!capsules || !out)) { g_err = "mi_capsule_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { capsuleQueryHost(*desc, kind, capsules, out, n, visits); });
-}
-
-int mi_capsule_offsets_host(const mi_scene_desc* desc, const mi_capsule* capsules, uint64_t* offsets, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_capsule_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!capsules || !offsets)) { g_err = "mi_capsule_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { capsuleOffsetsHost(*desc, capsules, offsets, n, visits); });
-}
-
-int mi_capsule_fill_host(const mi_scene_desc* desc, const mi_capsule* capsules, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_capsule_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!capsules || !offsets || !hits)) { g_err = "mi_capsule_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { capsuleFillHost(*desc, capsules, offsets, hits, capacity, n, visits); });
-}
-
-int mi_capsule_meets_bounds_host(const mi_capsule* capsule, const float mn[3], const float mx[3]) {
-  if (!capsule || !mn || !mx) return 0;
-  mi_capsule q;
-  memcpy(&q, capsule, sizeof q);
-  return capsuleMeetsBoundsHost(q, mn, mx) ? 1 : 0;
-}
-
-// Frustum queries: the host twins of mi_frustum_query* / mi_frustum_offsets* / mi_frustum_fill* (frustum_query_host.cpp)
-int mi_frustum_query_host(const mi_scene_desc* desc, int kind, const mi_frustum* frusta, void* out, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_frustum_query_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (kind != MI_FRUSTUM_ANY && kind != MI_FRUSTUM_COUNT) { g_err = "mi_frustum_query_host: unknown frustum kind"; return MI_ERR_INVALID_ARG; }
-  if (n && (!frusta || !out)) { g_err = "mi_frustum_query_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { frustumQueryHost(*desc, kind, frusta, out, n, visits); });
-}
-
-int mi_frustum_offsets_host(const mi_scene_desc* desc, const mi_frustum* frusta, uint64_t* offsets, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_frustum_offsets_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!frusta || !offsets)) { g_err = "mi_frustum_offsets_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { frustumOffsetsHost(*desc, frusta, offsets, n, visits); });
-}
-
-int mi_frustum_fill_host(const mi_scene_desc* desc, const mi_frustum* frusta, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t visits[2]) {
-  if (!desc) { g_err = "mi_frustum_fill_host: null scene description"; return MI_ERR_INVALID_ARG; }
-  if (n && (!frusta || !offsets || !hits)) { g_err = "mi_frustum_fill_host: null buffer"; return MI_ERR_INVALID_ARG; }
-  return guarded([&] { frustumFillHost(*desc, frusta, offsets, hits, capacity, n, visits); });
-}
-
-int mi_frustum_meets_bounds_host(const mi_frustum* frustum, const float mn[3], const float mx[3]) {
-  if (!frustum || !mn || !mx) return 0;
-  mi_frustum q;
-  memcpy(&q, frustum, sizeof q);
-  return frustumMeetsBoundsHost(q, mn, mx) ? 1 : 0;
 }
 
 // The canonical primitive table of desc's arrays: the host twin of canon_prim_kernel (canon_kernels.hpp, mi_scene_set_geometry*) -

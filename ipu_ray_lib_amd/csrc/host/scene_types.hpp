@@ -123,29 +123,7 @@ void pointQueryHost(const mi_scene_desc& desc, int kind, const mi_point* points,
 // point_query_host.cpp: the host twins of mi_near_offsets / mi_near_fill (the same visits)
 void nearOffsetsHost(const mi_scene_desc& desc, const mi_point* points, uint64_t* offsets, size_t n, uint64_t* visits);
 void nearFillHost(const mi_scene_desc& desc, const mi_point* points, const uint64_t* offsets, mi_neighbour* hits, size_t capacity, size_t n, uint64_t* visits);
-// box_query_host.cpp: the host twins of mi_box_query / mi_box_offsets / mi_box_fill (the same visits)
-void boxQueryHost(const mi_scene_desc& desc, int kind, const mi_box* boxes, void* out, size_t n, uint64_t* visits);
-void boxOffsetsHost(const mi_scene_desc& desc, const mi_box* boxes, uint64_t* offsets, size_t n, uint64_t* visits);
-void boxFillHost(const mi_scene_desc& desc, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t* visits);
-// tri_query_host.cpp: the host twins of mi_tri_query / mi_tri_offsets / mi_tri_fill (the same visits)
-void triQueryHost(const mi_scene_desc& desc, int kind, const mi_tri* tris, void* out, size_t n, uint64_t* visits);
-void triOffsetsHost(const mi_scene_desc& desc, const mi_tri* tris, uint64_t* offsets, size_t n, uint64_t* visits);
-void triFillHost(const mi_scene_desc& desc, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity, size_t n, uint64_t* visits);
-// obox_query_host.cpp: the host twins of mi_obox_query / mi_obox_offsets / mi_obox_fill (the same visits), and the bounds test alone
-void oboxQueryHost(const mi_scene_desc& desc, int kind, const mi_obox* oboxes, void* out, size_t n, uint64_t* visits);
-void oboxOffsetsHost(const mi_scene_desc& desc, const mi_obox* oboxes, uint64_t* offsets, size_t n, uint64_t* visits);
-void oboxFillHost(const mi_scene_desc& desc, const mi_obox* oboxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t* visits);
-bool oboxMeetsBoundsHost(const mi_obox& obox, const float mn[3], const float mx[3]);
-// capsule_query_host.cpp: the host twins of mi_capsule_query / mi_capsule_offsets / mi_capsule_fill (the same visits), and the bounds test alone
-void capsuleQueryHost(const mi_scene_desc& desc, int kind, const mi_capsule* capsules, void* out, size_t n, uint64_t* visits);
-void capsuleOffsetsHost(const mi_scene_desc& desc, const mi_capsule* capsules, uint64_t* offsets, size_t n, uint64_t* visits);
-void capsuleFillHost(const mi_scene_desc& desc, const mi_capsule* capsules, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t* visits);
-bool capsuleMeetsBoundsHost(const mi_capsule& capsule, const float mn[3], const float mx[3]);
-// frustum_query_host.cpp: the host twins of mi_frustum_query / mi_frustum_offsets / mi_frustum_fill (the same visits), and the bounds test alone
-void frustumQueryHost(const mi_scene_desc& desc, int kind, const mi_frustum* frusta, void* out, size_t n, uint64_t* visits);
-void frustumOffsetsHost(const mi_scene_desc& desc, const mi_frustum* frusta, uint64_t* offsets, size_t n, uint64_t* visits);
-void frustumFillHost(const mi_scene_desc& desc, const mi_frustum* frusta, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n, uint64_t* visits);
-bool frustumMeetsBoundsHost(const mi_frustum& frustum, const float mn[3], const float mx[3]);
+// (the touch families' twins are templates over the family's shape: touch_host.hpp, instantiated by scene_api.cpp)
 // pose_host.cpp: the host twin of the pose pass of mi_scene_set_poses* (normalsOut may be null for a scene without normals)
 void poseGeometryHost(const mi_scene_desc& rest, const mi_pose* poses, uint32_t numGeometry, mi_vec3* vertsOut, mi_vec3* normalsOut, mi_sphere* spheresOut,
                       mi_disc* discsOut);

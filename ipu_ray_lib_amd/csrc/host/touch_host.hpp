@@ -1,11 +1,8 @@
-// touch_host.hpp — the host twins of the touch family's kernels (touch_kernels.hpp), written once: query, offsets and fill over
-// caller buffers that need not be aligned. A family describes itself as on the device, by a struct Q:
-//
-//   Q::Item, Q::Record                          mi_box / mi_overlap, mi_tri / mi_contact, mi_obox / mi_overlap, mi_capsule / mi_overlap, mi_frustum / mi_overlap
-//   Q::kQuery, Q::kOffsets, Q::kFill            the entries' names, for the message of what walkTable refuses
-//   Q::walk(nodes, item, boxTests, primTests, accept)
-//                                               the item's walk over walkHost (walk_host.hpp): accept(node index, flags) for each
-//                                               touching primitive, `flags` what a record of it carries; true ends the walk
+// touch_host.hpp — the host twins of the touch family's kernels (touch_kernels.hpp), written once: walk, query, offsets, fill and
+// the bounds test alone, over caller buffers that need not be aligned. A family is the shape S its kernels walk with (BoxShape in
+// box_math.hpp is the plainest; touch_kernels.hpp lists what a shape holds), so the twin and the device run one spelling of
+// `valid`, `meets_bounds`, `touches_prim` and of how `contained` becomes a record's flags. fn: the entry's name, for the message
+// of what walkTable refuses.
 //
 // The fill is "the len smallest keys, ascending" by a sort - keys are unique within an item, so the device's heap leaves the same
 // bytes. visits: {box tests, primitive tests}, may be null.
@@ -20,41 +17,55 @@
 
 namespace mi::host {
 
-// kind 0 (MI_BOX_ANY, MI_TRI_ANY, MI_OBOX_ANY, MI_CAPSULE_ANY, MI_FRUSTUM_ANY): n bytes, the walk stops at the first accept; kind 1: n uint32_t counts
-template <class Q>
-void touchQueryHost(const mi_scene_desc& d, int kind, const typename Q::Item* items, void* out, size_t n, uint64_t* visits) {
-  static_assert((int)MI_BOX_ANY == (int)MI_TRI_ANY, "any touch family's kind");
-  const std::vector<WalkNode> nodes = walkTable(d, Q::kQuery);
+// touch_walk of touch_kernels.hpp over walkHost: a node is entered when S::meets_bounds of its box holds; accept(node index, flags)
+// for each touching primitive of a reached leaf, true ends the walk.
+template <class S, class Accept>
+void touchWalkHost(const std::vector<WalkNode>& nodes, const typename S::Item& item, uint64_t& boxTests, uint64_t& primTests, const Accept& accept) {
+  const typename S::Fields fields = S::fields(item);
+  const auto& q = S::carry(fields);
+  walkHost(nodes, S::valid(fields), boxTests, primTests,
+    [&](const WalkNode& w) { return S::meets_bounds(mk(w.minx, w.miny, w.minz), mk(w.maxx, w.maxy, w.maxz), q); },
+    [&](uint32_t i, const WalkNode& w) {
+      bool contained;
+      return S::touches_prim(w.kind, w.f, q, &contained) && accept(i, S::flags(contained));
+    });
+}
+
+// kind S::kAny: n bytes, the walk stops at the first accept; S::kCount: n uint32_t counts
+template <class S>
+void touchQueryHost(const mi_scene_desc& d, const char* fn, int kind, const typename S::Item* items, void* out, size_t n, uint64_t* visits) {
+  const std::vector<WalkNode> nodes = walkTable(d, fn);
   uint64_t boxTests = 0, primTests = 0;
   for (size_t k = 0; k < n; ++k) {
-    typename Q::Item item;
+    typename S::Item item;
     memcpy(&item, items + k, sizeof item);
     uint32_t count = 0;
-    Q::walk(nodes, item, boxTests, primTests, [&](uint32_t, uint32_t) { ++count; return kind == MI_BOX_ANY; });
-    if (kind == MI_BOX_ANY) static_cast<uint8_t*>(out)[k] = count ? 1u : 0u;
+    touchWalkHost<S>(nodes, item, boxTests, primTests, [&](uint32_t, uint32_t) { ++count; return kind == S::kAny; });
+    if (kind == S::kAny) static_cast<uint8_t*>(out)[k] = count ? 1u : 0u;
     else memcpy(static_cast<char*>(out) + k * sizeof count, &count, sizeof count);
   }
   if (visits) { visits[0] = boxTests; visits[1] = primTests; }
 }
 
-template <class Q>
-void touchOffsetsHost(const mi_scene_desc& d, const typename Q::Item* items, uint64_t* offsets, size_t n, uint64_t* visits) {
-  const std::vector<WalkNode> nodes = walkTable(d, Q::kOffsets);
+template <class S>
+void touchOffsetsHost(const mi_scene_desc& d, const char* fn, const typename S::Item* items, uint64_t* offsets, size_t n, uint64_t* visits) {
+  const std::vector<WalkNode> nodes = walkTable(d, fn);
   uint64_t boxTests = 0, primTests = 0, total = 0;
   if (n) memcpy(offsets, &total, sizeof total);
   for (size_t k = 0; k < n; ++k) {
-    typename Q::Item item;
+    typename S::Item item;
     memcpy(&item, items + k, sizeof item);
-    Q::walk(nodes, item, boxTests, primTests, [&](uint32_t, uint32_t) { ++total; return false; });
+    touchWalkHost<S>(nodes, item, boxTests, primTests, [&](uint32_t, uint32_t) { ++total; return false; });
     memcpy(reinterpret_cast<char*>(offsets) + (k + 1) * sizeof total, &total, sizeof total);
   }
   if (visits) { visits[0] = boxTests; visits[1] = primTests; }
 }
 
-template <class Q>
-void touchFillHost(const mi_scene_desc& d, const typename Q::Item* items, const uint64_t* offsets, typename Q::Record* hits, size_t capacity, size_t n, uint64_t* visits) {
-  using Rec = typename Q::Record;
-  const std::vector<WalkNode> nodes = walkTable(d, Q::kFill);
+template <class S>
+void touchFillHost(const mi_scene_desc& d, const char* fn, const typename S::Item* items, const uint64_t* offsets, typename S::Record* hits, size_t capacity, size_t n,
+                   uint64_t* visits) {
+  using Rec = typename S::Record;
+  const std::vector<WalkNode> nodes = walkTable(d, fn);
   uint64_t boxTests = 0, primTests = 0;
   std::vector<Rec> found;      // every touching primitive of the item; its head is copied out once sorted
   for (size_t k = 0; k < n; ++k) {
@@ -63,10 +74,10 @@ void touchFillHost(const mi_scene_desc& d, const typename Q::Item* items, const 
     memcpy(&last, reinterpret_cast<const char*>(offsets) + (k + 1) * sizeof last, sizeof last);
     const uint64_t len = segment_len(first, last, capacity);
     if (!len) continue;
-    typename Q::Item item;
+    typename S::Item item;
     memcpy(&item, items + k, sizeof item);
     found.clear();
-    Q::walk(nodes, item, boxTests, primTests, [&](uint32_t at, uint32_t flags) {
+    touchWalkHost<S>(nodes, item, boxTests, primTests, [&](uint32_t at, uint32_t flags) {
       found.push_back(Rec{nodes[at].primID, nodes[at].geomID, (uint16_t)flags, (uint32_t)k, 0u});
       return false;
     });
@@ -76,6 +87,13 @@ void touchFillHost(const mi_scene_desc& d, const typename Q::Item* items, const 
     memcpy(reinterpret_cast<char*>(hits) + first * sizeof(Rec), found.data(), (size_t)len * sizeof(Rec));
   }
   if (visits) { visits[0] = boxTests; visits[1] = primTests; }
+}
+
+// The node test alone: whether a walk of `item` would enter the box [mn, mx]. An item that is not walked enters nothing.
+template <class S>
+bool touchMeetsBoundsHost(const typename S::Item& item, const float mn[3], const float mx[3]) {
+  const typename S::Fields fields = S::fields(item);
+  return S::valid(fields) && S::meets_bounds(mk(mn[0], mn[1], mn[2]), mk(mx[0], mx[1], mx[2]), S::carry(fields));
 }
 
 }  // namespace mi::host

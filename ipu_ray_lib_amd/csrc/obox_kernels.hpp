@@ -10,12 +10,15 @@
 //                        bounds, then the box family's test in the box's frame. accept(leaf index, geomID, contained) is called
 //                        for each touching primitive; returning true ends the walk.
 //   load_obox            an oriented box's three 16-byte loads.
-//   OBoxTouch            the two as the touch family takes them; a record's flags are MI_OVERLAP_CONTAINED or 0.
+//   OBoxTouch            the two as the touch kernels take them, on top of the family's shape (OBoxShape, obox_math.hpp: item, record
+//                        and the argument rules' words); a record's flags are MI_OVERLAP_CONTAINED or 0. The walk stays written out
+//                        here: through touch_walk over OBoxShape the same arithmetic compiles to other code - operands of
+//                        commutative instructions change places - and the device code is held fixed.
 // A lane carries the frame (9 floats), the centre and half extents (6) and the world bounds (6) across the walk, all in named
 // registers: nothing is indexed, no per-lane array, no LDS, no scratch. The node test is written with & and |, not && and ||: its
 // result selects between nd.hit and nd.link, and a short-circuit would have the compiler branch around that select (DESIGN.md
-// §32 records the trap for near_walk). The host twin (host/obox_query_host.cpp) returns the same bytes and the same visit totals
-// (DESIGN.md §34).
+// §32 records the trap for near_walk). The host twin (host/touch_host.hpp over OBoxShape) returns the same bytes and the same visit
+// totals.
 #pragma once
 
 #include "touch_kernels.hpp"
@@ -45,11 +48,9 @@ __device__ __forceinline__ void load_obox(const mi_obox* oboxes, uint32_t idx, f
   quat = p[2];
 }
 
-struct OBoxTouch {
-  using Item = mi_obox;
-  using Record = mi_overlap;
+struct OBoxTouch : OBoxShape {
   struct Loaded { f3 c, h; float4 quat; };
-  static constexpr const char *kQuery = "mi_obox_query", *kOffsets = "mi_obox_offsets", *kFill = "mi_obox_fill", *kNoun = "oriented boxes";
+  static constexpr const char *kQuery = "mi_obox_query", *kOffsets = "mi_obox_offsets", *kFill = "mi_obox_fill";
   static __device__ __forceinline__ Loaded load(const mi_obox* oboxes, uint32_t idx) {
     Loaded b;
     load_obox(oboxes, idx, b.c, b.h, b.quat);
@@ -57,7 +58,7 @@ struct OBoxTouch {
   }
   template <bool STATS, class Accept>
   static __device__ __forceinline__ void walk(const DeviceScene& sc, const Loaded& b, CastStats& cs, const Accept& accept) {
-    obox_walk<STATS>(sc, b.c, b.h, b.quat, cs, [&](uint32_t at, uint32_t geomID, bool contained) { return accept(at, geomID, contained ? (uint32_t)MI_OVERLAP_CONTAINED : 0u); });
+    obox_walk<STATS>(sc, b.c, b.h, b.quat, cs, [&](uint32_t at, uint32_t geomID, bool contained) { return accept(at, geomID, flags(contained)); });
   }
 };
 

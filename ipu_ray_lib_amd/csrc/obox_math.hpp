@@ -1,7 +1,7 @@
 // obox_math.hpp — the arithmetic of oriented-box queries (mi_obox_query* / mi_obox_offsets* / mi_obox_fill*, include/mi_raylib.h,
 // where the contract is written): whether a caller's rotated box - centre, half extents, a quaternion that need not be unit -
 // touches a node's box, a triangle, a sphere's shell or a disc. One definition, compiled by hipcc for the kernels
-// (obox_kernels.hpp) and by g++ for the host twin (host/obox_query_host.cpp): every function is a sequence of compares, selects
+// (obox_kernels.hpp) and by g++ for the host twin (host/touch_host.hpp over OBoxShape): every function is a sequence of compares, selects
 // and single binary32 operations in the order written (no contraction, correctly rounded divide on both sides), so the two
 // return the same bits. The primitive tests are box_math.hpp's, called in the box's own frame: nothing of them is repeated here.
 //
@@ -114,5 +114,24 @@ MI_HD bool obox_touches_prim(uint32_t kind, const float* f, const OBox& q, bool*
   if (!obox_meets_bounds(mn, mx, q)) return false;
   return box_touches_disc(obox_local_dir(q, n), obox_local_point(q, c), f[6], lo, hi, contained);
 }
+
+// The oriented boxes as a touch family (touch_kernels.hpp).
+struct OBoxShape {
+  using Item = mi_obox;
+  using Record = mi_overlap;
+  struct Fields { f3 c, h; float x, y, z, w; };      // centre, half extents, the quaternion as given
+  using Carried = OBox;
+  static constexpr int kAny = MI_OBOX_ANY, kCount = MI_OBOX_COUNT;
+  static constexpr size_t kAlign = 16;
+  static constexpr const char *kNoun = "oriented boxes", *kKindBad = "unknown oriented-box kind", *kAlignBad = "oriented boxes must be 16-byte aligned";
+  static MI_HD Fields fields(const mi_obox& b) {
+    return {mk(b.centre[0], b.centre[1], b.centre[2]), mk(b.half[0], b.half[1], b.half[2]), b.quat[0], b.quat[1], b.quat[2], b.quat[3]};
+  }
+  static MI_HD bool valid(const Fields& b) { return obox_query_valid(b.c, b.h, b.x, b.y, b.z, b.w); }
+  static MI_HD Carried carry(const Fields& b) { return obox_make(b.c, b.h, b.x, b.y, b.z, b.w); }
+  static MI_HD bool meets_bounds(f3 mn, f3 mx, const Carried& q) { return obox_meets_bounds(mn, mx, q); }
+  static MI_HD bool touches_prim(uint32_t kind, const float* f, const Carried& q, bool* contained) { return obox_touches_prim(kind, f, q, contained); }
+  static MI_HD uint32_t flags(bool contained) { return overlap_flags(contained); }
+};
 
 }  // namespace mi

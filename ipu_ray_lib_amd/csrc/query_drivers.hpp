@@ -1,11 +1,10 @@
-// The host side of the eight query families - ray queries (mi_query*), point queries (mi_point_query*), crossing counts and
-// signs (mi_count_query*, mi_point_sign*), crossing lists (mi_list_*), neighbour lists (mi_near_*), box queries (mi_box_*),
-// triangle queries (mi_tri_*), oriented-box queries (mi_obox_*), capsule queries (mi_capsule_*) and frustum queries
-// (mi_frustum_*): one launch frame, one
-// build selection, one argument checker, one two-slot host pipeline, and the extern "C" entries on top of them. Included by
-// raylib.hip, in its translation unit, once mi_scene, LaunchSlot, guarded, HIP_CHECK and kMaxWorkItems are defined
-// (group_render.hpp is included the same way). A new family supplies a kernel header, a launcher body inside launchFrame, its
-// buffer rules for queryArgsBad, and its entries.
+// The host side of the query families - ray queries (mi_query*), point queries (mi_point_query*), crossing counts and signs
+// (mi_count_query*, mi_point_sign*), crossing lists (mi_list_*), neighbour lists (mi_near_*) and the touch families, which
+// TouchFamilies below lists: one launch frame, one build selection, one argument checker, one two-slot host pipeline, and the
+// extern "C" entries on top of them. Included by raylib.hip, in its translation unit, once mi_scene, LaunchSlot, guarded,
+// HIP_CHECK and kMaxWorkItems are defined (group_render.hpp is included the same way). A new family supplies a kernel header, a
+// launcher body inside launchFrame, its buffer rules for queryArgsBad, and its entries; a new touch family
+// supplies its Q, one name in TouchFamilies and one MI_TOUCH_ENTRIES line.
 #pragma once
 
 #include <initializer_list>
@@ -179,26 +178,29 @@ void launchNearFill(mi_scene& S, const mi_point* d_points, const uint64_t* d_off
   });
 }
 
-// Touch queries - the box queries (Q = BoxTouch, box_kernels.hpp), the triangle queries (Q = TriTouch, contact_kernels.hpp) and the
-// oriented-box queries (Q = OBoxTouch, obox_kernels.hpp), the capsule queries (Q = CapsuleTouch, capsule_kernels.hpp) and the frustum
-// queries (Q = FrustumTouch, frustum_kernels.hpp), whose entries mirror the box queries'; the entry's name and the items' noun
-// for what launchFrame refuses come from Q. full_stats picks the instrumented build; no other option applies.
-// mi_box_query_device / mi_tri_query_device / mi_obox_query_device / mi_capsule_query_device / mi_frustum_query_device: whether a
-// primitive touches each item (kind 0, MI_BOX_ANY = MI_TRI_ANY = MI_OBOX_ANY = MI_CAPSULE_ANY = MI_FRUSTUM_ANY: n bytes) or how many do
-// (kind 1, MI_*_COUNT: n uint32_t), one thread per item (touch_query_kernel).
-static_assert((int)MI_BOX_COUNT == (int)MI_TRI_COUNT && (int)MI_BOX_COUNT == (int)MI_OBOX_COUNT && (int)MI_BOX_COUNT == (int)MI_CAPSULE_COUNT &&
-              (int)MI_BOX_COUNT == (int)MI_FRUSTUM_COUNT,
-              "launchTouchQuery takes any touch family's kind");
+// The touch families, each by its Q (touch_kernels.hpp): the one list there is. What must hold of all of them is folded over it.
+template <class... Q>
+struct TouchList {
+  static constexpr bool oneKindNumbering = (((int)Q::kAny == (int)MI_BOX_ANY && (int)Q::kCount == (int)MI_BOX_COUNT) && ...);
+  static constexpr size_t itemBytes = std::max({sizeof(typename Q::Item)...});
+};
+using TouchFamilies = TouchList<BoxTouch, TriTouch, OBoxTouch, CapsuleTouch, FrustumTouch>;
+static_assert(TouchFamilies::oneKindNumbering, "every touch family numbers its kinds alike: ANY = 0, COUNT = 1");
+
+// Touch queries, Q a family of TouchFamilies; the entry's name and the items' noun for what launchFrame refuses come from Q.
+// full_stats picks the instrumented build; no other option applies.
+// mi_X_query_device: whether a primitive touches each item (Q::kAny: n bytes) or how many do (Q::kCount: n uint32_t), one thread
+// per item (touch_query_kernel).
 template <class Q>
 void launchTouchQuery(mi_scene& S, int kind, const typename Q::Item* d_items, void* d_out, size_t n, hipStream_t stream) {
   launchFrame(S, Q::kQuery, Q::kNoun, n, stream, [&](LaunchSlot&, const DeviceScene& dsv, dim3 grid, dim3 block, uint32_t cnt) {
-    withFlag(kind == MI_BOX_COUNT, [&](auto count) { pickBuild<false, false>(S.opt, [&](auto b) {
+    withFlag(kind == Q::kCount, [&](auto count) { pickBuild<false, false>(S.opt, [&](auto b) {
       hipLaunchKernelGGL((touch_query_kernel<Q, decltype(count)::value, decltype(b)::stats>), grid, block, 0, stream, dsv, d_items, d_out, cnt);
     }); });
   });
 }
 
-// Box and contact lists, step 1 (mi_box_offsets_device / mi_tri_offsets_device): d_incl[i] = the primitives touching items 0 .. i.
+// Touch lists, step 1 (mi_X_offsets_device): d_incl[i] = the primitives touching items 0 .. i.
 // touch_count_kernel writes the counts as 64 bits, scanOffsets sums them.
 template <class Q>
 void launchTouchOffsets(mi_scene& S, const typename Q::Item* d_items, uint64_t* d_incl, size_t n, hipStream_t stream) {
@@ -211,7 +213,7 @@ void launchTouchOffsets(mi_scene& S, const typename Q::Item* d_items, uint64_t* 
   });
 }
 
-// Box and contact lists, step 2 (mi_box_fill_device / mi_tri_fill_device): touch_fill_kernel, one thread per item. itemBase: the
+// Touch lists, step 2 (mi_X_fill_device): touch_fill_kernel, one thread per item. itemBase: the
 // index of the launch's first item in the caller's numbering (the host entry's batches).
 template <class Q>
 void launchTouchFill(mi_scene& S, const typename Q::Item* d_items, const uint64_t* d_offsets, typename Q::Record* d_hits, size_t capacity, uint32_t itemBase, size_t n, hipStream_t stream) {
@@ -233,11 +235,6 @@ struct BufferRule { const void* p; size_t align; const char* why; };
 constexpr const char* kBuffers16 = "buffers must be 16-byte aligned";
 constexpr const char* kRays16 = "rays must be 16-byte aligned";
 constexpr const char* kPoints16 = "points must be 16-byte aligned";
-constexpr const char* kBoxes16 = "boxes must be 16-byte aligned";
-constexpr const char* kTris4 = "triangles must be 4-byte aligned";
-constexpr const char* kOBoxes16 = "oriented boxes must be 16-byte aligned";
-constexpr const char* kCapsules16 = "capsules must be 16-byte aligned";
-constexpr const char* kFrusta16 = "frusta must be 16-byte aligned";
 constexpr size_t kNoLimit = ~(size_t)0;      // (a host entry: its limit is per batch, hostBatch)
 
 // The argument rules of every query entry, in the order the entries have always applied them: the scene, the kind (kindBad: the
@@ -279,33 +276,21 @@ bool pointSignBad(const char* fn, const mi_scene* scene, int kind, const void* p
   return queryArgsBad(fn, scene, kind != MI_SIGN_INSIDE && kind != MI_SIGN_DISTANCE ? "unknown sign kind" : nullptr, dir, n, limit, "points",
                       {{points, 16, kBuffers16}, {out, kind == MI_SIGN_DISTANCE ? 16u : 1u, kBuffers16}});
 }
-bool boxQueryBad(const char* fn, const mi_scene* scene, int kind, const void* boxes, const void* out, size_t n, size_t limit) {
-  return queryArgsBad(fn, scene, kind != MI_BOX_ANY && kind != MI_BOX_COUNT ? "unknown box kind" : nullptr, nullptr, n, limit, "boxes",
-                      {{boxes, 16, kBoxes16}, {out, kind == MI_BOX_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
-}
-bool triQueryBad(const char* fn, const mi_scene* scene, int kind, const void* tris, const void* out, size_t n, size_t limit) {
-  return queryArgsBad(fn, scene, kind != MI_TRI_ANY && kind != MI_TRI_COUNT ? "unknown triangle kind" : nullptr, nullptr, n, limit, "triangles",
-                      {{tris, 4, kTris4}, {out, kind == MI_TRI_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
-}
-bool oboxQueryBad(const char* fn, const mi_scene* scene, int kind, const void* oboxes, const void* out, size_t n, size_t limit) {
-  return queryArgsBad(fn, scene, kind != MI_OBOX_ANY && kind != MI_OBOX_COUNT ? "unknown oriented-box kind" : nullptr, nullptr, n, limit, "oriented boxes",
-                      {{oboxes, 16, kOBoxes16}, {out, kind == MI_OBOX_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
-}
-bool capsuleQueryBad(const char* fn, const mi_scene* scene, int kind, const void* capsules, const void* out, size_t n, size_t limit) {
-  return queryArgsBad(fn, scene, kind != MI_CAPSULE_ANY && kind != MI_CAPSULE_COUNT ? "unknown capsule kind" : nullptr, nullptr, n, limit, "capsules",
-                      {{capsules, 16, kCapsules16}, {out, kind == MI_CAPSULE_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
-}
-bool frustumQueryBad(const char* fn, const mi_scene* scene, int kind, const void* frusta, const void* out, size_t n, size_t limit) {
-  return queryArgsBad(fn, scene, kind != MI_FRUSTUM_ANY && kind != MI_FRUSTUM_COUNT ? "unknown frustum kind" : nullptr, nullptr, n, limit, "frusta",
-                      {{frusta, 16, kFrusta16}, {out, kind == MI_FRUSTUM_COUNT ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
-}
-// (the entries of the crossing lists, the neighbour lists, the box lists, the contact lists, the oriented-box lists, the capsule
-// lists and the frustum lists: `in` the rays, the points, the boxes, the oriented boxes, the capsules, the frusta - 16-byte aligned -
-// or the triangles - inAlign = 4; hits: only the fill's)
+// (the entries of the lists: `in` the rays, the points or a touch family's items - inAlign bytes aligned; hits: only the fill's)
 bool listQueryBad(const char* fn, const mi_scene* scene, const char* noun, const char* inWhy, const void* in, const void* offsets, const void* hits, bool fill, size_t n, size_t limit,
                   size_t inAlign = 16) {
   return queryArgsBad(fn, scene, nullptr, nullptr, n, limit, noun,
                       {{in, inAlign, inWhy}, {offsets, 8, "offsets must be 8-byte aligned"}, {hits, fill ? 16u : 0u, "hits must be 16-byte aligned"}});
+}
+// (a touch family's entries: the unknown kind's message, the noun, the items' alignment and its message are Q's)
+template <class Q>
+bool touchQueryBad(const char* fn, const mi_scene* scene, int kind, const void* items, const void* out, size_t n, size_t limit) {
+  return queryArgsBad(fn, scene, kind != Q::kAny && kind != Q::kCount ? Q::kKindBad : nullptr, nullptr, n, limit, Q::kNoun,
+                      {{items, Q::kAlign, Q::kAlignBad}, {out, kind == Q::kCount ? 4u : 1u, "counts must be 4-byte aligned"}});      // (the bytes of ANY lie anywhere)
+}
+template <class Q>
+bool touchListBad(const char* fn, const mi_scene* scene, const void* items, const void* offsets, const void* hits, bool fill, size_t n, size_t limit) {
+  return listQueryBad(fn, scene, Q::kNoun, Q::kAlignBad, items, offsets, hits, fill, n, limit, Q::kAlign);
 }
 
 // The direction of an inside test: the caller's three floats or the default.
@@ -329,10 +314,9 @@ size_t hostBatch(const char* fn, const char* noun, const mi_scene* scene, size_t
 }
 
 // The device buffers and streams of the pipeline's slots: kept by the scene between calls, regrown when a batch is larger than
-// any before. A slot holds `batch` items in - sized for the largest, the 96-byte frustum; an oriented box is 48 bytes, a triangle 36,
-// rays, points, boxes and capsules are 32 - and `batch` 32-byte records out: room for any of the results, or batch + 1 offsets.
-// kQueryItemBytes sizes these input slots and nothing else.
-constexpr size_t kQueryItemBytes = std::max({sizeof(mi_ray), sizeof(mi_point), sizeof(mi_box), sizeof(mi_tri), sizeof(mi_obox), sizeof(mi_capsule), sizeof(mi_frustum)});
+// any before. A slot holds `batch` items in - sized for the largest item of any family, today the 96-byte frustum - and `batch`
+// 32-byte records out: room for any of the results, or batch + 1 offsets. kQueryItemBytes sizes these input slots and nothing else.
+constexpr size_t kQueryItemBytes = std::max({sizeof(mi_ray), sizeof(mi_point), TouchFamilies::itemBytes});
 static_assert(kQueryItemBytes == 96, "the pipeline's input slots hold the largest item, mi_frustum");
 void ensureQuerySlots(mi_scene* scene, size_t batch, int slots) {
   for (int i = 0; i < slots; ++i) {
@@ -369,8 +353,8 @@ void pipelinedQuery(mi_scene* scene, const void* in, size_t inSize, void* out, s
   } catch (...) { (void)hipDeviceSynchronize(); throw; }
 }
 
-// mi_list_offsets, mi_near_offsets, mi_box_offsets, mi_tri_offsets, mi_obox_offsets, mi_capsule_offsets and mi_frustum_offsets on host buffers: every batch's prefix sum starts at 0 on the device; what precedes the
-// batch is added here, batch by batch.
+// mi_list_offsets, mi_near_offsets and the touch families' mi_X_offsets on host buffers: every batch's prefix sum starts at 0 on
+// the device; what precedes the batch is added here, batch by batch.
 template <class Launch>
 void offsetsHost(mi_scene* scene, const void* in, size_t inSize, uint64_t* offsets, size_t n, size_t batch, const Launch& launch) {
   offsets[0] = 0;
@@ -382,7 +366,8 @@ void offsetsHost(mi_scene* scene, const void* in, size_t inSize, uint64_t* offse
   }
 }
 
-// mi_list_fill, mi_near_fill, mi_box_fill, mi_tri_fill, mi_obox_fill, mi_capsule_fill and mi_frustum_fill on host buffers (in: rays, points, boxes, triangles, oriented boxes, capsules or frusta of inSize bytes; hits: 16-byte records of any of the kinds;
+// mi_list_fill, mi_near_fill and the touch families' mi_X_fill on host buffers (in: items of inSize bytes; hits: 16-byte records of
+// any of the kinds;
 // launch(d_in, d_offsets, d_hits, capacity, base, cnt, stream) enqueues one batch's fill): the pipeline's slots - the result buffer
 // carries a batch's offsets in - plus a staging buffer of records per slot. A batch's segments are packed from 0 in the staging -
 // the device sees offsets of its own, cut at `capacity` here already - and copied to where the caller's offsets put them: in one
@@ -441,6 +426,71 @@ int deviceEntry(mi_scene* scene, const Launch& launch) {
   return guarded([&] {
     HIP_CHECK(hipSetDevice(scene->device));
     launch();
+  });
+}
+
+// The six entries of a touch family Q. fn: a device entry's name (the host entries' are Q::kQuery, Q::kOffsets, Q::kFill).
+template <class Q>
+int touchQueryDevice(const char* fn, mi_scene* scene, int kind, const void* d_items, void* d_out, size_t n, void* hip_stream) {
+  if (touchQueryBad<Q>(fn, scene, kind, d_items, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] { launchTouchQuery<Q>(*scene, kind, static_cast<const typename Q::Item*>(d_items), d_out, n, (hipStream_t)hip_stream); });
+}
+
+template <class Q>
+int touchQueryHostEntry(mi_scene* scene, int kind, const typename Q::Item* items, void* out, size_t n) {
+  if (touchQueryBad<Q>(Q::kQuery, scene, kind, items, out, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch(Q::kQuery, Q::kNoun, scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    pipelinedQuery(scene, items, sizeof(typename Q::Item), out, kind == Q::kAny ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchTouchQuery<Q>(*scene, kind, static_cast<const typename Q::Item*>(d_in), d_out, cnt, st);
+    });
+  });
+}
+
+template <class Q>
+int touchOffsetsDevice(const char* fn, mi_scene* scene, const void* d_items, uint64_t* d_offsets, size_t n, void* hip_stream) {
+  if (touchListBad<Q>(fn, scene, d_items, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] {
+    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
+    launchTouchOffsets<Q>(*scene, static_cast<const typename Q::Item*>(d_items), d_offsets + 1, n, (hipStream_t)hip_stream);
+  });
+}
+
+template <class Q>
+int touchFillDevice(const char* fn, mi_scene* scene, const void* d_items, const uint64_t* d_offsets, typename Q::Record* d_hits, size_t capacity, size_t n, void* hip_stream) {
+  if (touchListBad<Q>(fn, scene, d_items, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  return deviceEntry(scene, [&] { launchTouchFill<Q>(*scene, static_cast<const typename Q::Item*>(d_items), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
+}
+
+template <class Q>
+int touchOffsetsHostEntry(mi_scene* scene, const typename Q::Item* items, uint64_t* offsets, size_t n) {
+  if (touchListBad<Q>(Q::kOffsets, scene, items, offsets, nullptr, false, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch(Q::kOffsets, Q::kNoun, scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    offsetsHost(scene, items, sizeof(typename Q::Item), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
+      launchTouchOffsets<Q>(*scene, static_cast<const typename Q::Item*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
+    });
+  });
+}
+
+template <class Q>
+int touchFillHostEntry(mi_scene* scene, const typename Q::Item* items, const uint64_t* offsets, typename Q::Record* hits, size_t capacity, size_t n) {
+  if (touchListBad<Q>(Q::kFill, scene, items, offsets, hits, true, n, kNoLimit)) return MI_ERR_INVALID_ARG;
+  if (n == 0) return MI_OK;
+  const size_t batch = hostBatch(Q::kFill, Q::kNoun, scene, n);
+  if (!batch) return MI_ERR_INVALID_ARG;
+  return guarded([&] {
+    listFillHost(scene, items, sizeof(typename Q::Item), offsets, hits, capacity, n, batch,
+                 [&](const void* d_in, const uint64_t* d_off, typename Q::Record* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
+      launchTouchFill<Q>(*scene, static_cast<const typename Q::Item*>(d_in), d_off, d_hits, cap, base, cnt, st);
+    });
   });
 }
 
@@ -598,289 +648,27 @@ int mi_near_fill(mi_scene* scene, const mi_point* points, const uint64_t* offset
   });
 }
 
-int mi_box_query_device(mi_scene* scene, int kind, const void* d_boxes, void* d_out, size_t n, void* hip_stream) {
-  if (boxQueryBad("mi_box_query_device", scene, kind, d_boxes, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchQuery<BoxTouch>(*scene, kind, static_cast<const mi_box*>(d_boxes), d_out, n, (hipStream_t)hip_stream); });
-}
-
-int mi_box_query(mi_scene* scene, int kind, const mi_box* boxes, void* out, size_t n) {
-  if (boxQueryBad("mi_box_query", scene, kind, boxes, out, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_box_query", "boxes", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    pipelinedQuery(scene, boxes, sizeof(mi_box), out, kind == MI_BOX_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchQuery<BoxTouch>(*scene, kind, static_cast<const mi_box*>(d_in), d_out, cnt, st);
-    });
-  });
-}
-
-int mi_box_offsets_device(mi_scene* scene, const void* d_boxes, uint64_t* d_offsets, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_box_offsets_device", scene, "boxes", kBoxes16, d_boxes, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] {
-    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
-    launchTouchOffsets<BoxTouch>(*scene, static_cast<const mi_box*>(d_boxes), d_offsets + 1, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_box_fill_device(mi_scene* scene, const void* d_boxes, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_box_fill_device", scene, "boxes", kBoxes16, d_boxes, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchFill<BoxTouch>(*scene, static_cast<const mi_box*>(d_boxes), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
-}
-
-int mi_box_offsets(mi_scene* scene, const mi_box* boxes, uint64_t* offsets, size_t n) {
-  if (listQueryBad("mi_box_offsets", scene, "boxes", kBoxes16, boxes, offsets, nullptr, false, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_box_offsets", "boxes", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    offsetsHost(scene, boxes, sizeof(mi_box), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchOffsets<BoxTouch>(*scene, static_cast<const mi_box*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
-    });
-  });
-}
-
-int mi_box_fill(mi_scene* scene, const mi_box* boxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n) {
-  if (listQueryBad("mi_box_fill", scene, "boxes", kBoxes16, boxes, offsets, hits, true, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_box_fill", "boxes", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    listFillHost(scene, boxes, sizeof(mi_box), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_overlap* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
-      launchTouchFill<BoxTouch>(*scene, static_cast<const mi_box*>(d_in), d_off, d_hits, cap, base, cnt, st);
-    });
-  });
-}
-
-int mi_tri_query_device(mi_scene* scene, int kind, const void* d_tris, void* d_out, size_t n, void* hip_stream) {
-  if (triQueryBad("mi_tri_query_device", scene, kind, d_tris, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchQuery<TriTouch>(*scene, kind, static_cast<const mi_tri*>(d_tris), d_out, n, (hipStream_t)hip_stream); });
-}
-
-int mi_tri_query(mi_scene* scene, int kind, const mi_tri* tris, void* out, size_t n) {
-  if (triQueryBad("mi_tri_query", scene, kind, tris, out, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_tri_query", "triangles", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    pipelinedQuery(scene, tris, sizeof(mi_tri), out, kind == MI_TRI_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchQuery<TriTouch>(*scene, kind, static_cast<const mi_tri*>(d_in), d_out, cnt, st);
-    });
-  });
-}
-
-int mi_tri_offsets_device(mi_scene* scene, const void* d_tris, uint64_t* d_offsets, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_tri_offsets_device", scene, "triangles", kTris4, d_tris, d_offsets, nullptr, false, n, kMaxWorkItems, 4)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] {
-    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
-    launchTouchOffsets<TriTouch>(*scene, static_cast<const mi_tri*>(d_tris), d_offsets + 1, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_tri_fill_device(mi_scene* scene, const void* d_tris, const uint64_t* d_offsets, mi_contact* d_hits, size_t capacity, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_tri_fill_device", scene, "triangles", kTris4, d_tris, d_offsets, d_hits, true, n, kMaxWorkItems, 4)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchFill<TriTouch>(*scene, static_cast<const mi_tri*>(d_tris), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
-}
-
-int mi_tri_offsets(mi_scene* scene, const mi_tri* tris, uint64_t* offsets, size_t n) {
-  if (listQueryBad("mi_tri_offsets", scene, "triangles", kTris4, tris, offsets, nullptr, false, n, kNoLimit, 4)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_tri_offsets", "triangles", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    offsetsHost(scene, tris, sizeof(mi_tri), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchOffsets<TriTouch>(*scene, static_cast<const mi_tri*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
-    });
-  });
-}
-
-int mi_tri_fill(mi_scene* scene, const mi_tri* tris, const uint64_t* offsets, mi_contact* hits, size_t capacity, size_t n) {
-  if (listQueryBad("mi_tri_fill", scene, "triangles", kTris4, tris, offsets, hits, true, n, kNoLimit, 4)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_tri_fill", "triangles", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    listFillHost(scene, tris, sizeof(mi_tri), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_contact* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
-      launchTouchFill<TriTouch>(*scene, static_cast<const mi_tri*>(d_in), d_off, d_hits, cap, base, cnt, st);
-    });
-  });
-}
-
-int mi_obox_query_device(mi_scene* scene, int kind, const void* d_oboxes, void* d_out, size_t n, void* hip_stream) {
-  if (oboxQueryBad("mi_obox_query_device", scene, kind, d_oboxes, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchQuery<OBoxTouch>(*scene, kind, static_cast<const mi_obox*>(d_oboxes), d_out, n, (hipStream_t)hip_stream); });
-}
-
-int mi_obox_query(mi_scene* scene, int kind, const mi_obox* oboxes, void* out, size_t n) {
-  if (oboxQueryBad("mi_obox_query", scene, kind, oboxes, out, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_obox_query", "oriented boxes", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    pipelinedQuery(scene, oboxes, sizeof(mi_obox), out, kind == MI_OBOX_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchQuery<OBoxTouch>(*scene, kind, static_cast<const mi_obox*>(d_in), d_out, cnt, st);
-    });
-  });
-}
-
-int mi_obox_offsets_device(mi_scene* scene, const void* d_oboxes, uint64_t* d_offsets, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_obox_offsets_device", scene, "oriented boxes", kOBoxes16, d_oboxes, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] {
-    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
-    launchTouchOffsets<OBoxTouch>(*scene, static_cast<const mi_obox*>(d_oboxes), d_offsets + 1, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_obox_fill_device(mi_scene* scene, const void* d_oboxes, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_obox_fill_device", scene, "oriented boxes", kOBoxes16, d_oboxes, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchFill<OBoxTouch>(*scene, static_cast<const mi_obox*>(d_oboxes), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
-}
-
-int mi_obox_offsets(mi_scene* scene, const mi_obox* oboxes, uint64_t* offsets, size_t n) {
-  if (listQueryBad("mi_obox_offsets", scene, "oriented boxes", kOBoxes16, oboxes, offsets, nullptr, false, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_obox_offsets", "oriented boxes", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    offsetsHost(scene, oboxes, sizeof(mi_obox), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchOffsets<OBoxTouch>(*scene, static_cast<const mi_obox*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
-    });
-  });
-}
-
-int mi_obox_fill(mi_scene* scene, const mi_obox* oboxes, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n) {
-  if (listQueryBad("mi_obox_fill", scene, "oriented boxes", kOBoxes16, oboxes, offsets, hits, true, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_obox_fill", "oriented boxes", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    listFillHost(scene, oboxes, sizeof(mi_obox), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_overlap* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
-      launchTouchFill<OBoxTouch>(*scene, static_cast<const mi_obox*>(d_in), d_off, d_hits, cap, base, cnt, st);
-    });
-  });
-}
-
-int mi_capsule_query_device(mi_scene* scene, int kind, const void* d_capsules, void* d_out, size_t n, void* hip_stream) {
-  if (capsuleQueryBad("mi_capsule_query_device", scene, kind, d_capsules, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchQuery<CapsuleTouch>(*scene, kind, static_cast<const mi_capsule*>(d_capsules), d_out, n, (hipStream_t)hip_stream); });
-}
-
-int mi_capsule_query(mi_scene* scene, int kind, const mi_capsule* capsules, void* out, size_t n) {
-  if (capsuleQueryBad("mi_capsule_query", scene, kind, capsules, out, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_capsule_query", "capsules", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    pipelinedQuery(scene, capsules, sizeof(mi_capsule), out, kind == MI_CAPSULE_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchQuery<CapsuleTouch>(*scene, kind, static_cast<const mi_capsule*>(d_in), d_out, cnt, st);
-    });
-  });
-}
-
-int mi_capsule_offsets_device(mi_scene* scene, const void* d_capsules, uint64_t* d_offsets, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_capsule_offsets_device", scene, "capsules", kCapsules16, d_capsules, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] {
-    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
-    launchTouchOffsets<CapsuleTouch>(*scene, static_cast<const mi_capsule*>(d_capsules), d_offsets + 1, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_capsule_fill_device(mi_scene* scene, const void* d_capsules, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_capsule_fill_device", scene, "capsules", kCapsules16, d_capsules, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchFill<CapsuleTouch>(*scene, static_cast<const mi_capsule*>(d_capsules), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
-}
-
-int mi_capsule_offsets(mi_scene* scene, const mi_capsule* capsules, uint64_t* offsets, size_t n) {
-  if (listQueryBad("mi_capsule_offsets", scene, "capsules", kCapsules16, capsules, offsets, nullptr, false, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_capsule_offsets", "capsules", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    offsetsHost(scene, capsules, sizeof(mi_capsule), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchOffsets<CapsuleTouch>(*scene, static_cast<const mi_capsule*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
-    });
-  });
-}
-
-int mi_capsule_fill(mi_scene* scene, const mi_capsule* capsules, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n) {
-  if (listQueryBad("mi_capsule_fill", scene, "capsules", kCapsules16, capsules, offsets, hits, true, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_capsule_fill", "capsules", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    listFillHost(scene, capsules, sizeof(mi_capsule), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_overlap* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
-      launchTouchFill<CapsuleTouch>(*scene, static_cast<const mi_capsule*>(d_in), d_off, d_hits, cap, base, cnt, st);
-    });
-  });
-}
-
-int mi_frustum_query_device(mi_scene* scene, int kind, const void* d_frusta, void* d_out, size_t n, void* hip_stream) {
-  if (frustumQueryBad("mi_frustum_query_device", scene, kind, d_frusta, d_out, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchQuery<FrustumTouch>(*scene, kind, static_cast<const mi_frustum*>(d_frusta), d_out, n, (hipStream_t)hip_stream); });
-}
-
-int mi_frustum_query(mi_scene* scene, int kind, const mi_frustum* frusta, void* out, size_t n) {
-  if (frustumQueryBad("mi_frustum_query", scene, kind, frusta, out, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_frustum_query", "frusta", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    pipelinedQuery(scene, frusta, sizeof(mi_frustum), out, kind == MI_FRUSTUM_ANY ? 1 : sizeof(uint32_t), n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchQuery<FrustumTouch>(*scene, kind, static_cast<const mi_frustum*>(d_in), d_out, cnt, st);
-    });
-  });
-}
-
-int mi_frustum_offsets_device(mi_scene* scene, const void* d_frusta, uint64_t* d_offsets, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_frustum_offsets_device", scene, "frusta", kFrusta16, d_frusta, d_offsets, nullptr, false, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] {
-    HIP_CHECK(hipMemsetAsync(d_offsets, 0, sizeof(uint64_t), (hipStream_t)hip_stream));
-    launchTouchOffsets<FrustumTouch>(*scene, static_cast<const mi_frustum*>(d_frusta), d_offsets + 1, n, (hipStream_t)hip_stream);
-  });
-}
-
-int mi_frustum_fill_device(mi_scene* scene, const void* d_frusta, const uint64_t* d_offsets, mi_overlap* d_hits, size_t capacity, size_t n, void* hip_stream) {
-  if (listQueryBad("mi_frustum_fill_device", scene, "frusta", kFrusta16, d_frusta, d_offsets, d_hits, true, n, kMaxWorkItems)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  return deviceEntry(scene, [&] { launchTouchFill<FrustumTouch>(*scene, static_cast<const mi_frustum*>(d_frusta), d_offsets, d_hits, capacity, 0u, n, (hipStream_t)hip_stream); });
-}
-
-int mi_frustum_offsets(mi_scene* scene, const mi_frustum* frusta, uint64_t* offsets, size_t n) {
-  if (listQueryBad("mi_frustum_offsets", scene, "frusta", kFrusta16, frusta, offsets, nullptr, false, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_frustum_offsets", "frusta", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    offsetsHost(scene, frusta, sizeof(mi_frustum), offsets, n, batch, [&](void* d_in, void* d_out, size_t cnt, hipStream_t st) {
-      launchTouchOffsets<FrustumTouch>(*scene, static_cast<const mi_frustum*>(d_in), static_cast<uint64_t*>(d_out), cnt, st);
-    });
-  });
-}
-
-int mi_frustum_fill(mi_scene* scene, const mi_frustum* frusta, const uint64_t* offsets, mi_overlap* hits, size_t capacity, size_t n) {
-  if (listQueryBad("mi_frustum_fill", scene, "frusta", kFrusta16, frusta, offsets, hits, true, n, kNoLimit)) return MI_ERR_INVALID_ARG;
-  if (n == 0) return MI_OK;
-  const size_t batch = hostBatch("mi_frustum_fill", "frusta", scene, n);
-  if (!batch) return MI_ERR_INVALID_ARG;
-  return guarded([&] {
-    listFillHost(scene, frusta, sizeof(mi_frustum), offsets, hits, capacity, n, batch, [&](const void* d_in, const uint64_t* d_off, mi_overlap* d_hits, size_t cap, uint32_t base, size_t cnt, hipStream_t st) {
-      launchTouchFill<FrustumTouch>(*scene, static_cast<const mi_frustum*>(d_in), d_off, d_hits, cap, base, cnt, st);
-    });
-  });
-}
+// The touch families' entries: the bodies are the templates above, a family is one line.
+#define MI_TOUCH_ENTRIES(X, Q)                                                                                                                              \
+  int mi_##X##_query_device(mi_scene* scene, int kind, const void* d_items, void* d_out, size_t n, void* hip_stream) {                                      \
+    return touchQueryDevice<Q>("mi_" #X "_query_device", scene, kind, d_items, d_out, n, hip_stream);                                                       \
+  }                                                                                                                                                         \
+  int mi_##X##_query(mi_scene* scene, int kind, const Q::Item* items, void* out, size_t n) { return touchQueryHostEntry<Q>(scene, kind, items, out, n); }   \
+  int mi_##X##_offsets_device(mi_scene* scene, const void* d_items, uint64_t* d_offsets, size_t n, void* hip_stream) {                                      \
+    return touchOffsetsDevice<Q>("mi_" #X "_offsets_device", scene, d_items, d_offsets, n, hip_stream);                                                     \
+  }                                                                                                                                                         \
+  int mi_##X##_fill_device(mi_scene* scene, const void* d_items, const uint64_t* d_offsets, Q::Record* d_hits, size_t capacity, size_t n, void* hip_stream) { \
+    return touchFillDevice<Q>("mi_" #X "_fill_device", scene, d_items, d_offsets, d_hits, capacity, n, hip_stream);                                         \
+  }                                                                                                                                                         \
+  int mi_##X##_offsets(mi_scene* scene, const Q::Item* items, uint64_t* offsets, size_t n) { return touchOffsetsHostEntry<Q>(scene, items, offsets, n); }   \
+  int mi_##X##_fill(mi_scene* scene, const Q::Item* items, const uint64_t* offsets, Q::Record* hits, size_t capacity, size_t n) {                           \
+    return touchFillHostEntry<Q>(scene, items, offsets, hits, capacity, n);                                                                                 \
+  }
+MI_TOUCH_ENTRIES(box, BoxTouch)
+MI_TOUCH_ENTRIES(tri, TriTouch)
+MI_TOUCH_ENTRIES(obox, OBoxTouch)
+MI_TOUCH_ENTRIES(capsule, CapsuleTouch)
+MI_TOUCH_ENTRIES(frustum, FrustumTouch)
+#undef MI_TOUCH_ENTRIES
 
 }  // extern "C"

@@ -1,17 +1,28 @@
 // touch_kernels.hpp — the kernels of a "touch query": every primitive that TOUCHES a caller-supplied item, with no distance and
-// no order among the touching primitives but their key (geomID, primID). The box queries (box_kernels.hpp, Q = BoxTouch), the
-// triangle queries (contact_kernels.hpp, Q = TriTouch), the oriented-box queries (obox_kernels.hpp, Q = OBoxTouch), the capsule
-// queries (capsule_kernels.hpp, Q = CapsuleTouch) and the frustum queries (frustum_kernels.hpp, Q = FrustumTouch) are the five
-// there are; a family describes itself by a struct Q:
+// no order among the touching primitives but their key (geomID, primID). The families are the ones query_drivers.hpp lists in
+// TouchFamilies; a family describes itself once, by a shape S next to its arithmetic (BoxShape in box_math.hpp is the plainest),
+// which the kernels here and their host twins (host/touch_host.hpp) both walk with:
 //
-//   Q::Item, Q::Record                      what a batch holds (mi_box, mi_tri, mi_obox, mi_capsule, mi_frustum) and what a list holds (mi_overlap, mi_contact: 16
-//                                           bytes, {primID, geomID | flags << 16, item, 0})
-//   Q::Loaded, Q::load(items, idx)          item idx as the walk wants it, and its loads
+//   S::Item, S::Record                      what a batch holds and what a list holds (16 bytes: {primID, geomID | flags << 16, item, 0})
+//   S::Fields, S::fields(item)              the item's fields as the arithmetic takes them, from the C struct
+//   S::valid(fields)                        whether the item is walked at all
+//   S::Carried, S::carry(fields)            what a lane carries across the walk
+//   S::meets_bounds(mn, mx, carried)        whether a node's box is entered; a primitive's own bounds precede its test
+//   S::touches_prim(kind, f, carried, &contained)
+//   S::flags(contained)                     what a record of a touching primitive carries
+//   S::kAny, kCount, kNoun, kKindBad, kAlign, kAlignBad
+//                                           the kinds, and the words and the item alignment of the entries' argument rules
+//
+// and for the device by Q = the shape plus (box_kernels.hpp is the plainest)
+//
+//   Q::load(items, idx)                     item idx as the walk takes it: the width of the loads is the family's choice
 //   Q::walk<STATS>(sc, item, cs, accept)    the item's walk over walk_preorder (bvh_walk.hpp): accept(leaf index, geomID, flags) is
-//                                           called for each touching primitive, `flags` what a record of it carries; returning true
-//                                           ends the walk
-//   Q::kQuery, kOffsets, kFill, kNoun       the entries' names and the items' noun, for query_drivers.hpp's launchers
+//                                           called for each touching primitive; returning true ends the walk. SharedWalk<S> below
+//                                           supplies it from the shape; a family whose kernels would come out as other code
+//                                           through it keeps a walk of its own (DESIGN.md §38 names them)
+//   Q::kQuery, kOffsets, kFill              the entries' names, for query_drivers.hpp's launchers
 //
+//   touch_walk           walk_preorder with S::meets_bounds at the nodes and S::touches_prim at a reached leaf.
 //   touch_query_kernel   one thread per item: a byte (ANY: the walk stops at the first accept) or a uint32 count.
 //   touch_count_kernel   one thread per item: the count as 64 bits (scan_*_kernel of list_kernels.hpp then runs in place on them).
 //   touch_fill_kernel    (key_heap_fill) one thread per item, into the item's OWN segment [offsets[i], offsets[i + 1]) cut at
@@ -23,7 +34,7 @@
 //                        and padded. Keys are unique within an item, so the bytes do not depend on the visit order. An item whose
 //                        segment is empty is not walked.
 // No LDS, no stack, no per-lane array, no scratch: a lane carries the item, the segment's base and length, the number of records
-// held, the root's key and the record being placed. The host twins are host/touch_host.hpp.
+// held, the root's key and the record being placed.
 #pragma once
 
 #include "bvh_walk.hpp"
@@ -37,6 +48,28 @@ __device__ __forceinline__ uint4 overlap_words(uint32_t primID, uint32_t geomID,
   return make_uint4(primID, geomID | (flags << 16), item, 0u);
 }
 __device__ __forceinline__ uint64_t overlap_key_of(const uint4& r) { return overlap_key(r.y & 0xFFFFu, r.x); }
+
+// The walk of one item. The node test's result selects between nd.hit and nd.link: a family writes it with & and |, never && and ||,
+// where a short-circuit would have the compiler branch around that select.
+template <class S, bool STATS, class Accept>
+__device__ __forceinline__ void touch_walk(const DeviceScene& sc, const typename S::Fields& item, CastStats& cs, const Accept& accept) {
+  const auto& q = S::carry(item);
+  walk_preorder<STATS>(sc, S::valid(item), cs,
+    [&](const GNode& nd) { return S::meets_bounds(mk(nd.minx, nd.miny, nd.minz), mk(nd.maxx, nd.maxy, nd.maxz), q); },
+    [&](uint32_t at, uint32_t type, const float (&f)[9]) {
+      bool contained;
+      return S::touches_prim(type & 0xFFFFu, f, q, &contained) && accept(at, type >> 16, S::flags(contained));
+    });
+}
+
+// The device side of a family that walks through touch_walk: its Q is this plus load and the entries' names.
+template <class S>
+struct SharedWalk : S {
+  template <bool STATS, class Accept>
+  static __device__ __forceinline__ void walk(const DeviceScene& sc, const typename S::Fields& item, CastStats& cs, const Accept& accept) {
+    touch_walk<S, STATS>(sc, item, cs, accept);
+  }
+};
 
 // COUNT: out = n uint32_t, the number of touching primitives; otherwise n bytes, 1 when there is one.
 template <class Q, bool COUNT, bool STATS>

@@ -1,15 +1,5 @@
 #!/bin/bash
-# The host twin of rigid poses (mi_pose_geometry_host) under AddressSanitizer + UndefinedBehaviorSanitizer: the host library's
-# sources and tools/sanitize_pose.c (a stand-alone program with its own main) built with -fsanitize=address,undefined into one
-# executable, which is run from the repository root. CPU only; nothing is loaded into python.
+# The host twin of rigid poses (mi_pose_geometry_host) under AddressSanitizer + UndefinedBehaviorSanitizer:
+# tools/sanitize_pose.c built and run by tools/sanitize_standalone.sh. CPU only; nothing is loaded into python.
 #   tools/sanitize_pose.sh
-set -e
-R=$(cd "$(dirname "$0")/.." && pwd)
-mkdir -p $R/build/san
-H=$R/ipu_ray_lib_amd/csrc/host
-SAN="-O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined"
-gcc -std=c11 $SAN -Wall -I $R/include -c -o $R/build/san/sanitize_pose.o $R/tools/sanitize_pose.c
-g++ -std=c++17 $SAN -ffp-contract=off -fno-fast-math -Wall -o $R/build/san/sanitize_pose $R/build/san/sanitize_pose.o \
-    $H/bvh_sah.cpp $H/lbvh.cpp $H/glb_reader.cpp $H/dae_reader.cpp $H/scene_builtin.cpp $H/scene_api.cpp $H/nif_assets.cpp $H/walk_table.cpp $H/point_query_host.cpp $H/box_query_host.cpp $H/tri_query_host.cpp $H/obox_query_host.cpp $H/capsule_query_host.cpp $H/frustum_query_host.cpp $H/pose_host.cpp $H/cross_host.cpp $H/hot_order.cpp $H/leaf_frame.cpp -ldl -lm
-cd $R
-ASAN_OPTIONS=detect_leaks=1:abort_on_error=1 UBSAN_OPTIONS=print_stacktrace=1 $R/build/san/sanitize_pose $R/assets/monkey_bust.glb
+exec "$(dirname "$0")/sanitize_standalone.sh" pose
